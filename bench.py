@@ -12,12 +12,17 @@ For N > 1 every frame is sharded by interleaved 8-row screen tiles across the N
 GPUs (tree replicated) and the RGBA8 tiles are gathered to rank 0 with one RCCL
 gather per frame, pipelined one frame deep ("strong" scaling: total work fixed).
 
-Prints ONE JSON line on rank 0 (metric = Mrays/s; FPS rides along), including
+Prints ONE JSON line on rank 0 (metric = Mrays/s; FPS and ms_per_step ride along).
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.
+With --full the line also carries what takes work of its own outside the timed steps:
   roofline     -- algorithmic bytes per launch (instrumented kernel flavour,
                   counted once per pose OUTSIDE the timed region) / mean kernel
                   duration measured with HIP events on the launch stream
+  parity       -- frames of the timed region against the CPU oracle
+  repeats / ms_per_step_cold -- the K-step region again: noise floor, idle-GPU start
   cpu_baseline -- the CPU oracle (kind "port") timed on a bounded sample of the
                   same frame on the host cores (rank 0, N=1 only).
+--dump-outputs DIR writes the frame of the last timed step as DIR/rgba.npy (float32).
 """
 from __future__ import annotations
 
@@ -44,7 +49,8 @@ VALU_ISSUE_CYCLES = 4.0       # flat price of a wave64 vector instruction (what 
                               # (tools/isa_issue_model.py), t_issue_flat4_ms this flat price
 ROUND_FLOOR_US = 0.62         # a dependent march round of a lone wave on an otherwise idle SIMD: 1300-1500
                               # shader clocks (profiles/r04_tail_profile.jsonl, the last buckets of a one-frame launch)
-CACHE_DIR = os.environ.get("VOLREND_BENCH_CACHE", "/dev/shm/volrend_amd_cache")
+# per user: on a shared host another user's cache directory is not writable
+CACHE_DIR = os.environ.get("VOLREND_BENCH_CACHE", f"/dev/shm/volrend_amd_cache_{os.getuid()}")
 
 
 def log(*a):
@@ -357,7 +363,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=5,
                     help="after the timed region, the identical K-step region is run this many more "
                          "times (not part of value / ms_per_step): the line's own noise floor")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what needs work outside the timed steps: roofline and "
+                         "scheduler counters, parity with the CPU oracle, --repeats, --cold, the sharded-frame "
+                         "self-check, --live-traffic and the CPU baselines (a plain run does none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the frame of the last timed step as DIR/rgba.npy (float32, HxWx4, 0..255)")
     args = ap.parse_args()
+    full = args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # plain `python bench.py --gpus N`: become the launcher (one process per GPU), relay the line
@@ -561,47 +574,48 @@ def main():
     run(n_streams * B, 0)
     torch.cuda.synchronize()
 
-    # ---- algorithmic bytes: instrumented flavour, outside the timed region -----
+    # ---- algorithmic bytes: instrumented flavour, outside the timed region (--full) -----
     K = args.steps
     n_distinct = min(K, len(transforms))
-    counters = torch.zeros((B, 7), dtype=torch.int64, device=dev)
-    scratch = [torch.zeros((H, W, 4), dtype=torch.uint8, device=dev) for _ in range(B)]
-    full = api.TileShard(tile_w, tile_h, s_rank, s_world, compact=False)
-    # B_unique: distinct 128-byte lines of the tree arrays that the accesses of one
-    # launch / one frame touch -- the compulsory-traffic lower bound next to the algorithmic bytes
-    # (distinct-line bitmaps of the instrumented flavour, vr_touch_enable / vr_touch_count)
-    tree.touch_enable(True)
-    unique_launch = None
-    jd = 0
-    while jd < n_distinct:  # same batching as the timed region
-        n = min(B, n_distinct - jd)
-        tr = [pose_of(args.warmup + jd + i) for i in range(n)]
-        api.launch_renderer_batch(tree, cam, tr, opts, scratch[:n], stream, True, shard=full,
-                                  fp_mode=fp_mode, counters=[counters[i] for i in range(n)])
-        if jd == 0:
-            unique_launch = (n, tree.touch_count(reset=True))
-        jd += n
-    tree.touch_count(reset=True)
-    torch.cuda.synchronize()
-    sched = tree.sched_stats()  # of the launches above only: the timed region's poses and batching
-    unique_frames = []
-    side = torch.zeros((1, 7), dtype=torch.int64, device=dev)
-    for i in range(4):  # four single frames spread over the timed poses
-        tr = [pose_of(args.warmup + (i * n_distinct) // 4)]
-        api.launch_renderer_batch(tree, cam, tr, opts, scratch[:1], stream, True, shard=full,
-                                  fp_mode=fp_mode, counters=[side[0]])
-        unique_frames.append(tree.touch_count(reset=True))
-    tree.touch_enable(False)
-    del side
-    torch.cuda.synchronize()
-    cnt = dict(zip(_abi.COUNTER_FIELDS, [int(v) for v in counters.sum(dim=0).cpu().tolist()]))
-    alg_bytes_per_frame = cnt["alg_bytes"] / n_distinct  # this rank's share of a frame
-    tree.sched_stats()  # (drop the four single-frame launches)
-    log(f"[bench r{rank}] sched per frame: " + ", ".join(
-        f"{k}={v / n_distinct:.0f}" for k, v in sched.items()) +
-        f"; march util {sched['march_lanes'] / max(64 * sched['march_rounds'], 1):.2f}"
-        f", shade util {sched['shade_lanes'] / max(64 * sched['shade_rounds'], 1):.2f}")
-    del scratch
+    if full:
+        counters = torch.zeros((B, 7), dtype=torch.int64, device=dev)
+        scratch = [torch.zeros((H, W, 4), dtype=torch.uint8, device=dev) for _ in range(B)]
+        whole = api.TileShard(tile_w, tile_h, s_rank, s_world, compact=False)
+        # B_unique: distinct 128-byte lines of the tree arrays that the accesses of one
+        # launch / one frame touch -- the compulsory-traffic lower bound next to the algorithmic bytes
+        # (distinct-line bitmaps of the instrumented flavour, vr_touch_enable / vr_touch_count)
+        tree.touch_enable(True)
+        unique_launch = None
+        jd = 0
+        while jd < n_distinct:  # same batching as the timed region
+            n = min(B, n_distinct - jd)
+            tr = [pose_of(args.warmup + jd + i) for i in range(n)]
+            api.launch_renderer_batch(tree, cam, tr, opts, scratch[:n], stream, True, shard=whole,
+                                      fp_mode=fp_mode, counters=[counters[i] for i in range(n)])
+            if jd == 0:
+                unique_launch = (n, tree.touch_count(reset=True))
+            jd += n
+        tree.touch_count(reset=True)
+        torch.cuda.synchronize()
+        sched = tree.sched_stats()  # of the launches above only: the timed region's poses and batching
+        unique_frames = []
+        side = torch.zeros((1, 7), dtype=torch.int64, device=dev)
+        for i in range(4):  # four single frames spread over the timed poses
+            tr = [pose_of(args.warmup + (i * n_distinct) // 4)]
+            api.launch_renderer_batch(tree, cam, tr, opts, scratch[:1], stream, True, shard=whole,
+                                      fp_mode=fp_mode, counters=[side[0]])
+            unique_frames.append(tree.touch_count(reset=True))
+        tree.touch_enable(False)
+        del side
+        torch.cuda.synchronize()
+        cnt = dict(zip(_abi.COUNTER_FIELDS, [int(v) for v in counters.sum(dim=0).cpu().tolist()]))
+        alg_bytes_per_frame = cnt["alg_bytes"] / n_distinct  # this rank's share of a frame
+        tree.sched_stats()  # (drop the four single-frame launches)
+        log(f"[bench r{rank}] sched per frame: " + ", ".join(
+            f"{k}={v / n_distinct:.0f}" for k, v in sched.items()) +
+            f"; march util {sched['march_lanes'] / max(64 * sched['march_rounds'], 1):.2f}"
+            f", shade util {sched['shade_lanes'] / max(64 * sched['shade_rounds'], 1):.2f}")
+        del scratch
 
     # ---- timed region ----------------------------------------------------------
     n_launch = (K + B - 1) // B
@@ -629,12 +643,16 @@ def main():
     elapsed = time.perf_counter() - t_start
 
     # frames of the LAST timed launch stay in their buffer set: first and last of them are
-    # compared with the oracle after the clock has stopped
+    # compared with the oracle after the clock has stopped (--full), the last one is the output of
+    # the last timed step (--dump-outputs)
+    j_last = n_launch - 1
+    first_last = args.warmup + j_last * B
+    n_last = K - j_last * B
+    last_frame = None
+    if rank == 0 and args.dump_outputs:
+        last_frame = frame_sets[j_last % 2][n_last - 1].cpu().numpy()
     parity_frames = []
-    if rank == 0 and not args.no_parity and not replicas:
-        j_last = n_launch - 1
-        first_last = args.warmup + j_last * B
-        n_last = K - j_last * B
+    if full and rank == 0 and not args.no_parity and not replicas:
         for i in sorted({0, n_last - 1}):
             parity_frames.append((first_last + i, pose_of(first_last + i),
                                   frame_sets[j_last % 2][i].cpu().numpy()))
@@ -642,7 +660,7 @@ def main():
     # ---- the line's own noise floor: the identical K-step region, R more times (same poses, same
     # prepared launches, same barriers; none of it enters value / ms_per_step) ----
     repeat_ms = []
-    for _ in range(max(args.repeats, 0)):
+    for _ in range(max(args.repeats, 0) if full else 0):
         barrier()
         torch.cuda.synchronize()
         t_rep = time.perf_counter()
@@ -659,7 +677,7 @@ def main():
     # ---- the same region out of an idle GPU: 50 ms without work, then the K steps (no pre-roll, no
     # warm-up in front: what a lone launch costs a caller that renders now and then) ----
     cold_ms = None
-    if args.cold:
+    if full and args.cold:
         barrier()
         torch.cuda.synchronize()
         time.sleep(0.05)
@@ -698,7 +716,7 @@ def main():
     # self-check of the sharded path (untimed): the gathered + de-interleaved frame must equal
     # the frame rendered by one GPU alone, byte for byte
     shard_ok = None
-    if sharded:
+    if full and sharded:
         run(1, 0)
         torch.cuda.synchronize()
         if rank == 0:
@@ -713,7 +731,6 @@ def main():
     kern_total_s = float(np.sum(kern_ms)) / 1e3
     log(f"[bench r{rank}] launch durations (HIP events, ms): " + " ".join(f"{x:.3f}" for x in kern_ms[:16]))
     kern_mean_s = kern_total_s / n_launch
-    alg_bytes_per_launch = alg_bytes_per_frame * K / n_launch
 
     # HBM-side traffic: PMC counters need rocprofv3 runs of their own (tools/measure_traffic.py, one
     # counter group per pass), so the bench reports the committed measurement of this config,
@@ -722,14 +739,14 @@ def main():
     traffic, traffic_src, traffic_extrapolated = None, None, None
     launch_sizes = [min(B, K - j * B) for j in range(n_launch)]
     live, committed_note = None, None
-    want_live = args.live_traffic == 1
+    want_live = full and args.live_traffic == 1
     if world == 1 and rank == 0 and want_live and not args.readback and n_streams == 1:
         # the child processes of the live passes upload the tree themselves: this process is done
         # with the GPU, so its copy (and the frame sets) go first
         tree.free_device()
         tree = None
         live = live_traffic(args.config, args.fp, launch_sizes[0], args.tune)
-    if world == 1:
+    if full and world == 1:
         per_frame, traffic_src, profiled_fpl = committed_traffic(args.config, args.fp,
                                                                  want_fpl=launch_sizes[0])
         committed_note = traffic_src
@@ -762,7 +779,6 @@ def main():
         # replicas: every rank rendered its own K frames; tile mode: the K frames were shared
         rays_total = W * H * K * (world if replicas else 1)
         mrays = rays_total / elapsed / 1e6
-        achieved = alg_bytes_per_launch / kern_mean_s / 1e9
         result = {
             "metric": f"Mrays/s at {W}x{H}, NeRF-synthetic-like {cfg['fmt']}{cfg['basis_dim']} "
                       f"(synthetic {args.config})",
@@ -798,7 +814,11 @@ def main():
                     f"screen tiles {tile_w}x{tile_h} round-robin over {world} GPUs, "
                     f"tree replicated, one RCCL gather of RGBA8 to rank 0 per launch"),
             },
-            "roofline": {
+        }
+        if full:
+            alg_bytes_per_launch = alg_bytes_per_frame * K / n_launch
+            achieved = alg_bytes_per_launch / kern_mean_s / 1e9
+            result["roofline"] = {
                 "bound": "hbm",
                 "achieved": round(achieved, 2),
                 "peak": HBM_PEAK_GBS,
@@ -829,8 +849,7 @@ def main():
                 "unique_bytes_per_frame": int(128 * np.mean([sum(u.values()) for u in unique_frames])),
                 "unique_lines_per_frame_by_array": {
                     k: int(np.mean([u[k] for u in unique_frames])) for k in unique_frames[0]},
-            },
-        }
+            }
         if cold_ms is not None:
             result["ms_per_step_cold"] = round(cold_ms, 5)
             result["cold_is"] = ("the identical K-step region once more behind 50 ms of idling (no pre-roll, "
@@ -843,73 +862,79 @@ def main():
                 "ms_per_step": [round(x, 5) for x in repeat_ms],
                 "min": round(allms[0], 5), "median": round(allms[len(allms) // 2], 5),
                 "max": round(allms[-1], 5)}
-        # lane utilisation of the march and shade rounds (instrumented flavour, same poses, outside
-        # the timed region) and -- from the committed PMC passes of these very sources -- the
-        # instructions a frame executes: a later change is checkable against this line alone
-        prof = committed_traffic.last_profile or {}
-        result["sched"] = {
-            "march_util": round(sched["march_lanes"] / max(64 * sched["march_rounds"], 1), 4),
-            "shade_util": round(sched["shade_lanes"] / max(64 * sched["shade_rounds"], 1), 4),
-            "march_rounds_per_frame": int(sched["march_rounds"] / n_distinct),
-            "shade_rounds_per_frame": int(sched["shade_rounds"] / n_distinct),
-            "valu_insts_per_frame": prof.get("valu_insts_per_frame"),
-            "salu_insts_per_frame": prof.get("salu_insts_per_frame"),
-            "valu_source": committed_note if prof else "no hash-verified PMC profile of these sources",
-        }
         if parity is not None:
             result["parity"] = parity
-        # roofline.model: the kernel's OWN lower bounds per launch, each from a measurement -- the
-        # algorithmic `frac` above saturates (its bytes are the reference's root-to-leaf reads, which
-        # this kernel mostly serves from two cached lookups), this one keeps its headroom visible
-        fpl = launch_sizes[0]
-        bounds = {}
-        if traffic is not None:
-            bounds["t_fabric_ms"] = traffic / 128.0 / GATHER_LINES_PER_S * 1e3
-        flat4, im = None, None
-        if prof.get("valu_insts_per_frame"):
-            flat4 = prof["valu_insts_per_frame"] * fpl * VALU_ISSUE_CYCLES / (N_SIMD * SIMD_HZ) * 1e3
-            im = issue_model(args.fp, cfg["basis_dim"], bool(info.get("brick_blocked")))
-            if im:  # march rounds (instrumented flavour) x the round's static mix + the rest at the rest's mix
-                v_march = min(sched["march_rounds"] / n_distinct * im["march_valu"], prof["valu_insts_per_frame"])
-                cyc = v_march * im["march_cpv"] + (prof["valu_insts_per_frame"] - v_march) * im["rest_cpv"]
-                bounds["t_issue_ms"] = cyc * fpl / (N_SIMD * SIMD_HZ) * 1e3
-            else:
-                bounds["t_issue_ms"] = flat4
-        if parity is not None and parity.get("longest_ray_samples"):
-            bounds["t_chain_ms"] = parity["longest_ray_samples"] * ROUND_FLOOR_US * 1e-3
-        if bounds:
-            binding = max(bounds, key=bounds.get)
-            result["roofline"]["model"] = {
-                **{k: round(v, 5) for k, v in bounds.items()},
-                "binding": binding,
-                "kernel_ms": round(kern_mean_s * 1e3, 5),
-                "frac_of_model": round(bounds[binding] / (kern_mean_s * 1e3), 4),
-                "t_issue_flat4_ms": None if flat4 is None else round(flat4, 5),
-                "frac_of_model_flat4": None if flat4 is None else round(
-                    max(flat4, *[v for k, v in bounds.items() if k != "t_issue_ms"]) / (kern_mean_s * 1e3), 4),
-                "t_issue_is": (f"class-weighted: {im['march_valu']} vector instructions per march round at "
-                               f"{im['march_cpv']} cycles, the rest at {im['rest_cpv']} ({im['source']}: ISA class "
-                               "histogram x 2.5 / 4 / 7.6 cycles, profiles/r04_valu_issue_cost.jsonl)") if im else
-                              "flat 4 cycles per vector instruction (no hash-verified ISA histogram of these sources)",
-                "what": "lower bounds of ONE launch: t_fabric = measured L2<->fabric lines / the chip's "
-                        f"random-line rate ({GATHER_LINES_PER_S / 1e9:.1f} G lines/s, profiles/r01_gather_ceiling.txt); "
-                        f"t_issue = vector instructions (hash-verified PMC profile) x their class-weighted cycles "
-                        f"(t_issue_is; flat {VALU_ISSUE_CYCLES:.0f} cycles: t_issue_flat4_ms) / "
-                        f"({N_SIMD} SIMDs x {SIMD_HZ / 1e9:.1f} GHz); t_chain = samples of the longest ray of the "
-                        f"checked frames x {ROUND_FLOOR_US} us (a dependent march round of a lone wave, "
-                        "profiles/r05_tail_profile.jsonl); frac_of_model = the largest / the launch's duration",
+        if full:
+            # lane utilisation of the march and shade rounds (instrumented flavour, same poses, outside
+            # the timed region) and -- from the committed PMC passes of these very sources -- the
+            # instructions a frame executes: a later change is checkable against this line alone
+            prof = committed_traffic.last_profile or {}
+            result["sched"] = {
+                "march_util": round(sched["march_lanes"] / max(64 * sched["march_rounds"], 1), 4),
+                "shade_util": round(sched["shade_lanes"] / max(64 * sched["shade_rounds"], 1), 4),
+                "march_rounds_per_frame": int(sched["march_rounds"] / n_distinct),
+                "shade_rounds_per_frame": int(sched["shade_rounds"] / n_distinct),
+                "valu_insts_per_frame": prof.get("valu_insts_per_frame"),
+                "salu_insts_per_frame": prof.get("salu_insts_per_frame"),
+                "valu_source": committed_note if prof else "no hash-verified PMC profile of these sources",
             }
+            # roofline.model: the kernel's OWN lower bounds per launch, each from a measurement -- the
+            # algorithmic `frac` above saturates (its bytes are the reference's root-to-leaf reads, which
+            # this kernel mostly serves from two cached lookups), this one keeps its headroom visible
+            fpl = launch_sizes[0]
+            bounds = {}
+            if traffic is not None:
+                bounds["t_fabric_ms"] = traffic / 128.0 / GATHER_LINES_PER_S * 1e3
+            flat4, im = None, None
+            if prof.get("valu_insts_per_frame"):
+                flat4 = prof["valu_insts_per_frame"] * fpl * VALU_ISSUE_CYCLES / (N_SIMD * SIMD_HZ) * 1e3
+                im = issue_model(args.fp, cfg["basis_dim"], bool(info.get("brick_blocked")))
+                if im:  # march rounds (instrumented flavour) x the round's static mix + the rest at the rest's mix
+                    v_march = min(sched["march_rounds"] / n_distinct * im["march_valu"], prof["valu_insts_per_frame"])
+                    cyc = v_march * im["march_cpv"] + (prof["valu_insts_per_frame"] - v_march) * im["rest_cpv"]
+                    bounds["t_issue_ms"] = cyc * fpl / (N_SIMD * SIMD_HZ) * 1e3
+                else:
+                    bounds["t_issue_ms"] = flat4
+            if parity is not None and parity.get("longest_ray_samples"):
+                bounds["t_chain_ms"] = parity["longest_ray_samples"] * ROUND_FLOOR_US * 1e-3
+            if bounds:
+                binding = max(bounds, key=bounds.get)
+                result["roofline"]["model"] = {
+                    **{k: round(v, 5) for k, v in bounds.items()},
+                    "binding": binding,
+                    "kernel_ms": round(kern_mean_s * 1e3, 5),
+                    "frac_of_model": round(bounds[binding] / (kern_mean_s * 1e3), 4),
+                    "t_issue_flat4_ms": None if flat4 is None else round(flat4, 5),
+                    "frac_of_model_flat4": None if flat4 is None else round(
+                        max(flat4, *[v for k, v in bounds.items() if k != "t_issue_ms"]) / (kern_mean_s * 1e3), 4),
+                    "t_issue_is": (f"class-weighted: {im['march_valu']} vector instructions per march round at "
+                                   f"{im['march_cpv']} cycles, the rest at {im['rest_cpv']} ({im['source']}: ISA class "
+                                   "histogram x 2.5 / 4 / 7.6 cycles, profiles/r04_valu_issue_cost.jsonl)") if im else
+                                  "flat 4 cycles per vector instruction (no hash-verified ISA histogram of these sources)",
+                    "what": "lower bounds of ONE launch: t_fabric = measured L2<->fabric lines / the chip's "
+                            f"random-line rate ({GATHER_LINES_PER_S / 1e9:.1f} G lines/s, profiles/r01_gather_ceiling.txt); "
+                            f"t_issue = vector instructions (hash-verified PMC profile) x their class-weighted cycles "
+                            f"(t_issue_is; flat {VALU_ISSUE_CYCLES:.0f} cycles: t_issue_flat4_ms) / "
+                            f"({N_SIMD} SIMDs x {SIMD_HZ / 1e9:.1f} GHz); t_chain = samples of the longest ray of the "
+                            f"checked frames x {ROUND_FLOOR_US} us (a dependent march round of a lone wave, "
+                            "profiles/r05_tail_profile.jsonl); frac_of_model = the largest / the launch's duration",
+                }
         if use_dist:
             result["rccl"] = {"world_size": dist.get_world_size(), "backend": dist.get_backend(),
                               "gather": gather_path,
                               "nccl_version": ".".join(map(str, torch.cuda.nccl.version()))
                               if not share_gpu else None,
                               "devices": torch.cuda.device_count()}
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(stree, transforms, W, H, focal, args.cpu_budget)
             result["cpu_baseline"]["rtfrag"] = rtfrag_baseline()
         else:
             result["cpu_baseline"] = None
+        if last_frame is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            np.save(os.path.join(args.dump_outputs, "rgba.npy"), last_frame.astype(np.float32))
+            log(f"[bench] frame of step {first_last + n_last - 1} (the last timed step) -> "
+                f"{os.path.join(args.dump_outputs, 'rgba.npy')}")
         os.write(json_fd, (json.dumps(result) + "\n").encode())
     if use_dist:
         dist.barrier()

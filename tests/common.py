@@ -1,10 +1,77 @@
 """Shared helpers for the parity tests: seeded scenes + oracle/kernel runners."""
 from __future__ import annotations
 
+import hashlib
+import json
+import os
+
 import numpy as np
 
 from oracle import binding as ob
 from volrend_amd import synth
+
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+_ref_pins = {}
+
+
+def _pins(name):
+    if name not in _ref_pins:
+        path = os.path.join(GOLDEN, name)
+        _ref_pins[name] = json.load(open(path)) if name.endswith(".json") else np.load(path)
+    return _ref_pins[name]
+
+
+def digest(a) -> str:
+    """SHA-256 of an array's dtype, shape and bytes."""
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
+
+
+def _record(key, what, value):
+    path = os.path.join(os.environ["VOLREND_RECORD_REF_PINS"], key.replace("/", "__") + what)
+    if what == ".npy":
+        np.save(path, value)
+    else:
+        open(path, "w").write(value)
+
+
+def _live(available):
+    return ob.ref_lib() is not None if available is None else available
+
+
+def assert_ref_equal(key, got, live, available=None, msg=""):
+    """``got`` equals output ``key`` of the reference's own code (its device code compiled for the
+    host, oracle/_ref, or its GLSL backend) bit for bit.  The reference's output is stored as a
+    SHA-256 digest in tests/golden/ref_pins_v1.json (tests/golden/make_ref_pins.py), so the pin holds
+    where the reference is not built.  Where it is (``available``, default: the host build loads),
+    ``live()`` recomputes the output and ``got`` must equal it as well.  With
+    VOLREND_RECORD_REF_PINS=DIR the digest of ``live()`` is recorded into DIR (make_ref_pins.py)."""
+    got = np.ascontiguousarray(got)
+    recording = bool(os.environ.get("VOLREND_RECORD_REF_PINS"))
+    if recording or _live(available):
+        want = np.ascontiguousarray(live())
+        assert want.dtype == got.dtype and want.shape == got.shape and want.tobytes() == got.tobytes(), \
+            f"{key}: differs from the reference {msg}"
+        if recording:
+            _record(key, ".sha256", digest(want))
+            return
+    assert digest(got) == _pins("ref_pins_v1.json")[key], f"{key}: differs from the reference {msg}"
+
+
+def ref_array(key, live, available=None):
+    """Output ``key`` of the reference's code where a test computes with its values instead of testing
+    equality: stored as it is in tests/golden/ref_frames_v1.npz.  Where the reference is available,
+    ``live()`` recomputes it and must equal the stored copy."""
+    if os.environ.get("VOLREND_RECORD_REF_PINS"):
+        want = np.asarray(live())
+        _record(key, ".npy", want)
+        return want
+    want = _pins("ref_frames_v1.npz")[key]
+    if _live(available):
+        got = np.asarray(live())
+        assert got.dtype == want.dtype and np.array_equal(got, want), \
+            f"{key}: the reference no longer reproduces its stored output (tests/golden/make_ref_pins.py)"
+    return want
 
 
 def small_scene(depth=5, basis_dim=16, fmt="SH", seed=11, **kw):

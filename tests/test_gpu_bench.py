@@ -20,7 +20,7 @@ def gpu():
 
 def test_bench_prints_one_json_line_with_the_contract_keys(gpu):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C0", "--steps",
-                        "16", "--warmup", "8", "--batch", "8"], capture_output=True, text=True,
+                        "16", "--warmup", "8", "--batch", "8", "--full"], capture_output=True, text=True,
                        timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -60,6 +60,38 @@ def test_bench_prints_one_json_line_with_the_contract_keys(gpu):
         cb["rtfrag"]["value"] > 0 and cb["rtfrag"]["cores"] >= 1 and cb["rtfrag"]["rasteriser"]))
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_frame(gpu, tmp_path):
+    """Without --full the line carries the headline figures only; --dump-outputs writes the frame of
+    the last timed step (here the last of a partial second launch), which must be the oracle's."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    from oracle import binding as ob
+    from volrend_amd import synth
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C0", "--steps", "12",
+                        "--warmup", "8", "--batch", "8", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 12 and d["warmup"] == 8 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+    assert d["config"]["frames_per_launch"] == [8, 4] and d["config"]["launches"] == 2
+    for k in ("roofline", "parity", "repeats", "ms_per_step_cold", "sched"):
+        assert k not in d, k
+    assert d["cpu_baseline"] is None
+    got = np.load(tmp_path / "out" / "rgba.npy")
+    cfg = synth.CONFIGS["C0"]
+    assert got.dtype == np.float32 and got.shape == (cfg["height"], cfg["width"], 4)
+    tree = bench.load_or_make_tree(synth, "C0", 0, lambda: None)
+    tr = synth.c2w_to_transform(synth.make_poses(200)[8 + 12 - 1])
+    want, _, _ = ob.render(ob.TreeHandle(tree), ob.make_camera(tr, cfg["width"], cfg["height"], cfg["focal"]),
+                           ob.default_options(), ob.FP_STRICT, want_accum=False,
+                           nthreads=min(16, os.cpu_count() or 1))
+    assert np.array_equal(got, want.astype(np.float32))
+
+
 @pytest.mark.parametrize("mode", ["tile", "replicas"])
 def test_bench_multirank_rehearsal(gpu, mode):
     env = dict(os.environ, VOLREND_BENCH_SHARE_GPU="1")
@@ -67,7 +99,7 @@ def test_bench_multirank_rehearsal(gpu, mode):
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                         "29541", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C0",
                         "--steps", "16", "--warmup", "8", "--batch", "4", "--no-cpu-baseline",
-                        "--mode", mode], capture_output=True, text=True, timeout=600, cwd=ROOT,
+                        "--mode", mode, "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT,
                        env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -88,8 +120,8 @@ def test_bench_one_rank_through_the_product_collective(gpu):
     volrend_headless --gpus N ships) and the batch de-interleave, and must still equal the oracle."""
     env = dict(os.environ, VOLREND_FORCE_GATHER="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "C0", "--steps", "16",
-                        "--warmup", "8", "--batch", "4", "--no-cpu-baseline"], capture_output=True, text=True,
-                       timeout=600, cwd=ROOT, env=env)
+                        "--warmup", "8", "--batch", "4", "--no-cpu-baseline", "--full"], capture_output=True,
+                       text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.strip().startswith("{")][-1])
     assert d["n_gpus"] == 1 and d["parity"]["rgba8_equal"] is True
@@ -111,7 +143,7 @@ def test_bench_two_gpus_over_rccl(gpu, mode):
                         "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
                         "29543", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C0",
                         "--steps", "16", "--warmup", "8", "--batch", "4", "--no-cpu-baseline",
-                        "--mode", mode], capture_output=True, text=True, timeout=900, cwd=ROOT,
+                        "--mode", mode, "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -136,7 +168,7 @@ def test_bench_plain_form_launches_itself(gpu):
     if not two:
         env["VOLREND_BENCH_SHARE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "C0",
-                        "--steps", "16", "--warmup", "8", "--batch", "4", "--no-cpu-baseline"],
+                        "--steps", "16", "--warmup", "8", "--batch", "4", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

@@ -6,7 +6,7 @@ OUT=gpurun_out/ab_$TAG.jsonl; : > $OUT
 for rep in $(seq $REPS); do for v in "$@"; do
   lib=""; [ "$v" != base ] && lib="$PWD/volrend_amd/libvolrend_hip_$v.so"
   for spec in "256 64" "20 5"; do set -- $spec $@; s=$1; w=$2; shift 2
-    VOLREND_HIP_LIB=$lib timeout 300 python bench.py --steps $s --warmup $w --no-cpu-baseline ${SWEEP_ARGS:-} 2>/dev/null | python -c '
+    VOLREND_HIP_LIB=$lib timeout 300 python bench.py --full --steps $s --warmup $w --no-cpu-baseline ${SWEEP_ARGS:-} 2>/dev/null | python -c '
 import json,sys
 for l in sys.stdin:
     d=json.loads(l); print(json.dumps({"variant": sys.argv[1], "steps": d["steps"], "ms": d["ms_per_step"], "kernel_ms": d["roofline"]["kernel_ms_per_frame"]}))' $v >> $OUT

@@ -7,7 +7,7 @@ OUT=gpurun_out/geom_$TAG.jsonl
 : > $OUT
 for pair in $*; do
   g0=${pair%,*}; bl=${pair#*,}
-  VR_TOP_LEVELS=$g0 VR_BRICK_LEVELS=$bl timeout 300 python bench.py --config $CFG --no-cpu-baseline ${SWEEP_ARGS:-} \
+  VR_TOP_LEVELS=$g0 VR_BRICK_LEVELS=$bl timeout 300 python bench.py --full --config $CFG --no-cpu-baseline ${SWEEP_ARGS:-} \
       2>> gpurun_out/geom_$TAG.log | python -c '
 import json,sys
 g0,bl=sys.argv[1:3]

@@ -7,7 +7,7 @@ OUT=gpurun_out/sweep_$TAG.jsonl
 : > $OUT
 for spec in "1 64 8" "4 128 16" "16 256 32" "20 20 5" "64 256 64"; do
   set -- $spec
-  timeout 300 python bench.py --batch $1 --steps $2 --warmup $3 --no-cpu-baseline ${SWEEP_ARGS:-} \
+  timeout 300 python bench.py --full --batch $1 --steps $2 --warmup $3 --no-cpu-baseline ${SWEEP_ARGS:-} \
       2>> gpurun_out/sweep_$TAG.log | python -c '
 import json,sys
 for l in sys.stdin:

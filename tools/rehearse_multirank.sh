@@ -5,4 +5,4 @@
 N=${1:-2}; shift || true
 export VOLREND_BENCH_SHARE_GPU=1
 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 \
-  --master-port 29533 bench.py --gpus $N --steps 32 --warmup 16 --batch 8 --no-cpu-baseline "$@"
+  --master-port 29533 bench.py --full --gpus $N --steps 32 --warmup 16 --batch 8 --no-cpu-baseline "$@"

@@ -10,7 +10,7 @@ for v in "$@"; do
   lib=""; [ "$v" != base ] && lib="$PWD/volrend_amd/libvolrend_hip_$v.so"
   for spec in "256 64" "20 5"; do
     set -- $spec
-    VR_TIMELINE=$([ "$v" = tl ] && echo 1) VOLREND_HIP_LIB=$lib timeout 300 python bench.py --steps $1 --warmup $2 --no-cpu-baseline ${SWEEP_ARGS:-} \
+    VR_TIMELINE=$([ "$v" = tl ] && echo 1) VOLREND_HIP_LIB=$lib timeout 300 python bench.py --full --steps $1 --warmup $2 --no-cpu-baseline ${SWEEP_ARGS:-} \
         2>> gpurun_out/variants_$TAG.log | python -c '
 import json,sys
 v=sys.argv[1]
