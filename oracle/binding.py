@@ -96,6 +96,7 @@ def lib():
                                C.POINTER(C.c_int)]
         L.or_expf.restype = C.c_float
         L.or_expf.argtypes = [C.c_float]
+        L.or_expf_n.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.or_half2float.restype = C.c_float
         L.or_half2float.argtypes = [C.c_uint16]
         L.or_basis.argtypes = [C.POINTER(OrTree), C.POINTER(C.c_float * 3), C.c_int,

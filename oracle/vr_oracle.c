@@ -166,6 +166,9 @@ int64_t or_query(const OrTree* tree, float xyz[3], float* cube_sz, int* depth) {
 }
 
 float or_expf(float x) { return vr_det_expf(x); }
+void or_expf_n(const float* x, float* out, int64_t n) {
+    for (int64_t i = 0; i < n; ++i) out[i] = vr_det_expf(x[i]);
+}
 float or_half2float(uint16_t h) { return vr_half_bits_to_float(h); }
 
 void or_basis(const OrTree* tree, const float dir[3], int fp_mode, float out[25]) {

@@ -126,6 +126,8 @@ int64_t or_query(const OrTree* tree, float xyz[3], float* cube_sz, int* depth);
 
 /* deterministic expf shared by spec with the HIP kernel (DESIGN.md "vr_expf") */
 float or_expf(float x);
+/* out[i] = or_expf(x[i]), i < n */
+void or_expf_n(const float* x, float* out, int64_t n);
 /* fp16 bits -> fp32, exact */
 float or_half2float(uint16_t h);
 /* SH/SG/ASG basis of a direction (lumisphere.hpp:9-87), out[25] */

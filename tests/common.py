@@ -271,3 +271,175 @@ def camera_at(position, look_at=(0.5, 0.5, 0.5), size=40, focal=28.0):
     up = np.cross(back, right)
     tr = np.concatenate([right, up, back]).astype(np.float32)
     return np.concatenate([tr, c]).astype(np.float32), size, size, focal
+
+
+# Special values of the value-domain tests, as binary16 bit patterns.
+#   sigma: -0, negative, smallest / largest subnormal, 65504, +-inf, NaN, and 0.5 (a sigma_thresh that
+#   binary16 represents) with its neighbours one half-ulp below / above
+EDGE_SIGMA = [0x8000, 0xB800, 0xC000, 0x0001, 0x03FF, 0x7BFF, 0x7C00, 0xFC00, 0x7E00, 0x3800, 0x37FF, 0x3801]
+#   SH / SG / ASG coefficients: NaN, +-inf, +-65504 (sums overflow, inf meets -inf, inf meets a basis
+#   value of 0), and values that put the sigmoid argument -0.2821 * c of basis 0 into the subnormal
+#   band of exp ([-104, -87]: c in [308, 369]), at +-88 / 89 (c = +-312, +-316) and beyond the clamp
+EDGE_COEFF = [0x7E00, 0x7C00, 0xFC00, 0x7BFF, 0xFBFF] + [
+    int(np.float16(s * v).view(np.uint16)) for v in (308, 312, 316, 330, 350, 369, 390, 1000) for s in (1, -1)]
+#   RGBA colours: negative, > 1, the largest finite, +-inf, NaN
+EDGE_RGBA = [0xB800, 0xC200, 0x3E00, 0x4700, 0x7BFF, 0x7C00, 0xFC00, 0x7E00]
+
+
+def apply_value_edges(tree, seed, frac=0.08):
+    """Overwrites a seeded fraction ``frac`` of the leaf records of ``tree`` (occupied and empty
+    alike) with special values: in each chosen record 1-3 colour entries from EDGE_COEFF / EDGE_RGBA
+    (for SH / SG / ASG basis 0 of a channel half the time, whose basis value is the constant 0.2821)
+    and, in half of them, sigma from EDGE_SIGMA.  SG / ASG lobes get special parameters too: lambda
+    NaN, inf, 0 and 1e30 in lobes 0-3 and a mu of length 2 in lobe 4.  Returns a new tree."""
+    import dataclasses
+    rng = np.random.default_rng(seed)
+    dd = tree.data_dim
+    data = tree.data.reshape(-1, dd).view(np.uint16).copy()
+    leaf = np.flatnonzero(tree.child.reshape(-1) == 0)
+    pick = leaf[rng.random(leaf.size) < frac]
+    rgba = tree.format_name == "RGBA"
+    bd = max(tree.basis_dim, 1)
+    cat = np.array(EDGE_RGBA if rgba else EDGE_COEFF, np.uint16)
+    for r in pick:
+        for _ in range(int(rng.integers(1, 4))):
+            ch = int(rng.integers(3))
+            j = ch if rgba else ch * bd + (0 if rng.random() < 0.5 else int(rng.integers(bd)))
+            data[r, j] = cat[rng.integers(cat.size)]
+        if rng.random() < 0.5:
+            data[r, dd - 1] = EDGE_SIGMA[int(rng.integers(len(EDGE_SIGMA)))]
+    extra = tree.extra
+    if extra is not None:
+        extra = extra.copy()
+        ex = extra.reshape(bd, -1)      # one row per lobe: SG [lambda, mu], ASG [lambda_x, lambda_y, axes]
+        for lobe, lam in zip(range(4), (np.nan, np.inf, 0.0, 1e30)):
+            if lobe < bd:
+                ex[lobe, 0] = lam
+        if bd > 4:
+            ex[4, 1:4] *= 2.0
+    return dataclasses.replace(tree, data=data.view(np.float16).reshape(tree.data.shape), extra=extra)
+
+
+def value_edge_tree(fmt="SH", basis_dim=16, seed=0, depth=5, frac=0.08):
+    """A seeded small_scene with special values in a fraction of its leaf records (apply_value_edges)."""
+    return apply_value_edges(small_scene(depth=depth, basis_dim=basis_dim, fmt=fmt, seed=seed), seed + 1, frac)
+
+
+def axis_camera(size=63, focal=70.0, dist=4.0):
+    """A camera on the +z axis looking down -z with an identity rotation: for an odd ``size`` the
+    centre row and column of rays have direction components that are exactly 0 (SH basis values
+    such as y, x*y are exactly 0 there)."""
+    tr = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, dist], dtype=np.float32)
+    return tr, size, size, focal
+
+
+def fog_tree(fmt="SH", basis_dim=16, seed=0, depth=5, sigma=(0.05, 0.4)):
+    """A full tree (every node refined down to ``depth`` levels, all 8^depth leaves occupied) of
+    low density: rays cross the whole volume and every sample is a hit, so the deferred shading
+    (colour queues, the wave ring and its flushes) runs under full pressure.  Colours as
+    small_scene; sigma uniform in ``sigma``."""
+    rng = np.random.default_rng(seed)
+    data_dim = 4 if fmt == "RGBA" else 3 * basis_dim + 1
+    n_inner = sum(8 ** d for d in range(depth - 1))       # nodes whose 8 slots are nodes
+    cap = n_inner + 8 ** (depth - 1)
+    child = np.zeros((cap, 8), np.int32)
+    node = np.arange(n_inner)
+    child[:n_inner] = (8 * node[:, None] + 1 + np.arange(8)[None, :]) - node[:, None]   # breadth-first
+    data = np.zeros((cap, 8, data_dim), np.float32)
+    data[..., :-1] = rng.standard_normal((cap, 8, data_dim - 1)) * 0.6
+    if fmt == "RGBA":
+        data[..., :3] = rng.uniform(0.05, 0.95, size=(cap, 8, 3))
+    data[..., -1] = rng.uniform(*sigma, size=(cap, 8))
+    data[child != 0] = 0
+    base = small_scene(depth=2, basis_dim=basis_dim, fmt=fmt, seed=seed)   # offset, scale, SG / ASG lobes
+    name = "RGBA" if fmt == "RGBA" else f"{fmt}{basis_dim}"
+    return synth.SynthTree(child.reshape(cap, 2, 2, 2), data.astype(np.float16).reshape(cap, 2, 2, 2, data_dim),
+                           base.offset, base.invradius3, name, base.extra, depth)
+
+
+def assert_same_values(rgba_g, acc_g, rgba_o, acc_o, what=""):
+    """NaN-aware equality for the value-domain tests: RGBA8 bytes equal; fp32 words bit-equal or
+    both NaN, with the NaNs in exactly the same places (only the sign and payload of a NaN may
+    differ: x86 makes 0xFFC00000 where gfx950 makes 0x7FC00000)."""
+    bad_px = int((rgba_g != rgba_o).any(-1).sum())
+    assert bad_px == 0, f"{what}: {bad_px} RGBA8 pixels differ"
+    if acc_o is None:
+        return
+    ng, no = np.isnan(acc_g), np.isnan(acc_o)
+    assert np.array_equal(ng, no), f"{what}: NaN in {int((ng & ~no).sum())} kernel / {int((no & ~ng).sum())} " \
+                                   f"oracle accumulator words only"
+    diff = (acc_g.view(np.uint32) != acc_o.view(np.uint32)) & ~no
+    assert not diff.any(), f"{what}: {int(diff.sum())} accumulator words differ"
+
+
+# The value-domain cases (tests/test_oracle_vs_ref.py, tests/test_gpu_value_domain.py):
+#   name -> (fmt, basis_dim, camera: "orbit" | "axis", render options)
+VALUE_CASES = {
+    "SH1": ("SH", 1, "orbit", {}),
+    "SH4": ("SH", 4, "orbit", {}),
+    "SH9": ("SH", 9, "orbit", {}),
+    "SH16": ("SH", 16, "orbit", {}),
+    "SH25": ("SH", 25, "orbit", {}),
+    "RGBA": ("RGBA", 0, "orbit", {}),
+    "SG7": ("SG", 7, "orbit", dict(basis_minmax=(1, 6))),        # lobe 0 (lambda NaN) left out
+    "SG9_nan_lobe": ("SG", 9, "orbit", {}),                       # ... and taken: every colour NaN
+    "ASG4": ("ASG", 4, "orbit", dict(basis_minmax=(1, 3))),
+    "SH16_axis": ("SH", 16, "axis", {}),                          # inf coefficient x basis value 0
+    "SH9_basis_range": ("SH", 9, "axis", dict(basis_minmax=(1, 5))),
+    "SH9_thresh_edge": ("SH", 9, "orbit", dict(sigma_thresh=0.5)),
+    "SH4_negative_thresh": ("SH", 4, "orbit", dict(sigma_thresh=-1.0)),   # every sample a hit
+    "SH16_stop_ge_1": ("SH", 16, "orbit", dict(stop_thresh=1.5, background_brightness=-0.75)),
+    "RGBA_never_stop": ("RGBA", 0, "orbit", dict(stop_thresh=-0.5, background_brightness=3e7)),
+    "RGBA_stop_ge_1": ("RGBA", 0, "axis", dict(stop_thresh=1.0, background_brightness=1.5)),
+    "SH16_depth": ("SH", 16, "orbit", dict(render_depth=1)),
+}
+
+
+def value_case(name, size=56):
+    """-> (tree, transform, w, h, focal, option kwargs) of VALUE_CASES[name]."""
+    fmt, bd, cam, kw = VALUE_CASES[name]
+    seed = 7000 + sum(map(ord, name))
+    tree = value_edge_tree(fmt, bd, seed=seed)
+    tr, w, h, f = axis_camera(size | 1) if cam == "axis" else camera_for(pose_idx=seed % 8, size=size)
+    return tree, tr, w, h, f, dict(kw)
+
+
+# fog scenes: name -> (fmt, basis_dim, render options)
+FOG_CASES = {
+    "SH16": ("SH", 16, {}),
+    "SH25": ("SH", 25, {}),
+    "SG7": ("SG", 7, {}),
+    "RGBA": ("RGBA", 0, {}),
+    "SH16_negative_thresh": ("SH", 16, dict(sigma_thresh=-0.5)),  # zero-density samples queue items too
+}
+
+
+def fog_case(name, size=48):
+    """-> (tree, transform, w, h, focal, option kwargs) of FOG_CASES[name]: a depth-6 fog tree
+    (every sample a hit, ~90 hits per ray, no early stop).  The negative-threshold variant zeroes a
+    third of the leaves' densities."""
+    fmt, bd, kw = FOG_CASES[name]
+    seed = 8000 + sum(map(ord, name))
+    tree = fog_tree(fmt, bd, seed=seed, depth=6)
+    if kw.get("sigma_thresh", 0.0) < 0:
+        rng = np.random.default_rng(seed)
+        d = tree.data.reshape(-1, tree.data_dim)
+        d[rng.random(d.shape[0]) < 1 / 3, -1] = 0
+    tr, w, h, f = camera_for(pose_idx=seed % 8, size=size)
+    return tree, tr, w, h, f, dict(kw)
+
+
+def edge_probe_point(tree, seed=0):
+    """A world point whose leaf holds a non-finite colour coefficient (vr_probe_coeffs / the
+    probe overlay then see it)."""
+    import ctypes as C
+    th = ob.TreeHandle(tree)
+    rng = np.random.default_rng(seed)
+    out = np.zeros(tree.data_dim - 1, np.float32)
+    for _ in range(20000):
+        p = tuple(float(v) for v in rng.uniform(-1.4, 1.4, 3))
+        ob.lib().or_probe_coeffs(C.byref(th.struct), C.byref(ob.default_options(enable_probe=1, probe=p)),
+                                 out.ctypes.data)
+        if not np.isfinite(out[:3 * max(tree.basis_dim, 1)]).all():
+            return p
+    raise AssertionError("no leaf with a non-finite coefficient found")

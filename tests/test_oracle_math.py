@@ -32,6 +32,35 @@ def test_det_expf_accuracy_and_edges():
     assert L.or_expf(0.0) == 1.0
 
 
+def test_det_expf_within_one_ulp_dense_sweep():
+    """vr_det_expf against double-precision exp on every 64th float of [-104, 89] (about 35 M
+    inputs): normal, subnormal (x < -87.3) and overflowing (x > 88.72) results alike.  The error
+    is measured in units of the binary32 grid below |exp(x)| (2^-149 in the subnormal band); a
+    result that rounds beyond FLT_MAX must be +inf."""
+    L = ob.lib()
+    lo, hi = np.float32(-104.0).view(np.uint32), np.float32(89.0).view(np.uint32)
+    sweeps = [np.arange(0, int(hi) + 1, 64, dtype=np.uint32),              # +0 .. 89
+              np.arange(0x80000000, int(lo) + 1, 64, dtype=np.uint32)]     # -0 .. -104
+    n, worst = 0, 0.0
+    for bits in sweeps:
+        for part in np.array_split(bits, max(1, bits.size // (1 << 22))):
+            x = part.view(np.float32)
+            got = np.empty_like(x)
+            L.or_expf_n(x.ctypes.data, got.ctypes.data, x.size)
+            ref = np.exp(x.astype(np.float64))
+            with np.errstate(over="ignore"):
+                ref32 = ref.astype(np.float32)
+            inf = np.isinf(ref32)
+            assert np.array_equal(np.isinf(got), inf), x[np.isinf(got) != inf][:8]
+            r = ref32[~inf]
+            below = np.where(r.astype(np.float64) > ref[~inf], np.nextafter(r, np.float32(0)), r)
+            ulp = np.abs(got[~inf].astype(np.float64) - ref[~inf]) / np.spacing(below).astype(np.float64)
+            assert ulp.max() < 1.0, (ulp.max(), x[~inf][np.argmax(ulp)])
+            worst = max(worst, float(ulp.max()))
+            n += x.size
+    assert n > 30_000_000 and worst > 0.5
+
+
 def test_counters_consistent():
     tree = common.small_scene(depth=6, basis_dim=16, seed=5)
     tr, w, h, f = common.camera_for(pose_idx=2, size=64)

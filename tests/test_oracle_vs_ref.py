@@ -214,3 +214,66 @@ def test_deep_n2_chain_tree(request, depth, step):
     assert cnt["hit_samples"] > 5000 and cnt["child_reads"] > 8 * cnt["samples"]
     assert_ref_equal(request.node.name + "/rgba", rgba_o, lambda: ob.ref_render(th, cam, opt))
     assert_accum_equal(request.node.name, acc_o, th, cam, opt)
+
+
+@pytest.mark.parametrize("case", list(common.VALUE_CASES))
+def test_special_values_bit_exact(request, case):
+    """Leaf records with special values (tests/common.py apply_value_edges: sigma -0 / negative /
+    subnormal / 65504 / +-inf / NaN / at a threshold; colour coefficients NaN / +-inf / +-65504 /
+    sigmoid arguments in exp's subnormal band, at its overflow edge and beyond its clamp; RGBA
+    colours outside [0, 1]; SG / ASG lobes with lambda NaN / inf / 0 / 1e30) and the options at the
+    edges of their domains: the oracle's RGBA8 and fp32 accumulators equal the reference build's bit
+    for bit, NaNs included."""
+    tree, tr, w, h, f, kw = common.value_case(case)
+    rgba_o, acc_o, (th, cam, opt) = both(request.node.name, tree, tr, w, h, f, msg=str(kw), **kw)
+    assert_accum_equal(request.node.name, acc_o, th, cam, opt, msg=str(kw))
+    assert np.isfinite(acc_o).any() and (np.isnan(acc_o).any() or kw.get("render_depth"))
+
+
+@pytest.mark.parametrize("kind", ["N3", "chain26"])
+def test_special_values_generic_trees(request, kind):
+    """The same special values in an N = 3 tree and in a 26-level N = 2 chain around the camera
+    (both take the float descent)."""
+    if kind == "N3":
+        tree = common.apply_value_edges(common.random_tree_general_n(3, 3, 4, "SH", seed=703), 704, frac=0.15)
+        tr, w, h, f = common.camera_for(pose_idx=3, size=48)
+        kw = {}
+    else:
+        tree, T = common.deep_chain_tree_n2(depth=26, basis_dim=4, seed=705)
+        tree = common.apply_value_edges(tree, 706, frac=0.3)
+        tr, w, h, f = common.camera_at(T)
+        kw = dict(step_size=1e-8)
+    rgba_o, acc_o, (th, cam, opt) = both(request.node.name, tree, tr, w, h, f, **kw)
+    assert_accum_equal(request.node.name, acc_o, th, cam, opt)
+    assert np.isnan(acc_o).any() and np.isfinite(acc_o).any()
+
+
+@pytest.mark.parametrize("fmt,bd", [("SH", 9), ("SG", 4)])
+def test_special_values_probe(request, fmt, bd):
+    """Probe overlay and probe coefficients at a leaf that holds a non-finite coefficient."""
+    tree = common.value_edge_tree(fmt, bd, seed=710 + bd)
+    p = common.edge_probe_point(tree, seed=bd)
+    tr, w, h, f = common.camera_for(pose_idx=5, size=48)
+    th = ob.TreeHandle(tree)
+    cam = ob.make_camera(tr, w, h, f)
+    opt = ob.default_options(enable_probe=1, probe=p, probe_disp_size=30, basis_minmax=(0, bd - 1))
+    rgba_o, _, _ = ob.render(th, cam, opt)
+    assert_ref_equal(request.node.name + "/rgba", rgba_o, lambda: ob.ref_render(th, cam, opt))
+    n = tree.data_dim - 1
+    a = np.zeros(n, np.float32)
+    ob.lib().or_probe_coeffs(C.byref(th.struct), C.byref(opt), a.ctypes.data)
+    assert not np.isfinite(a).all()
+
+    def ref_coeffs():
+        b = np.zeros(n, np.float32)
+        ob.ref_lib().ref_probe_coeffs(C.byref(th.struct), C.byref(opt), b.ctypes.data)
+        return b.view(np.uint32)
+    assert_ref_equal(request.node.name + "/probe_coeffs", a.view(np.uint32), ref_coeffs)
+
+
+@pytest.mark.parametrize("case", list(common.FOG_CASES))
+def test_fog_bit_exact(request, case):
+    """Fog (every sample of ~90 per ray a hit, tests/common.py fog_tree) against the reference build."""
+    tree, tr, w, h, f, kw = common.fog_case(case)
+    rgba_o, acc_o, (th, cam, opt) = both(request.node.name, tree, tr, w, h, f, **kw)
+    assert_accum_equal(request.node.name, acc_o, th, cam, opt)

@@ -105,11 +105,22 @@ static __device__ __forceinline__ float mul_add_half(float b, uint32_t w, float 
 // a pure IEEE-op algorithm so host oracle and device agree bit for bit:
 //   clamp to [-104, 89]; k = rint(x*log2e); r = x - k*ln2 (two-step Cody-Waite);
 //   degree-5 Horner (Cephes coefficients); result = (y*2^(k>>1)) * 2^(k-(k>>1)).
-static __device__ __forceinline__ float vr_expf(float x) {
-    // Branch-free form of the spec: v_med3_f32 is the clamp (a NaN stays a NaN
-    // through the fma chain), v_ldexp_f32 is the single-rounding power-of-two
+//
+// NaN -> NaN, as the spec says.  The clamp is v_maximum3_f32 + v_minimum3_f32 (IEEE 754-2019
+// maximum / minimum: a NaN operand gives a quiet NaN) and the NaN then stays a NaN through the
+// fma chain and v_ldexp_f32.  A single v_med3_f32 is NOT a NaN-preserving clamp: the median of
+// (NaN, -104, 89) is one of the bounds (measured on gfx950: 89 -> +inf for a signalling NaN,
+// -104 -> 0 for a quiet one; the compiler folds a constant NaN to -104), so a NaN colour sum
+// would come out as a finite sigmoid.  vr_expf_nonan below keeps that one-instruction clamp
+// for arguments that cannot be NaN.
+template <bool NAN_IN = true>
+static __device__ __forceinline__ float vr_expf_impl(float x) {
+    // Branch-free form of the spec: v_ldexp_f32 is the single-rounding power-of-two
     // scaling (identical to the spec's two exact-then-rounded multiplies).
-    x = __builtin_amdgcn_fmed3f(x, -104.0f, 89.0f);
+    if (NAN_IN)
+        x = __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, -104.0f), 89.0f);
+    else
+        x = __builtin_amdgcn_fmed3f(x, -104.0f, 89.0f);
     const float kf = __builtin_rintf(x * 1.44269502162933349609375f);
     float r = __builtin_fmaf(kf, -0.693145751953125f, x);
     r = __builtin_fmaf(kf, -1.428606765330187045037746429443359375e-06f, r);
@@ -124,16 +135,20 @@ static __device__ __forceinline__ float vr_expf(float x) {
     y = y + 1.0f;
     return __builtin_amdgcn_ldexpf(y, (int)kf);
 }
+static __device__ __forceinline__ float vr_expf(float x) { return vr_expf_impl<true>(x); }
+// x must not be NaN (a NaN comes out as +inf or 0, see above); every other input, +-inf
+// included, gives the bits of vr_expf(x) -- one VALU instruction less.
+static __device__ __forceinline__ float vr_expf_nonan(float x) { return vr_expf_impl<false>(x); }
 
 // Two independent vr_expf in one instruction stream: the multiplies / fmas / adds are packed
 // (v_pk_mul_f32, v_pk_fma_f32, v_pk_add_f32: two binary32 operations per lane and issue slot,
-// each rounded exactly like its scalar form), clamp / rint / ldexp stay per component.  Every
+// each rounded exactly like its scalar form), clamp / rint / ldexp stay per component (the clamp
+// is the NaN-preserving one of vr_expf).  Every
 // component goes through the operation sequence of vr_expf above -- same bits.
 typedef float float2v __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ float2v splat2(float v) { return (float2v){v, v}; }
 static __device__ __forceinline__ float2v vr_expf2(float2v x) {
-    x.x = __builtin_amdgcn_fmed3f(x.x, -104.0f, 89.0f);
-    x.y = __builtin_amdgcn_fmed3f(x.y, -104.0f, 89.0f);
+    x = __builtin_elementwise_minimum(__builtin_elementwise_maximum(x, splat2(-104.0f)), splat2(89.0f));
     const float2v t = x * splat2(1.44269502162933349609375f);
     const float2v kf = {__builtin_rintf(t.x), __builtin_rintf(t.y)};
     float2v r = __builtin_elementwise_fma(kf, splat2(-0.693145751953125f), x);

@@ -1293,7 +1293,11 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
                     // taken now; the colour of this sample -- which nothing else depends on --
                     // becomes a work item for the shade phase.
                     if (COUNT) rc.hits++;
-                    const float att = vr_expf(-delta_t * ray.delta_scale * sigma);
+                    // vr_expf_nonan: the argument is never NaN -- sigma > sigma_thresh is false
+                    // for a NaN sigma, and delta_t (>= step_size > 0) and delta_scale are finite
+                    // and positive, so a sigma of +inf gives -inf, not NaN.  (Only a product
+                    // delta_t * delta_scale below 2^-150 could meet an infinite sigma as 0 * inf.)
+                    const float att = vr_expf_nonan(-delta_t * ray.delta_scale * sigma);
                     weight = ray.light * (1.f - att);
                     if (COUNT && p.render_depth)  // (depth launches take the FULL flavour)
                         ray.out[0] = P::madd(weight, ray.t, ray.out[0]);
