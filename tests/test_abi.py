@@ -204,7 +204,8 @@ def test_product_sources_carry_no_experiment_hooks_and_the_patch_applies(tmp_pat
     sources themselves must not name a hook, the patch must apply to them as they are, and the
     product build must refuse the hooks' flags."""
     csrc = os.path.join(ROOT, "volrend_amd", "csrc")
-    for f in ("vr_kernels.hip", "vr_api.cpp", "vr_internal.h", "vr_device_math.h"):
+    for f in ("vr_kernels.hip", "vr_api.cpp", "vr_internal.h", "vr_device_math.h", "vr_host.h", "vr_upload.cpp",
+              "vr_launch.cpp"):
         text = open(os.path.join(csrc, f)).read()
         assert not re.search(r"VR_EXP_|\bTL3?_[A-Z]|VR_ABLATE|VR_TIMELINE|vr_experiment_hooks", text), f
     assert not os.path.exists(os.path.join(csrc, "vr_experiment_hooks.h"))

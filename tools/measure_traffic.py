@@ -57,7 +57,8 @@ GROUPS = {
     # TA_* and TD_* counters abort rocprofv3 on this pool (measured twice in round 1): not offered
 }
 SOURCES = ["volrend_amd/csrc/vr_kernels.hip", "volrend_amd/csrc/vr_device_math.h",
-           "volrend_amd/csrc/vr_internal.h", "volrend_amd/csrc/vr_api.cpp", "include/volrend_hip.h"]
+           "volrend_amd/csrc/vr_internal.h", "volrend_amd/csrc/vr_api.cpp", "include/volrend_hip.h",
+           "volrend_amd/csrc/vr_host.h", "volrend_amd/csrc/vr_upload.cpp", "volrend_amd/csrc/vr_launch.cpp"]
 
 
 def kernel_source_hash() -> str:

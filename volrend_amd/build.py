@@ -24,8 +24,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvolrend_hip.so")
-SOURCES = ["vr_kernels.hip", "vr_api.cpp"]
-HEADERS = ["vr_internal.h", "vr_device_math.h", os.path.join(ROOT, "include", "volrend_hip.h")]
+SOURCES = ["vr_kernels.hip", "vr_api.cpp", "vr_upload.cpp", "vr_launch.cpp"]
+HEADERS = ["vr_internal.h", "vr_device_math.h", "vr_host.h", os.path.join(ROOT, "include", "volrend_hip.h")]
 EXPERIMENTS = os.path.join(ROOT, "tools", "experiments")
 HOOK_FLAGS = ("-DVR_ABLATE", "-DVR_TIMELINE", "-DVR_ROLE_DEBUG", "-DVR_MIN_WAVES_PER_EU", "-DVR_SH16_ROWS",
               "-DVR_SHADE_SCHED_BARRIER", "-DVR_SH16_WAVES", "-DVR_SH25_WAVES", "-DVR_SH9_WAVES", "-DVR_PACKED_EXP",

@@ -1,0 +1,380 @@
+// vr_launch.cpp -- launches (include/volrend_hip.h): vr_render_batch, vr_reserve*, vr_tree_status*,
+// the launch geometry and the launch-slot ring.  Built with -ffp-contract=off (the host-side
+// Rodrigues pre-computation below must round like the oracle).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstring>
+#include <mutex>
+
+#include "vr_host.h"
+
+namespace {
+
+// same rounding sequence as the oracle's norm3 (strict / fma)
+float host_norm3(const float* d, int fma) {
+    float s;
+    if (fma) {
+        s = std::fmaf(d[0], d[0], d[1] * d[1]);
+        s = std::fmaf(d[2], d[2], s);
+    } else {
+        s = d[0] * d[0] + d[1] * d[1];
+        s = d[2] * d[2] + s;
+    }
+    return std::sqrt(s);
+}
+
+// basis words kept per ray in the ray buffer: what the kernel flavour for this basis_dim reads
+int basis_words_of(const VrTreeOpaque* t) {
+    const int bd = t->desc.basis_dim;
+    if (t->desc.format == VR_FORMAT_RGBA || bd < 0) return 0;
+    return (bd == 4 || bd == 9 || bd == 16 || bd == 25) ? bd : 1;
+}
+
+// SH trees with a basis size the kernel knows: the ray record carries the view direction (3 words)
+// and the lane that takes the ray evaluates the basis; everything else carries the basis values
+bool ray_carries_vdir(const VrTreeOpaque* t) {
+    const int bw = basis_words_of(t);
+    return t->desc.format == VR_FORMAT_SH && bw > 3;
+}
+int ray_tail_words_of(const VrTreeOpaque* t) { return ray_carries_vdir(t) ? 3 : basis_words_of(t); }
+
+size_t ray_buffer_bytes(uint32_t total_rays, int tail_words) {
+    // the ray queues own whole groups of 16 blocks of 64 rays (vr_kernels.hip "Ray queues")
+    const size_t slots = (((size_t)total_rays / 64 + 15) / 16) * 16 * 64;
+    return slots * (16 + (size_t)tail_words) * sizeof(uint32_t);  // kRayWords + tail
+}
+
+// Replaces the ray buffer of a slot the caller owns (it holds the launch mutex, or has marked the
+// slot `growing` and dropped it) by one of `bytes`.  The slot's last launch must have finished
+// before its buffer goes; if that wait fails the buffer is still freed (hipFree synchronises by
+// itself): only a failing allocation fails, and nothing is leaked either way.
+hipError_t replace_ray_buffer(LaunchSlot& ls, size_t bytes) {
+    if (ls.rays) {
+        if (ls.used) (void)hipEventSynchronize(ls.done.get());
+        (void)ls.rays.reset();
+        (void)hipGetLastError();
+    }
+    return ls.rays.alloc(bytes);
+}
+
+}  // namespace
+
+void fill_tree_params(vr::KParams& k, const VrTreeOpaque* t) {
+    k.nodes = t->arrays[kNodes].get<uint32_t>();
+    k.leaves = t->arrays[kLeaves].get<uint16_t>();
+    k.top = t->arrays[kTop].get<uint2>();
+    k.bricks = t->arrays[kBricks].get<uint32_t>();
+    k.top_levels = t->top_levels;
+    k.brick_levels = t->brick_levels;
+    k.brick_blocked = t->brick_blocked;
+    k.extra = t->extra.get<float>();
+    for (int i = 0; i < 3; ++i) {
+        k.offset[i] = t->desc.offset[i];
+        k.scale[i] = t->desc.scale[i];
+    }
+    k.N = t->desc.N;
+    k.N3 = t->desc.N * t->desc.N * t->desc.N;
+    k.capacity = t->desc.capacity;
+    k.data_dim = t->desc.data_dim;
+    k.format = t->desc.format;
+    k.basis_dim = t->desc.basis_dim;
+    k.leaf_stride_h = t->leaf_stride_h;
+    k.max_depth = t->max_depth;
+    k.ndc_width = t->desc.ndc_width;
+    k.ndc_height = t->desc.ndc_height;
+    k.ndc_focal = t->desc.ndc_focal;
+    k.status = t->status.get<uint32_t>();
+    k.sched_stats = t->sched_stats.get<unsigned long long>();
+    for (int i = 0; i < 4; ++i) k.touch[i] = t->touch[i].get<uint32_t>();
+}
+
+int tile_geometry(int width, int height, int tile_w, int tile_h, int rank, int world, vr::KParams& k) {
+    if (width <= 0 || height <= 0) return fail(VR_ERR_INVALID_ARGUMENT, "empty image");
+    if (tile_w == 0 && tile_h == 0) {
+        tile_w = (width + 7) & ~7;
+        tile_h = (height + 7) & ~7;
+    }
+    if (tile_w <= 0 || tile_h <= 0 || (tile_w & 7) || (tile_h & 7))
+        return fail(VR_ERR_INVALID_ARGUMENT, "tile size %dx%d must be positive multiples of 8",
+                    tile_w, tile_h);
+    k.tile_w = tile_w;
+    k.tile_h = tile_h;
+    k.tiles_x = (width + tile_w - 1) / tile_w;
+    k.tiles_y = (height + tile_h - 1) / tile_h;
+    k.rank = rank;
+    k.world = world < 1 ? 1 : world;
+    k.n_local_tiles = (int32_t)(((int64_t)k.tiles_x * k.tiles_y - rank + k.world - 1) / k.world);
+    k.wblocks_per_tile_x = tile_w / 8;
+    k.wblocks_per_tile = (tile_w / 8) * (tile_h / 8);
+    k.n_wave_blocks = (int64_t)k.n_local_tiles * k.wblocks_per_tile;
+    return VR_OK;
+}
+
+int launch_geometry(int width, int height, int tile_w, int tile_h, int rank, int world, int n_frames,
+                    vr::KParams& k) {
+    // pixel coordinates travel as 16+16 bits, pixel offsets as 32 bits
+    if (width < 1 || height < 1 || width > 65535 || height > 65535)
+        return fail(VR_ERR_INVALID_ARGUMENT, "image size %dx%d outside [1, 65535]", width, height);
+    if (int rc = tile_geometry(width, height, tile_w, tile_h, rank, world, k)) return rc;
+    const int64_t total = k.n_wave_blocks * 64 * n_frames;
+    if (total >= (1ll << 30))  // ray-buffer fields are addressed with 32-bit byte offsets
+        return fail(VR_ERR_INVALID_ARGUMENT, "batch of %lld rays exceeds the 2^30-ray queue",
+                    (long long)total);
+    k.total_rays = (uint32_t)total;
+    return VR_OK;
+}
+
+extern "C" {
+
+int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                    const VrFrame* frames, void* stream) {
+    if (!t || !cams || !opt || !frames) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_frames < 1 || n_frames > VR_MAX_BATCH)
+        return fail(VR_ERR_INVALID_ARGUMENT, "n_frames=%d outside [1,%d]", n_frames, VR_MAX_BATCH);
+    const VrFrame* f = &frames[0];
+    const VrCamera* cam = &cams[0];
+    if (f->fp_mode != VR_FP_STRICT && f->fp_mode != VR_FP_FMA)
+        return fail(VR_ERR_INVALID_ARGUMENT, "unknown fp_mode %d", f->fp_mode);
+    if (f->layout != VR_LAYOUT_FRAME && f->layout != VR_LAYOUT_COMPACT)
+        return fail(VR_ERR_INVALID_ARGUMENT, "unknown layout %d", f->layout);
+    const int world = f->world < 1 ? 1 : f->world;
+    if (f->rank < 0 || f->rank >= world)
+        return fail(VR_ERR_INVALID_ARGUMENT, "rank %d outside world %d", f->rank, world);
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = launch_geometry(cam->width, cam->height, f->tile_w, f->tile_h, f->rank, world, n_frames, k))
+        return rc;
+    {
+        const int64_t pitch = f->pitch ? f->pitch : (int64_t)cam->width * 4;
+        if (pitch < (int64_t)cam->width * 4 || pitch * cam->height >= (1ll << 32))
+            return fail(VR_ERR_INVALID_ARGUMENT, "pitch %lld unusable for a %dx%d frame",
+                        (long long)pitch, cam->width, cam->height);
+    }
+    if (!(cam->fx != 0.f) || !(cam->fy != 0.f))
+        return fail(VR_ERR_INVALID_ARGUMENT, "focal length must be non-zero");
+
+    bool instrumented = false, any_accum = false;
+    for (int i = 0; i < n_frames; ++i) {
+        const VrFrame& fi = frames[i];
+        const VrCamera& ci = cams[i];
+        if (!fi.rgba) return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: rgba is NULL", i);
+        // one launch shares everything but the pose and the buffers
+        if (ci.width != cam->width || ci.height != cam->height || ci.fx != cam->fx ||
+            ci.fy != cam->fy)
+            return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: intrinsics differ within the batch", i);
+        if (fi.pitch != f->pitch || fi.offscreen != f->offscreen || fi.layout != f->layout ||
+            fi.tile_w != f->tile_w || fi.tile_h != f->tile_h || fi.rank != f->rank ||
+            fi.world != f->world || fi.fp_mode != f->fp_mode)
+            return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: layout/shard/fp_mode differ within the batch", i);
+        instrumented = instrumented || fi.counters != nullptr;
+        any_accum = any_accum || fi.accum != nullptr;
+    }
+
+    // the reference spins forever on step_size <= 0 (rt_core.cuh:108-175: t never advances past
+    // a leaf face); the kernel's iteration cap would cut such rays short silently -- refuse.
+    if (!(opt->step_size > 0.f))
+        return fail(VR_ERR_INVALID_ARGUMENT, "step_size must be positive (got %g)",
+                    (double)opt->step_size);
+
+    DeviceGuard device_guard(t->device);
+    k.width = cam->width;
+    k.height = cam->height;
+    k.fx = cam->fx;
+    k.fy = cam->fy;
+    k.step_size = opt->step_size;
+    k.sigma_thresh = opt->sigma_thresh;
+    k.stop_thresh = opt->stop_thresh;
+    k.background_brightness = opt->background_brightness;
+    memcpy(k.bbox, opt->render_bbox, sizeof(k.bbox));
+    k.basis_min = opt->basis_minmax[0];
+    k.basis_max = opt->basis_minmax[1];
+    k.render_depth = opt->render_depth != 0;
+    k.enable_probe = opt->enable_probe != 0;
+    k.probe_disp_size = opt->probe_disp_size;
+
+    // rodrigues (reference src/cuda/volrend.cu:57-71): angle/axis/cos/sin are
+    // uniform over the frame -> once here, with the oracle's rounding sequence
+    const float angle = host_norm3(opt->rot_dirs, f->fp_mode == VR_FP_FMA);
+    if ((double)angle < 1e-6) {
+        k.rot_enabled = 0;
+    } else {
+        k.rot_enabled = 1;
+        for (int i = 0; i < 3; ++i) k.rot_k[i] = opt->rot_dirs[i] / angle;
+        k.rot_cos = cosf(angle);
+        k.rot_sin = sinf(angle);
+    }
+    k.n_frames = n_frames;
+    k.pitch = f->pitch ? f->pitch : (int64_t)cam->width * 4;
+    k.offscreen = f->offscreen != 0;
+    k.layout = f->layout;
+    k.instrumented = instrumented ? 1 : 0;
+    k.any_accum = any_accum ? 1 : 0;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    std::unique_lock<std::mutex> guard(t->launch_mutex);
+    fill_tree_params(k, t);  // (under the mutex: vr_touch_enable / vr_touch_count (re)allocate the bitmaps)
+    const Tuning tn = t->tn;  // (a copy: the mutex is dropped once below, while a slot grows)
+    // lookup structure (top + bricks) beyond 4x the aggregate L2 (8 x 4 MiB on MI355X): the record
+    // stream would keep evicting it -- see the DMA loads in vr_kernels.hip
+    k.records_nt = tn.records_nt >= 0 ? tn.records_nt
+                                      : (t->arrays[kTop].bytes() + t->arrays[kBricks].bytes() > (128ull << 20));
+    k.march_max = tn.march_max;
+    k.refill_min = tn.refill_min;
+    k.drain_flush = tn.drain_flush;
+    k.max_iter = tn.max_iter;
+    k.frame_group = tn.frame_group < 1 || tn.frame_group > n_frames ? n_frames : tn.frame_group;
+    k.super_block = tn.super_block;
+    // launch slot: per-launch scratch in device memory (ring, see LaunchSlot)
+    const size_t need = ray_buffer_bytes(k.total_rays, ray_tail_words_of(t));
+    unsigned slot = kLaunchSlots;
+    for (int want_fit = 1; want_fit >= 0 && slot == kLaunchSlots; --want_fit) {
+        for (int pass = 0; pass < 2 && slot == kLaunchSlots; ++pass)
+            for (unsigned i = 0; i < kLaunchSlots; ++i) {
+                const LaunchSlot& c = t->slots[i];
+                if (c.growing || (want_fit && c.rays.bytes() < need)) continue;
+                const bool ok = pass == 0 ? (c.used && c.last_stream == hs)
+                                          : (!c.used || hipEventQuery(c.done.get()) == hipSuccess);
+                if (ok) {
+                    slot = i;
+                    break;
+                }
+            }
+    }
+    (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is an answer, not an error
+    if (slot == kLaunchSlots) {  // all busy elsewhere: queue up behind one (not one that is growing)
+        for (unsigned a = 0; a < kLaunchSlots && slot == kLaunchSlots; ++a)
+            if (!t->slots[(t->launch_seq + a) % kLaunchSlots].growing) slot = (t->launch_seq + a) % kLaunchSlots;
+        if (slot == kLaunchSlots)
+            return fail(VR_ERR_HIP, "all %u launch slots are being resized by other threads", kLaunchSlots);
+    }
+    t->launch_seq++;
+    LaunchSlot& ls = t->slots[slot];
+    k.frames = t->slot_frames.get<vr::FrameDesc>() + (size_t)slot * vr::kMaxBatch;
+    k.queue_head = t->slot_heads.get<uint32_t>() + kSlotWords * slot + 16;
+    k.n_queues = tn.xcd_queues ? 8 : 1;
+    k.chunk_max = tn.chunk_max;
+    k.basis_words = basis_words_of(t);
+    k.ray_tail_words = ray_tail_words_of(t);
+    k.ray_vdir = ray_carries_vdir(t) ? 1 : 0;
+    if (ls.rays.bytes() < need) {
+        // First use of the slot, or a larger batch than any before: (re)allocate.  This is the
+        // one place where an enqueue-only call may block -- on THIS slot's previous launch
+        // only, and hipFree/hipMalloc may synchronise the device; vr_reserve() / vr_reserve_tiles()
+        // move it out of the render loop.
+        // The wait, the free and the allocation run WITHOUT the launch mutex: the slot is marked
+        // `growing` (nobody else picks it) and other threads keep enqueueing on the other slots.
+        ls.growing = true;
+        guard.unlock();
+        const hipError_t ge = replace_ray_buffer(ls, need);
+        guard.lock();
+        ls.growing = false;
+        fill_tree_params(k, t);  // (the mutex was dropped: see above)
+        if (ge != hipSuccess)
+            return fail(hip_code(ge), "ray buffer of %zu bytes: %s", need, hipGetErrorString(ge));
+    }
+    k.ray_buf_rw = ls.rays.get<uint32_t>();
+    k.ray_buf = k.ray_buf_rw;
+    // whoever used this slot last (any stream) must have finished before its scratch is rewritten
+    if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
+    // From here on kernels of this launch may be in the stream: whatever happens below (a later
+    // enqueue failing), the slot's event is recorded behind them and the slot is marked used, so
+    // that the next user of the slot -- any stream -- waits for whatever did get enqueued.
+    struct SlotSeal {
+        LaunchSlot& ls;
+        hipStream_t hs;
+        ~SlotSeal() {
+            if (hipEventRecord(ls.done.get(), hs) == hipSuccess) {
+                ls.used = true;
+                ls.last_stream = hs;
+            } else {
+                (void)hipGetLastError();
+            }
+        }
+    } seal{ls, hs};
+    k.probe_coeffs = t->probe_buf.get<float>() + (size_t)slot * (size_t)t->desc.data_dim;
+    if (k.enable_probe)  // launch_renderer's pre-kernel, volrend.cu:202-209
+        HIP_TRY(vr::launch_probe(k, opt->probe, const_cast<float*>(k.probe_coeffs), hs));
+
+    // frame table -> device memory, kTableChunk poses per (tiny) kernel
+    for (int first = 0; first < n_frames; first += vr::kTableChunk) {
+        vr::FrameTable tbl;
+        memset(&tbl, 0, sizeof(tbl));
+        tbl.first = first;
+        tbl.n = n_frames - first < vr::kTableChunk ? n_frames - first : vr::kTableChunk;
+        for (int i = 0; i < tbl.n; ++i) {
+            memcpy(tbl.f[i].xf, cams[first + i].transform, sizeof(tbl.f[i].xf));
+            tbl.f[i].rgba = static_cast<uint8_t*>(frames[first + i].rgba);
+            tbl.f[i].accum = frames[first + i].accum;
+            tbl.f[i].depth = frames[first + i].depth;
+            tbl.f[i].counters = reinterpret_cast<unsigned long long*>(frames[first + i].counters);
+        }
+        HIP_TRY(vr::launch_prepare(k, tbl, hs));
+    }
+    // waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
+    // two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
+    // 4 waves find room there much earlier (vr_kernels.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
+    // two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
+    // 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
+    const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
+    HIP_TRY(vr::launch_render(k, f->fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
+    return VR_OK;  // (`seal` records the slot's event)
+}
+
+int vr_reserve_tiles(vr_tree_t t, int width, int height, int n_frames, int tile_w, int tile_h,
+                     int world, int n_slots) {
+    if (!t) return fail(VR_ERR_INVALID_ARGUMENT, "tree is NULL");
+    if (n_frames < 1 || n_frames > VR_MAX_BATCH)
+        return fail(VR_ERR_INVALID_ARGUMENT, "vr_reserve(%d x %d, %d frames) out of range", width,
+                    height, n_frames);
+    if (n_slots < 1 || n_slots > (int)kLaunchSlots)
+        return fail(VR_ERR_INVALID_ARGUMENT, "n_slots=%d outside [1,%u]", n_slots, kLaunchSlots);
+    // exactly the ray count vr_render_batch computes, for rank 0 (which holds the most tiles)
+    vr::KParams geo;
+    if (int rc = launch_geometry(width, height, tile_w, tile_h, 0, world, n_frames, geo)) return rc;
+    const size_t need = ray_buffer_bytes(geo.total_rays, ray_tail_words_of(t));
+    DeviceGuard device_guard(t->device);
+    std::lock_guard<std::mutex> guard(t->launch_mutex);
+    for (int i = 0; i < n_slots; ++i) {
+        LaunchSlot& ls = t->slots[i];
+        if (ls.growing || ls.rays.bytes() >= need) continue;
+        const hipError_t e = replace_ray_buffer(ls, need);
+        if (e != hipSuccess) return fail(hip_code(e), "ray buffer of %zu bytes: %s", need, hipGetErrorString(e));
+    }
+    return VR_OK;
+}
+
+// two slots of whole frames: what a render loop on one stream (one slot) or on two alternating
+// streams needs
+int vr_reserve(vr_tree_t t, int width, int height, int n_frames) {
+    return vr_reserve_tiles(t, width, height, n_frames, 0, 0, 1, 2);
+}
+
+int vr_tree_status(vr_tree_t t, uint32_t* status, int reset) {
+    if (!t || !status) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard guard(t->device);
+    HIP_TRY(hipMemcpy(status, t->status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(t->status.get(), 0, sizeof(uint32_t)));
+    return VR_OK;
+}
+
+int vr_tree_status_on(vr_tree_t t, uint32_t* status, int reset, void* stream) {
+    if (!t || !status) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard guard(t->device);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // a pinned word per calling thread: the copy is asynchronous and ordered on `hs` alone.
+    // Portable: the thread may read the status of trees on several devices through it.
+    thread_local uint32_t* pinned = nullptr;
+    if (!pinned) HIP_TRY(hipHostMalloc((void**)&pinned, sizeof(uint32_t), hipHostMallocPortable));
+    HIP_TRY(hipMemcpyAsync(pinned, t->status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+    if (reset) HIP_TRY(hipMemsetAsync(t->status.get(), 0, sizeof(uint32_t), hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    *status = *pinned;
+    return VR_OK;
+}
+
+int vr_render(vr_tree_t t, const VrCamera* cam, const VrRenderOptions* opt, const VrFrame* f,
+              void* stream) {
+    return vr_render_batch(t, 1, cam, opt, f, stream);
+}
+
+}  // extern "C"
