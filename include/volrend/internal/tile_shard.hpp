@@ -16,10 +16,13 @@
 // enqueue order -- consumers (vr_read_back) enqueue there.
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "volrend/internal/hip_owners.hpp"
 #include "volrend/n3tree.hpp"
+#include "volrend_gather.h"
 #include "volrend_hip.h"
 
 namespace volrend {
@@ -45,31 +48,32 @@ class TileShardRenderer {
     // Enqueues launch number `seq` (0, 1, 2, ...): cams[0..n) -> frames(seq & 1)[0..n).
     void render(int seq, const VrCamera* cams, int n, const VrRenderOptions& opt, int fp_mode);
     // Assembled frames of buffer set `set` on the root device: frame i at + i * frame_bytes()
-    uint8_t* frames(int set) const { return frames_[set]; }
+    uint8_t* frames(int set) const { return frames_[set].get<uint8_t>(); }
     size_t frame_bytes() const { return (size_t)width_ * height_ * 4; }
-    void* out_stream() const { return comm_stream_[0]; }
-    int root_device() const { return device_[0]; }
+    void* out_stream() const { return ranks_[0].comm_stream.get(); }
+    int root_device() const { return ranks_[0].device; }
     // "RCCL <version>, N ranks" or the rehearsal label
     const std::string& transport() const { return transport_; }
     void sync();
 
    private:
-    void init(const N3Tree& tree, const TileShardConfig& cfg);
-    void release();
+    struct Rank {
+        int device = 0;
+        vr_tree_t tree = nullptr;  // its replica: `clone`, or the caller's tree when that lives on the root
+        std::unique_ptr<VrTreeOpaque, decltype(&vr_tree_free)> clone{nullptr, vr_tree_free};
+        DeviceStream render_stream, comm_stream;
+        DeviceEvent rendered[2], released[2];  // per buffer set
+        bool released_used[2] = {false, false};
+        DeviceBuffer compact[2];  // peers; rank 0 only in the self-transfer mode
+        std::unique_ptr<VrGatherOpaque, decltype(&vr_gather_free)> gather{nullptr, vr_gather_free};
+    };
     int n_, width_, height_, tile_w_, tile_h_, max_batch_;
     bool share_, rccl_self_;
     int64_t compact_bytes_ = 0;  // one rank's share of one frame
-    std::vector<int> device_;
-    std::vector<vr_tree_t> tree_;     // tree_[0] is borrowed when it already lives on device_[0]
-    std::vector<bool> owns_tree_;
-    std::vector<void*> render_stream_, comm_stream_;
-    std::vector<void*> rendered_[2], released_[2];  // events per rank and set
-    std::vector<bool> released_used_[2];
-    std::vector<uint8_t*> compact_[2];  // per rank (peers; rank 0 only in the self-transfer mode)
-    uint8_t* gather_[2] = {nullptr, nullptr};   // root: [n_ranks][max_batch][compact_bytes]
-    uint8_t* frames_[2] = {nullptr, nullptr};   // root: [max_batch][H][W][4]
-    std::vector<void*> comm_;  // vr_gather_t per rank
-    std::string transport_, p2p_note_;
+    std::vector<Rank> ranks_;
+    DeviceBuffer gather_[2];  // root: [n_ranks][max_batch][compact_bytes]
+    DeviceBuffer frames_[2];  // root: [max_batch][H][W][4]
+    std::string transport_;
 };
 
 }  // namespace internal

@@ -58,7 +58,8 @@ GROUPS = {
 }
 SOURCES = ["volrend_amd/csrc/vr_kernels.hip", "volrend_amd/csrc/vr_device_math.h",
            "volrend_amd/csrc/vr_internal.h", "volrend_amd/csrc/vr_api.cpp", "include/volrend_hip.h",
-           "volrend_amd/csrc/vr_host.h", "volrend_amd/csrc/vr_upload.cpp", "volrend_amd/csrc/vr_launch.cpp"]
+           "volrend_amd/csrc/vr_host.h", "volrend_amd/csrc/vr_upload.cpp", "volrend_amd/csrc/vr_launch.cpp",
+           "include/volrend/internal/hip_owners.hpp"]
 
 
 def kernel_source_hash() -> str:

@@ -25,7 +25,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvolrend_hip.so")
 SOURCES = ["vr_kernels.hip", "vr_api.cpp", "vr_upload.cpp", "vr_launch.cpp"]
-HEADERS = ["vr_internal.h", "vr_device_math.h", "vr_host.h", os.path.join(ROOT, "include", "volrend_hip.h")]
+HEADERS = ["vr_internal.h", "vr_device_math.h", "vr_host.h", os.path.join(ROOT, "include", "volrend_hip.h"),
+           os.path.join(ROOT, "include", "volrend", "internal", "hip_owners.hpp")]
 EXPERIMENTS = os.path.join(ROOT, "tools", "experiments")
 HOOK_FLAGS = ("-DVR_ABLATE", "-DVR_TIMELINE", "-DVR_ROLE_DEBUG", "-DVR_MIN_WAVES_PER_EU", "-DVR_SH16_ROWS",
               "-DVR_SHADE_SCHED_BARRIER", "-DVR_SH16_WAVES", "-DVR_SH25_WAVES", "-DVR_SH9_WAVES", "-DVR_PACKED_EXP",

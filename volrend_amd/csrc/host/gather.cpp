@@ -8,6 +8,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <vector>
 
@@ -76,11 +77,17 @@ int vr_gather_init_rank(const void* id_bytes, int rank, int world, int device, v
 
 int vr_gather_init_all(int n, const int* devices, vr_gather_t* out) {
     if (n < 1 || !devices || !out) return fail("bad arguments");
+    // the handles exist before the communicators do: once ncclCommInitAll has succeeded nothing can
+    // fail, so out[0..n) is filled completely or not at all
+    std::vector<std::unique_ptr<VrGatherOpaque>> gs((size_t)n);
+    for (auto& g : gs) {
+        g.reset(new (std::nothrow) VrGatherOpaque());
+        if (!g) return fail("host allocation failed");
+    }
     std::vector<ncclComm_t> comms((size_t)n);
     NCCL_TRY(ncclCommInitAll(comms.data(), n, devices));
     for (int r = 0; r < n; ++r) {
-        VrGatherOpaque* g = new (std::nothrow) VrGatherOpaque();
-        if (!g) return fail("host allocation failed");
+        VrGatherOpaque* g = gs[(size_t)r].release();
         g->comm = comms[(size_t)r];
         g->rank = r;
         g->world = n;

@@ -21,6 +21,7 @@
 
 #include <memory>
 
+#include "volrend/internal/hip_owners.hpp"
 #include "volrend/internal/imwrite.hpp"
 #include "volrend/internal/opts.hpp"
 #include "volrend/internal/tile_shard.hpp"
@@ -358,49 +359,53 @@ int main(int argc, char* argv[]) {
     }
     // Device frames: two sets of `batch` contiguous frames -- launch k renders into set k % 2
     // while the read-back of launch k - 1 drains the other one (the tile shard brings its own).
-    uint8_t* image_sets[2] = {nullptr, nullptr};
+    internal::DeviceBuffer image_sets[2];
     if (!shard)
-        for (auto& is : image_sets) HIP_OK(hipMalloc((void**)&is, frame_bytes * batch));
-    uint8_t* host_sets[2] = {nullptr, nullptr};  // pinned, one per in-flight batch
-    std::unique_ptr<EncodePool> pool;
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t rendered[2] = {nullptr, nullptr}, copied[2] = {nullptr, nullptr};
+        for (auto& is : image_sets) HIP_OK(is.alloc(frame_bytes * batch));
+    internal::PinnedBuffer host_sets[2];  // one per in-flight batch
+    std::unique_ptr<EncodePool> pool;     // (goes before host_sets: its workers read them)
+    internal::DeviceStream copy_stream;
+    internal::DeviceEvent rendered[2], copied[2];
     // one event behind the copy of every frame of a set: a frame is handed to the encoders as soon
     // as ITS copy has landed, so that the encoding of the last launch runs under its own copies
-    std::vector<hipEvent_t> frame_copied[2];
+    std::vector<internal::DeviceEvent> frame_copied[2];
     if (!out_dir.empty()) {
         make_dirs(out_dir);
-        for (auto& hs : host_sets) HIP_OK(hipHostMalloc((void**)&hs, frame_bytes * batch));
+        for (auto& hs : host_sets) HIP_OK(hs.alloc(frame_bytes * batch));
         unsigned nt = std::thread::hardware_concurrency();
         nt = nt == 0 ? 4 : (nt > 64 ? 64 : nt);
         pool.reset(new EncodePool(nt));
-        HIP_OK(hipStreamCreateWithFlags(&copy_stream, hipStreamNonBlocking));
+        HIP_OK(copy_stream.create(hipStreamNonBlocking));
         for (int i = 0; i < 2; ++i) {
-            HIP_OK(hipEventCreateWithFlags(&rendered[i], hipEventDisableTiming));
-            HIP_OK(hipEventCreateWithFlags(&copied[i], hipEventDisableTiming));
+            HIP_OK(rendered[i].create());
+            HIP_OK(copied[i].create());
             frame_copied[i].resize((size_t)batch);
-            for (auto& e : frame_copied[i]) HIP_OK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (auto& e : frame_copied[i]) HIP_OK(e.create());
         }
     }
     // Render streams: launch k runs on stream k % n_streams and writes image set k % 2 -- with two
     // streams every stream owns one image set (the tile shard brings its own streams).
     const int n_streams = shard ? 1 : plan.n_streams;
+    internal::DeviceStream own_streams[2];
     hipStream_t streams[2] = {nullptr, nullptr};
     if (shard) streams[0] = static_cast<hipStream_t>(shard->out_stream());
     else
-        for (int i = 0; i < n_streams; ++i) HIP_OK(hipStreamCreate(&streams[i]));
-    hipEvent_t start, stop, joined;
-    HIP_OK(hipEventCreate(&start));
-    HIP_OK(hipEventCreate(&stop));
-    HIP_OK(hipEventCreateWithFlags(&joined, hipEventDisableTiming));
+        for (int i = 0; i < n_streams; ++i) {
+            HIP_OK(own_streams[i].create(hipStreamDefault));
+            streams[i] = own_streams[i].get();
+        }
+    internal::DeviceEvent start, stop, joined;
+    HIP_OK(start.create(hipEventDefault));
+    HIP_OK(stop.create(hipEventDefault));
+    HIP_OK(joined.create());
 
     // Frame egress of launch `seq` (frames [first, first + n)): called one launch late, so the
     // host waits for the copies of launch k - 1 while the GPU renders launch k.
     auto submit_encodes = [&](int set, size_t first, int n) {
         for (int i = 0; i < n; ++i) {
-            HIP_OK(hipEventSynchronize(frame_copied[set][(size_t)i]));
+            HIP_OK(hipEventSynchronize(frame_copied[set][(size_t)i].get()));
             const std::string fpath = out_dir + "/" + basenames[first + i] + ".png";
-            const uint8_t* src = host_sets[set] + frame_bytes * i;
+            const uint8_t* src = host_sets[set].get<uint8_t>() + frame_bytes * i;
             pool->submit(set, [fpath, src, width, height] {
                 internal::write_png_file(fpath, src, width, height);
             });
@@ -415,8 +420,8 @@ int main(int argc, char* argv[]) {
         fprintf(stderr, "ERROR: %s\n", vr_last_error());
         return 1;
     }
-    HIP_OK(hipEventRecord(start, streams[0]));
-    if (n_streams > 1) HIP_OK(hipStreamWaitEvent(streams[1], start, 0));  // the clock starts before any launch
+    HIP_OK(hipEventRecord(start.get(), streams[0]));
+    if (n_streams > 1) HIP_OK(hipStreamWaitEvent(streams[1], start.get(), 0));  // the clock starts before any launch
     int seq = 0;
     size_t prev_first = 0;
     int prev_n = 0;
@@ -434,13 +439,13 @@ int main(int argc, char* argv[]) {
             cams[i].fx = fx;
             cams[i].fy = fy;
             vr_default_frame(&frames[i]);
-            frames[i].rgba = shard ? nullptr : image_sets[set] + frame_bytes * i;
+            frames[i].rgba = shard ? nullptr : image_sets[set].get<uint8_t>() + frame_bytes * i;
             frames[i].offscreen = 1;
             frames[i].fp_mode = fp_mode;
         }
         // set `set` of the device frames was read back by launch seq - 2: that copy must be done
         // before this launch overwrites them (device-side wait, the host does not block)
-        if (copy_stream && seq >= 2) HIP_OK(hipStreamWaitEvent(stream, copied[set], 0));
+        if (copy_stream && seq >= 2) HIP_OK(hipStreamWaitEvent(stream, copied[set].get(), 0));
         const uint8_t* dev_frames = nullptr;
         if (shard) {
             try {
@@ -455,23 +460,23 @@ int main(int argc, char* argv[]) {
                 fprintf(stderr, "ERROR: %s\n", vr_last_error());
                 return 1;
             }
-            dev_frames = image_sets[set];
+            dev_frames = image_sets[set].get<uint8_t>();
         }
         if (!out_dir.empty()) {
-            HIP_OK(hipEventRecord(rendered[set], stream));
+            HIP_OK(hipEventRecord(rendered[set].get(), stream));
             pool->wait(set);  // the encoders (launch seq - 2) are done with this host buffer set
-            HIP_OK(hipStreamWaitEvent(copy_stream, rendered[set], 0));
+            HIP_OK(hipStreamWaitEvent(copy_stream.get(), rendered[set].get(), 0));
             // frame by frame (2.56 MB at 800 x 800: large enough for the copy engine), an event
             // behind each
             for (int i = 0; i < n; ++i) {
-                if (vr_read_back(host_sets[set] + frame_bytes * i, dev_frames + frame_bytes * i, 0, width,
-                                 height, copy_stream) != VR_OK) {
+                if (vr_read_back(host_sets[set].get<uint8_t>() + frame_bytes * i, dev_frames + frame_bytes * i,
+                                 0, width, height, copy_stream.get()) != VR_OK) {
                     fprintf(stderr, "ERROR: %s\n", vr_last_error());
                     return 1;
                 }
-                HIP_OK(hipEventRecord(frame_copied[set][(size_t)i], copy_stream));
+                HIP_OK(hipEventRecord(frame_copied[set][(size_t)i].get(), copy_stream.get()));
             }
-            HIP_OK(hipEventRecord(copied[set], copy_stream));
+            HIP_OK(hipEventRecord(copied[set].get(), copy_stream.get()));
             if (prev_n > 0) submit_encodes(set ^ 1, prev_first, prev_n);
             prev_first = first;
             prev_n = n;
@@ -484,11 +489,11 @@ int main(int argc, char* argv[]) {
         pool->wait(1);
     }
     if (n_streams > 1) {  // the clock stops behind the last launch of BOTH streams
-        HIP_OK(hipEventRecord(joined, streams[1]));
-        HIP_OK(hipStreamWaitEvent(streams[0], joined, 0));
+        HIP_OK(hipEventRecord(joined.get(), streams[1]));
+        HIP_OK(hipStreamWaitEvent(streams[0], joined.get(), 0));
     }
-    HIP_OK(hipEventRecord(stop, streams[0]));
-    HIP_OK(hipEventSynchronize(stop));
+    HIP_OK(hipEventRecord(stop.get(), streams[0]));
+    HIP_OK(hipEventSynchronize(stop.get()));
     // Everything has run: what the launches found out on the device surfaces now -- a ray that
     // hit the sample guard means wrong frames, and the reference's convention for device errors
     // is message + non-zero exit (src/cuda/common.cu:8-21).
@@ -500,27 +505,11 @@ int main(int argc, char* argv[]) {
         return 1;
     }
     float milliseconds = 0;
-    HIP_OK(hipEventElapsedTime(&milliseconds, start, stop));
+    HIP_OK(hipEventElapsedTime(&milliseconds, start.get(), stop.get()));
     milliseconds = milliseconds / trans.size();
 
     printf("%.10f ms per frame\n", milliseconds);
     printf("%.10f fps\n", 1000.f / milliseconds);
     printf("%.4f Mrays/s\n", (double)width * height / (milliseconds * 1e3));
-
-    pool.reset();
-    for (auto& hs : host_sets)
-        if (hs) HIP_OK(hipHostFree(hs));
-    for (int i = 0; i < 2; ++i) {
-        if (rendered[i]) HIP_OK(hipEventDestroy(rendered[i]));
-        if (copied[i]) HIP_OK(hipEventDestroy(copied[i]));
-        for (auto e : frame_copied[i]) HIP_OK(hipEventDestroy(e));
-    }
-    if (copy_stream) HIP_OK(hipStreamDestroy(copy_stream));
-    if (!shard) {
-        for (uint8_t* p : image_sets) HIP_OK(hipFree(p));
-        for (int i = 0; i < n_streams; ++i) HIP_OK(hipStreamDestroy(streams[i]));
-    }
-    HIP_OK(hipEventDestroy(joined));
-    shard.reset();
     return 0;
 }

@@ -2,6 +2,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "volrend/internal/check.hpp"
 #include "volrend/renderer_kernel.hpp"
 
 namespace volrend {
@@ -39,10 +40,6 @@ VrCamera to_c(const Camera& cam, const float* transform12) {
     return c;
 }
 
-void check(int rc, const char* what) {
-    if (rc != VR_OK) throw std::runtime_error(std::string(what) + ": " + vr_last_error());
-}
-
 }  // namespace
 
 void launch_renderer(const N3Tree& tree, const Camera& cam, const RenderOptions& options,
@@ -54,7 +51,7 @@ void launch_renderer(const N3Tree& tree, const Camera& cam, const RenderOptions&
     f.rgba = image_rgba8_dev;
     f.depth = depth_dev;
     f.offscreen = offscreen ? 1 : 0;
-    check(vr_render(tree.device, &c, &o, &f, stream), "vr_render");
+    internal::vr_check(vr_render(tree.device, &c, &o, &f, stream), "vr_render");
 }
 
 void launch_renderer_batch(const N3Tree& tree, const Camera& cam,
@@ -74,7 +71,7 @@ void launch_renderer_batch(const N3Tree& tree, const Camera& cam,
             frames[i].rgba = images[first + i];
             frames[i].offscreen = offscreen ? 1 : 0;
         }
-        check(vr_render_batch(tree.device, n, cams, &o, frames, stream), "vr_render_batch");
+        internal::vr_check(vr_render_batch(tree.device, n, cams, &o, frames, stream), "vr_render_batch");
     }
 }
 
@@ -91,14 +88,14 @@ void throw_on_status(uint32_t status) {
 void check_render_status(const N3Tree& tree) {
     if (!tree.device) return;
     uint32_t status = 0;
-    check(vr_tree_status(tree.device, &status, 1), "vr_tree_status");
+    internal::vr_check(vr_tree_status(tree.device, &status, 1), "vr_tree_status");
     throw_on_status(status);
 }
 
 void check_render_status(const N3Tree& tree, void* stream) {
     if (!tree.device) return;
     uint32_t status = 0;
-    check(vr_tree_status_on(tree.device, &status, 1, stream), "vr_tree_status_on");
+    internal::vr_check(vr_tree_status_on(tree.device, &status, 1, stream), "vr_tree_status_on");
     throw_on_status(status);
 }
 

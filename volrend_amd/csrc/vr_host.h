@@ -4,11 +4,19 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
-#include <utility>
 
 #include "vr_internal.h"
 
 #pragma GCC visibility push(hidden)
+
+// DeviceGuard, DeviceBuffer, DeviceEvent (inside the hidden region: they are not exported either).
+// A tree lives on ONE device; its calls run there under a DeviceGuard whatever the calling thread's
+// current device is (one host thread may drive the trees of several devices), and leave the
+// thread's device as they found it.
+#include "volrend/internal/hip_owners.hpp"
+using volrend::internal::DeviceBuffer;
+using volrend::internal::DeviceEvent;
+using volrend::internal::DeviceGuard;
 
 // Formats the message vr_last_error() returns (one buffer per thread, vr_api.cpp); returns `code`.
 int fail(int code, const char* fmt, ...);
@@ -21,66 +29,6 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? VR_ERR_OUT
             return fail(hip_code(e_), "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, \
                         __LINE__);                                                                    \
     } while (0)
-
-// A tree lives on ONE device; its calls run there whatever the calling thread's current device
-// is (one host thread may drive the trees of several devices), and leave the thread's device
-// as they found it.
-class DeviceGuard {
-   public:
-    explicit DeviceGuard(int device) {
-        if (hipGetDevice(&prev_) == hipSuccess && prev_ != device) switched_ = hipSetDevice(device) == hipSuccess;
-    }
-    ~DeviceGuard() { if (switched_) (void)hipSetDevice(prev_); }
-    DeviceGuard(const DeviceGuard&) = delete;
-    DeviceGuard& operator=(const DeviceGuard&) = delete;
-
-   private:
-    int prev_ = 0;
-    bool switched_ = false;
-};
-
-// The one owner of a device allocation and its size (move-only).  The memory is freed when the
-// owner goes, which must happen with the allocation's device current.
-class DeviceBuffer {
-   public:
-    DeviceBuffer() = default;
-    DeviceBuffer(DeviceBuffer&& o) noexcept : p_(std::exchange(o.p_, nullptr)), bytes_(std::exchange(o.bytes_, 0)) {}
-    ~DeviceBuffer() { (void)reset(); }
-    hipError_t alloc(size_t bytes) {  // (frees what it held first)
-        (void)reset();
-        const hipError_t e = hipMalloc(&p_, bytes);
-        if (e == hipSuccess) bytes_ = bytes;
-        else p_ = nullptr;
-        return e;
-    }
-    hipError_t reset() {
-        const hipError_t e = p_ ? hipFree(p_) : hipSuccess;
-        p_ = nullptr;
-        bytes_ = 0;
-        return e;
-    }
-    template <class T = void>
-    T* get() const { return static_cast<T*>(p_); }
-    size_t bytes() const { return bytes_; }
-    explicit operator bool() const { return p_ != nullptr; }
-
-   private:
-    void* p_ = nullptr;
-    size_t bytes_ = 0;
-};
-
-// The one owner of an event (timing disabled).
-class DeviceEvent {
-   public:
-    DeviceEvent() = default;
-    DeviceEvent(const DeviceEvent&) = delete;
-    ~DeviceEvent() { if (e_) (void)hipEventDestroy(e_); }
-    hipError_t create() { return hipEventCreateWithFlags(&e_, hipEventDisableTiming); }
-    hipEvent_t get() const { return e_; }
-
-   private:
-    hipEvent_t e_ = nullptr;
-};
 
 // Scheduling / layout knobs.  They never change results.  Every tree carries its OWN copy
 // (vr_tree_set_tuning), taken at upload from the process defaults; the defaults come from

@@ -710,7 +710,7 @@ int vr_tree_clone(vr_tree_t src, int device, vr_tree_t* out) {
         HIP_TRY(hipDeviceSynchronize());
     }
     DeviceGuard guard(device);
-    std::unique_ptr<VrTreeOpaque> t(new (std::nothrow) VrTreeOpaque());  // (freed under `guard`)
+    std::unique_ptr<VrTreeOpaque> t(new (std::nothrow) VrTreeOpaque());
     if (!t) return fail(VR_ERR_OUT_OF_MEMORY, "host allocation failed");
     static_cast<TreeShape&>(*t) = *src;
     t->device = device;
@@ -754,9 +754,7 @@ int vr_tree_clone(vr_tree_t src, int device, vr_tree_t* out) {
 }
 
 int vr_tree_free(vr_tree_t t) {
-    if (!t) return VR_OK;
-    DeviceGuard guard(t->device);  // (the tree's owners free its memory on its device)
-    delete t;
+    delete t;  // (the tree's owners free its memory on its device)
     return VR_OK;
 }
 
