@@ -204,14 +204,17 @@ def test_product_sources_carry_no_experiment_hooks_and_the_patch_applies(tmp_pat
     sources themselves must not name a hook, the patch must apply to them as they are, and the
     product build must refuse the hooks' flags."""
     csrc = os.path.join(ROOT, "volrend_amd", "csrc")
-    for f in ("vr_kernels.hip", "vr_api.cpp", "vr_internal.h", "vr_device_math.h", "vr_host.h", "vr_upload.cpp",
+    for f in ("vr_render.hip", "vr_tree_kernels.hip", "vr_dev_layout.h", "vr_dev_shade.h", "vr_dev_query.h",
+              "vr_dev_rays.h", "vr_api.cpp", "vr_internal.h", "vr_device_math.h", "vr_host.h", "vr_upload.cpp",
               "vr_launch.cpp"):
         text = open(os.path.join(csrc, f)).read()
         assert not re.search(r"VR_EXP_|\bTL3?_[A-Z]|VR_ABLATE|VR_TIMELINE|vr_experiment_hooks", text), f
     assert not os.path.exists(os.path.join(csrc, "vr_experiment_hooks.h"))
     build.hooked_sources(str(tmp_path), dry_run=True)      # raises if a hunk does not apply
     build.hooked_sources(str(tmp_path))
-    patched = open(os.path.join(str(tmp_path), "vr_kernels.hip")).read()
-    assert "VR_EXP_BRICK_WORD(" in patched and "TL3_ROUND(go)" in patched and "vr_experiment_hooks.h" in patched
+    def patched(f):
+        return open(os.path.join(str(tmp_path), f)).read()
+    assert "VR_EXP_BRICK_WORD(" in patched("vr_dev_query.h")
+    assert "TL3_ROUND(go)" in patched("vr_render.hip") and "vr_experiment_hooks.h" in patched("vr_render.hip")
     with pytest.raises(ValueError):
         build.build(extra_flags=["-DVR_ABLATE=4"])          # never into libvolrend_hip.so

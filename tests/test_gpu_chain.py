@@ -162,7 +162,7 @@ def test_tree_with_backward_links(torch_cuda):
 def test_every_ray_queue_is_drained(torch_cuda, xcd_queues):
     """The ray buffer is cut into 8 queues, one per XCD; a wave steals from a foreign queue only
     while that queue holds a good part of its rays and leaves the rest to the queue's own waves
-    (vr_kernels.hip, grab_chunk).  A launch of fewer waves than queues has queues WITHOUT waves of
+    (vr_dev_rays.h, grab_chunk).  A launch of fewer waves than queues has queues WITHOUT waves of
     their own and must steal to the end; launches of a few, of about eight and of many waves, and
     the one-queue layout, all have to deliver every pixel the oracle delivers."""
     from volrend_amd import api

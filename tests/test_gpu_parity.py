@@ -316,7 +316,7 @@ def test_random_configurations_bit_exact(torch_cuda, fp_mode):
                           (1, 3, 1), (2, 3, 1), (3, 3, 1), (4, 3, 1), (6, 3, 1), (2, 4, 1)])
 def test_lookup_structure_geometries(torch_cuda, top_levels, brick_levels, blocked, fp_mode):
     """The N == 2 lookup structure (top grid of 2^G0 cells per axis + bricks of 2^BL entries per
-    axis + child words below, vr_kernels.hip) is a pure index: whatever its geometry, every
+    axis + child words below, vr_dev_layout.h) is a pure index: whatever its geometry, every
     sample must land in the leaf the reference's root descent finds (n3tree_query.hpp:13-48).
     Small geometries push a depth-7 tree through every branch: top leaves, brick leaves of all
     three depths, and the child-word walk below the bricks -- in both entry orders of the bricks
@@ -351,7 +351,7 @@ def test_lookup_structure_geometries(torch_cuda, top_levels, brick_levels, block
 
 @pytest.mark.parametrize("frame_group,super_block", [(1, 1), (2, 2), (3, 4), (0, 3), (4, 64)])
 def test_ray_order_is_scheduling_only(torch_cuda, frame_group, super_block):
-    """The ray-id order (frame groups x super-blocks of 8x8 pixel blocks, vr_kernels.hip locate())
+    """The ray-id order (frame groups x super-blocks of 8x8 pixel blocks, vr_dev_rays.h locate())
     decides which rays march together, never what they compute: a 5-pose batch of a ragged
     image -- whole frames and 3-way tile shards with odd tile sizes -- must equal the oracle
     under every order."""

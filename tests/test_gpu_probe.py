@@ -3,7 +3,7 @@
 Reference: the probe circle overlay of render_kernel (src/cuda/volrend.cu:100-134), the
 coefficient fetch retrieve_cursor_lumisphere_kernel (volrend.cu:175-191) and the pre-kernel
 launch of launch_renderer (volrend.cu:202-209).  Here: probe_overlay_kernel, probe_kernel and
-vr_probe_coeffs (volrend_amd/csrc/vr_kernels.hip).  Bar: RGBA8 and fp32 accumulators bit-equal.
+vr_probe_coeffs (volrend_amd/csrc/vr_render.hip).  Bar: RGBA8 and fp32 accumulators bit-equal.
 """
 import ctypes as C
 

@@ -1,6 +1,6 @@
 """-m gpu: the sample guard's status word reaches every product caller.
 
-vr_render* only enqueues, so a launch whose rays hit the guard (vr_kernels.hip: a wave that
+vr_render* only enqueues, so a launch whose rays hit the guard (vr_render.hip: a wave that
 marches `max_iter` rounds without retiring a ray cuts what is still marching) cannot fail the
 call: the sticky word of vr_tree_status carries it, and every render loop of the product checks
 it once its last launch has run -- volrend_headless (message + exit 1, the reference's

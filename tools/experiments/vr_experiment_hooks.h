@@ -1,7 +1,8 @@
-// vr_experiment_hooks.h -- timing experiments and profiling builds of vr_kernels.hip; nothing in
-// here is part of the product.  Included twice by vr_kernels.hip:
-//   VR_HOOKS_PART 1 (inside namespace vr::{anonymous}, before the kernels): the VR_EXP_* / TL_* /
-//                   TL3_* macros the kernels use.  In the product build (VR_ABLATE == 0,
+// vr_experiment_hooks.h -- timing experiments and profiling builds of the render path (vr_render.hip and
+// the vr_dev_*.h headers it includes); nothing in here is part of the product.  Included twice by
+// vr_render.hip:
+//   VR_HOOKS_PART 1 (inside namespace vr::{anonymous}, before the vr_dev_*.h headers): the VR_EXP_* /
+//                   TL_* / TL3_* macros the kernels use.  In the product build (VR_ABLATE == 0,
 //                   VR_TIMELINE == 0) every one of them expands to the plain expression / nothing.
 //   VR_HOOKS_PART 2 (global namespace, end of the file): the host-side reader of the
 //                   -DVR_TIMELINE=3 tallies.

@@ -9,7 +9,7 @@ bench.py priced every vector instruction at 4 SIMD cycles.  The chip's own numbe
          bfe / lshl_or / add_lshl / or3, conversions, fract, ldexp, rndne, mbcnt, alignbit, cndmask,
          v_fma_mix_f32, v_pk_*_f32, fp64, div_scale / fmas / fixup, ...
     7.6  v_rcp_f32 / v_exp_f32 (transcendental unit)
-This tool compiles vr_kernels.hip to ISA (hipcc -S, no GPU needed), takes the FAST flavour of a basis
+This tool compiles vr_render.hip to ISA (hipcc -S, no GPU needed), takes the FAST flavour of a basis
 size (default SH16, strict), and counts the three classes (a) in the march round -- the loop from its
 header to the first shade round, as tools/march_loop_isa.sh cuts it -- and (b) in the rest of the
 kernel (shade rounds, retire / refill).  bench.py weights (a) with the march rounds the instrumented
@@ -89,7 +89,7 @@ def main():
         asm = os.path.join(td, "k.s")
         flags = [f for f in vb.FLAGS if f not in ("-shared", "-fPIC")]
         subprocess.check_call([vb.HIPCC, *flags, "-I", os.path.join(ROOT, "include"), "-I", vb.CSRC, "-S",
-                               "--cuda-device-only", os.path.join(vb.CSRC, "vr_kernels.hip"), "-o", asm],
+                               "--cuda-device-only", os.path.join(vb.CSRC, "vr_render.hip"), "-o", asm],
                               stderr=subprocess.DEVNULL)
         text = open(asm).read().split("\n")
     kernels = {}

@@ -1,10 +1,12 @@
 #!/bin/bash
-# Prints VGPR/SGPR/scratch/occupancy per kernel of vr_kernels.hip (hipcc remark output).
+# Prints VGPR/SGPR/scratch/occupancy per kernel of vr_render.hip and vr_tree_kernels.hip (hipcc remark output).
 cd "$(dirname "$0")/.."
+for unit in vr_render vr_tree_kernels; do
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off \
   -fhip-fp32-correctly-rounded-divide-sqrt -fno-gpu-flush-denormals-to-zero -x hip \
-  -I include -I volrend_amd/csrc -c volrend_amd/csrc/vr_kernels.hip -o /tmp/vr_k.o \
-  -Rpass-analysis=kernel-resource-usage "$@" 2>&1 | python3 -c '
+  -I include -I volrend_amd/csrc -c volrend_amd/csrc/$unit.hip -o /tmp/vr_k.o \
+  -Rpass-analysis=kernel-resource-usage "$@" 2>&1
+done | python3 -c '
 import sys,re
 cur={}
 for line in sys.stdin:

@@ -56,7 +56,9 @@ GROUPS = {
     "sq4": "SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INSTS_SMEM SQ_WAIT_INST_LDS",
     # TA_* and TD_* counters abort rocprofv3 on this pool (measured twice in round 1): not offered
 }
-SOURCES = ["volrend_amd/csrc/vr_kernels.hip", "volrend_amd/csrc/vr_device_math.h",
+# (vr_tree_kernels.hip stays out: an edit to an upload kernel does not retire a render profile)
+SOURCES = ["volrend_amd/csrc/vr_render.hip", "volrend_amd/csrc/vr_dev_layout.h", "volrend_amd/csrc/vr_dev_shade.h",
+           "volrend_amd/csrc/vr_dev_query.h", "volrend_amd/csrc/vr_dev_rays.h", "volrend_amd/csrc/vr_device_math.h",
            "volrend_amd/csrc/vr_internal.h", "volrend_amd/csrc/vr_api.cpp", "include/volrend_hip.h",
            "volrend_amd/csrc/vr_host.h", "volrend_amd/csrc/vr_upload.cpp", "volrend_amd/csrc/vr_launch.cpp",
            "include/volrend/internal/hip_owners.hpp"]

@@ -1,5 +1,5 @@
 // vr_host.h -- shared by the host sources of libvolrend_hip.so (vr_api.cpp, vr_upload.cpp,
-// vr_launch.cpp).  Host only (not for vr_kernels.hip); nothing here is exported from the library.
+// vr_launch.cpp).  Host only (not for the .hip units); nothing here is exported from the library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,17 +40,17 @@ struct Tuning {
     int refill_min = 20;
     int drain_flush = 16;  // drain phase: partial round for a blocked ray when <= this many lanes march (0 = off;
                            // measured 4..64, profiles/r05_experiments.jsonl: one frame per launch -13 %, two / four -5 %)
-    int waves_per_cu = 0;   // 0: what the kernel flavour fits (vr_kernels.hip waves_per_cu<>)
+    int waves_per_cu = 0;   // 0: what the kernel flavour fits (vr_render.hip waves_per_cu<>)
     int frame_group = 0;   // poses per ray-order group (0 = all poses of the launch, 1 = frame-major)
     int super_block = 1;   // 8x8 blocks per super-block edge in the ray order
     int records_nt = -1;   // record stream non-temporal: -1 = by lookup-structure size, 0 / 1 = forced
     int xcd_queues = 1;
     int chunk_max = 4096;
     int raygen_waves = 0;  // waves per ray-generation workgroup: 16 / 4 / 1; 0 = by launch size (vr_render_batch)
-    int top_levels = 0;    // lookup structure built at upload (vr_kernels.hip); 0 = auto
+    int top_levels = 0;    // lookup structure built at upload (vr_dev_layout.h); 0 = auto
     int brick_levels = 3;
     int brick_blocked = -1;  // 8^3 bricks in 4 x 4 x 2 line blocks: -1 = when the lookup structure exceeds 128 MB, 0 / 1 = forced
-    int max_iter = 1 << 22;  // the sample guard (vr_kernels.hip); the one knob that is NOT scheduling-only:
+    int max_iter = 1 << 22;  // the sample guard (vr_render.hip); the one knob that is NOT scheduling-only:
                              // a launch that trips it reports through vr_tree_status (tests lower it)
 };
 Tuning default_tuning();  // the process defaults, for a tree being uploaded
@@ -74,7 +74,7 @@ struct LaunchSlot {
     DeviceBuffer rays;          // ray buffer, grown on demand (or up front by vr_reserve)
 };
 
-// The tree arrays in device layout (vr_kernels.hip), in the order of the touch bitmaps.
+// The tree arrays in device layout (vr_dev_layout.h), in the order of the touch bitmaps.
 enum TreeArray { kLeaves = 0, kNodes = 1, kTop = 2, kBricks = 3 };
 
 // What a tree is apart from its device memory: vr_tree_clone copies it in one assignment.
@@ -82,8 +82,8 @@ struct TreeShape {
     VrTreeDesc desc{};  // pointers cleared; scalars kept
     int32_t max_depth = 0;
     int leaf_stride_h = 0;
-    int top_levels = 0, brick_levels = 0, n_bricks = 0;  // lookup structure (N == 2), see vr_kernels.hip
-    int brick_blocked = 0;  // entry order of the bricks (vr_kernels.hip), fixed at upload
+    int top_levels = 0, brick_levels = 0, n_bricks = 0;  // lookup structure (N == 2), see vr_dev_layout.h
+    int brick_blocked = 0;  // entry order of the bricks (vr_dev_layout.h), fixed at upload
     uint64_t device_bytes = 0;
 };
 

@@ -1,5 +1,5 @@
-// vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp) and the
-// gfx950 kernels (vr_kernels.hip).  Not part of the public ABI.
+// vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp, vr_upload.cpp, vr_launch.cpp) and
+// the gfx950 kernels (vr_render.hip, vr_tree_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,9 +35,9 @@ struct FrameTable {
 // 12-float pose through a 48-byte H2D copy per frame, src/camera.cpp:67-75).
 struct KParams {
     // ---- tree (TreeSpec, data_spec.hpp:23-50), device layout ----
-    const uint32_t* nodes;    // one word per child slot (vr_kernels.hip)
+    const uint32_t* nodes;    // one word per child slot (vr_dev_layout.h)
     const uint16_t* leaves;   // padded coefficient records
-    const uint2* top;         // N == 2: 8^top_levels cells, see "lookup structure" in vr_kernels.hip
+    const uint2* top;         // N == 2: 8^top_levels cells, see "Lookup structure" in vr_dev_layout.h
     const uint32_t* bricks;   // N == 2: n_bricks * 8^brick_levels entries
     const float* extra;
     float offset[3];
@@ -88,7 +88,7 @@ struct KParams {
     int32_t n_queues;            // 1 or 8 (one ray-id range per XCD)
     int32_t chunk_max;           // largest ray-id chunk a wave takes at once (multiple of 64)
     const uint32_t* ray_buf;     // rays (written by raygen_kernel), blocked SoA; queue x's rays compacted to the
-    uint32_t* ray_buf_rw;        // front of its region (vr_kernels.hip "Ray queues")
+    uint32_t* ray_buf_rw;        // front of its region (vr_dev_rays.h "Ray queues")
     int32_t basis_words;         // basis_fn values a ray carries in registers (0 for RGBA)
     int32_t ray_tail_words;      // words of a ray record behind its 16-word head: the 3 words of the
                                  // view direction (ray_vdir) or the basis_words basis values
@@ -111,16 +111,14 @@ struct KParams {
     uint32_t* touch[4];
 };
 
-// vr_kernels.hip
+// vr_render.hip: the kernels of a launch
 hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream);
 hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
                          hipStream_t stream);
-hipError_t launch_assemble(uint8_t* frame, int64_t pitch, const uint8_t* gathered, int width,
-                           int height, int tile_w, int tile_h, int world, int n_frames,
-                           int64_t out_stride, int64_t rank_stride, int64_t in_stride,
-                           hipStream_t stream);
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
                         hipStream_t stream);
+
+// vr_tree_kernels.hip: upload, tile gather, touch meter
 // upload-time re-layout of the reference arrays into the device layout
 int leaf_stride_halfs(int data_dim);
 hipError_t launch_relayout(const int32_t* child, const uint16_t* data, const int32_t* perm,
@@ -130,12 +128,17 @@ hipError_t launch_relayout(const int32_t* child, const uint16_t* data, const int
 hipError_t launch_decode_quant(const uint16_t* colors, const uint16_t* map, const uint16_t* sigma,
                                const uint16_t* retained, uint16_t* data, int64_t n_slots,
                                int n_quant, int n_ret, int data_dim, hipStream_t stream);
-// number of set bits of a bitmap of n_words 32-bit words, added to *out
-hipError_t launch_popcount(const uint32_t* words, uint64_t n_words, unsigned long long* out,
-                           hipStream_t stream);
 // N == 2 lookup structure (top grid + bricks), built from the re-laid-out node words
 hipError_t launch_build_lookup(const uint32_t* nodes, const int32_t* brick_root, int n_bricks,
                                uint2* top, uint32_t* bricks, int top_levels, int brick_levels,
                                int brick_blocked, uint32_t* error_flag, hipStream_t stream);
+// number of set bits of a bitmap of n_words 32-bit words, added to *out
+hipError_t launch_popcount(const uint32_t* words, uint64_t n_words, unsigned long long* out,
+                           hipStream_t stream);
+// de-interleave of `world` gathered COMPACT tile buffers into frames
+hipError_t launch_assemble(uint8_t* frame, int64_t pitch, const uint8_t* gathered, int width,
+                           int height, int tile_w, int tile_h, int world, int n_frames,
+                           int64_t out_stride, int64_t rank_stride, int64_t in_stride,
+                           hipStream_t stream);
 
 }  // namespace vr

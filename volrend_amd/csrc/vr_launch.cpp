@@ -40,7 +40,7 @@ bool ray_carries_vdir(const VrTreeOpaque* t) {
 int ray_tail_words_of(const VrTreeOpaque* t) { return ray_carries_vdir(t) ? 3 : basis_words_of(t); }
 
 size_t ray_buffer_bytes(uint32_t total_rays, int tail_words) {
-    // the ray queues own whole groups of 16 blocks of 64 rays (vr_kernels.hip "Ray queues")
+    // the ray queues own whole groups of 16 blocks of 64 rays (vr_dev_rays.h "Ray queues")
     const size_t slots = (((size_t)total_rays / 64 + 15) / 16) * 16 * 64;
     return slots * (16 + (size_t)tail_words) * sizeof(uint32_t);  // kRayWords + tail
 }
@@ -215,7 +215,7 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     fill_tree_params(k, t);  // (under the mutex: vr_touch_enable / vr_touch_count (re)allocate the bitmaps)
     const Tuning tn = t->tn;  // (a copy: the mutex is dropped once below, while a slot grows)
     // lookup structure (top + bricks) beyond 4x the aggregate L2 (8 x 4 MiB on MI355X): the record
-    // stream would keep evicting it -- see the DMA loads in vr_kernels.hip
+    // stream would keep evicting it -- see the DMA loads in vr_render.hip
     k.records_nt = tn.records_nt >= 0 ? tn.records_nt
                                       : (t->arrays[kTop].bytes() + t->arrays[kBricks].bytes() > (128ull << 20));
     k.march_max = tn.march_max;
@@ -312,7 +312,7 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     }
     // waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
     // two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
-    // 4 waves find room there much earlier (vr_kernels.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
+    // 4 waves find room there much earlier (vr_render.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
     // two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
     // 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
     const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);

@@ -601,7 +601,7 @@ int upload_body(const VrTreeDesc* d, const VrQuantDesc* q, vr_tree_t* out) {
                                 t->arrays[kLeaves].get<uint16_t>(), (int64_t)n_slots, N3, d->data_dim,
                                 t->leaf_stride_h, nullptr);
     t->device_bytes = child_sz + leaves_sz + sizeof(uint32_t);
-    // lookup structure: top grid + bricks (vr_kernels.hip), built from the node words
+    // lookup structure: top grid + bricks (vr_dev_layout.h), built from the node words
     DeviceBuffer d_roots;
     if (e == hipSuccess && G0 > 0) {
         const size_t top_sz = ((size_t)1 << (3 * G0)) * sizeof(uint2);
