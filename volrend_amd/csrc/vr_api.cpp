@@ -203,11 +203,11 @@ int vr_tree_set_tuning(vr_tree_t t, const char* key, int value) {
     return VR_OK;
 }
 
-int vr_sched_stats(vr_tree_t t, uint64_t out[8], int reset) {
+int vr_sched_stats(vr_tree_t t, uint64_t out[vr::kSchedStats], int reset) {
     if (!t || !out) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
     DeviceGuard guard(t->device);
-    HIP_TRY(hipMemcpy(out, t->sched_stats.get(), 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    if (reset) HIP_TRY(hipMemset(t->sched_stats.get(), 0, 8 * sizeof(uint64_t)));
+    HIP_TRY(hipMemcpy(out, t->sched_stats.get(), vr::kSchedStats * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(t->sched_stats.get(), 0, vr::kSchedStats * sizeof(uint64_t)));
     return VR_OK;
 }
 

@@ -10,9 +10,7 @@ namespace {
 
 constexpr int kWave = 64;
 
-enum { BASIS_RGBA = -1, BASIS_1 = 1, BASIS_4 = 4, BASIS_9 = 9, BASIS_16 = 16, BASIS_25 = 25 };
-
-// Kernel flavours.  FAST is the production path: N == 2 integer descent, SH/RGBA
+// Kernel flavours (the basis flavours BASIS_*: vr_internal.h).  FAST is the production path: N == 2 integer descent, SH/RGBA
 // only, no instrumentation, zero scratch.  FULL adds the SG/ASG lobe code and
 // the optional access counters (VrFrame.counters); GENERIC additionally swaps in
 // the literal float descent for N != 2 (or trees deeper than 24 levels).

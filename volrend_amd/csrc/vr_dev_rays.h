@@ -26,6 +26,10 @@ __device__ __forceinline__ uint32_t lane_id_now() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
 }
+// Number of set bits of a wave mask below this lane: the lane's rank among the lanes of the mask.
+__device__ __forceinline__ uint32_t lane_rank(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
 
 struct Ray {
     float cen[3], dir[3], invdir[3];
@@ -97,11 +101,16 @@ __device__ __forceinline__ PixelRef locate(const KParams& p, uint32_t id) {
     return r;
 }
 
+// The RGBA8 of frame pixel (x, y) = pixel (lx, ly) of the rank's k-th tile.
+__device__ __forceinline__ uint8_t* pixel_address(const KParams& p, const FrameDesc& fd, int k, int lx,
+                                                  int ly, int x, int y) {
+    if (p.layout == VR_LAYOUT_COMPACT)
+        return fd.rgba + ((int64_t)k * p.tile_w * p.tile_h + (int64_t)ly * p.tile_w + lx) * 4;
+    return fd.rgba + (int64_t)y * p.pitch + (int64_t)x * 4;
+}
 __device__ __forceinline__ uint8_t* pixel_ptr(const KParams& p, const FrameDesc& fd,
                                               const PixelRef& r) {
-    if (p.layout == VR_LAYOUT_COMPACT)
-        return fd.rgba + ((int64_t)r.k * p.tile_w * p.tile_h + (int64_t)r.ly * p.tile_w + r.lx) * 4;
-    return fd.rgba + (int64_t)r.y * p.pitch + (int64_t)r.x * 4;
+    return pixel_address(p, fd, r.k, r.lx, r.ly, r.x, r.y);
 }
 
 // Ray generation + trace_ray prologue up to the ray/box test
@@ -232,19 +241,23 @@ __device__ __forceinline__ void finish_ray(const KParams& p, Ray& ray, const Ray
     }
     if (COUNT && p.frames[frame].counters) {
         const FrameDesc& fd = p.frames[frame];
-        // VrCounters: rays, rays_hit_box, samples, child_reads, hit_samples, alg_bytes,
-        // early_stops.  alg_bytes per SURVEY.md 8(d):
+        // alg_bytes per SURVEY.md 8(d):
         //   sum over samples (4*L + 2 + hit*2*(data_dim-1)) + 4 per pixel
         const unsigned long long bytes = 4ull * rc.child_reads + 2ull * rc.samples +
                                          2ull * (unsigned long long)(p.data_dim - 1) * rc.hits +
                                          4ull;
-        if (p.N > 0) atomicAdd(&fd.counters[0], 1ull);
-        atomicAdd(&fd.counters[1], ray.entered ? 1ull : 0ull);
-        atomicAdd(&fd.counters[2], (unsigned long long)rc.samples);
-        atomicAdd(&fd.counters[3], (unsigned long long)rc.child_reads);
-        atomicAdd(&fd.counters[4], (unsigned long long)rc.hits);
-        atomicAdd(&fd.counters[5], bytes);
-        atomicAdd(&fd.counters[6], (unsigned long long)rc.early);
+        // (the struct is reached through the frame table at every add, not through a local copy of
+        // the pointer: that would change the code of every instrumented flavour)
+        auto tally = [](uint64_t& word, unsigned long long v) {
+            atomicAdd(reinterpret_cast<unsigned long long*>(&word), v);
+        };
+        if (p.N > 0) tally(fd.counters->rays, 1ull);
+        tally(fd.counters->rays_hit_box, ray.entered ? 1ull : 0ull);
+        tally(fd.counters->samples, rc.samples);
+        tally(fd.counters->child_reads, rc.child_reads);
+        tally(fd.counters->hit_samples, rc.hits);
+        tally(fd.counters->alg_bytes, bytes);
+        tally(fd.counters->early_stops, rc.early);
     }
     if (p.any_accum) {  // launch-uniform: the frame table is only consulted when some frame asks
         float* accum = p.frames[frame].accum;
@@ -272,13 +285,8 @@ __device__ __forceinline__ void finish_ray(const KParams& p, Ray& ray, const Ray
 }
 
 // ---------------------------------------------------------------------------
-// Ray buffer (global memory, written by raygen_kernel; blocked structure of arrays, see
-// ray_slot), the words of a ray:
-//   0-2 cen, 3-5 dir, 6-8 invdir, 9 t, 10 tmax, 11 delta_scale, 12 xy, 13-14 the 64-bit
-//   address of the pixel's RGBA8 (so that retiring a ray needs no frame-table lookup),
-//   15 frame, 16.. basis_fn[0..nb)
+// Ray buffer (global memory, written by raygen_kernel; the words of a ray: kRay*, vr_internal.h).
 // ---------------------------------------------------------------------------
-constexpr int kRayWords = 16;
 // Blocked structure of arrays: the rays are stored in blocks of 64, word k of the 64 rays of a
 // block contiguous (256 bytes), the words of a block back to back.  So word k of ray r lives at
 //   buf + ((r >> 6) * words_per_ray + k) * 64 + (r & 63)
@@ -290,11 +298,11 @@ __device__ __forceinline__ T* ray_slot(T* buf, int words_per_ray, uint32_t r) {
     return buf + ((size_t)(r >> 6) * (uint32_t)words_per_ray * 64u + (r & 63u));
 }
 __device__ __forceinline__ uint32_t ray_word(const uint32_t* slot, int k) { return slot[k * 64]; }
-constexpr int kQueueStride = 16;  // words between queue heads (one 64-byte line each: head, count)
+__device__ __forceinline__ uint32_t& ray_word(uint32_t* slot, int k) { return slot[k * 64]; }
 constexpr uint32_t kStealMin = 8192;  // rays a foreign queue must still hold to be worth a steal (or an eighth of its length)
 
 // Ray queues.  The 8x8 pixel blocks of a launch (ray-id order: locate()) are cut into n_queues (1 or
-// 8) contiguous runs -- screen regions of the batch -- at multiples of 16 blocks; queue x owns the ray
+// kMaxQueues) contiguous runs -- screen regions of the batch -- at multiples of 16 blocks; queue x owns the ray
 // slots of its blocks, [first_block(x) * 64, first_block(x + 1) * 64), and two words of one 64-byte
 // line: head (rays handed out, render_kernel) and count (rays stored, raygen_kernel).  Ray generation
 // compacts the rays that enter the volume to the front of their queue's region (one atomic on the
@@ -302,6 +310,11 @@ constexpr uint32_t kStealMin = 8192;  // rays a foreign queue must still hold to
 // what lets small launches generate their rays in workgroups of one or four waves: raygen_kernel).
 __device__ __forceinline__ uint32_t queue_first_block(uint32_t n_groups16, uint32_t x, uint32_t sh) {
     return (uint32_t)(((uint64_t)n_groups16 * x) >> sh) << 4;
+}
+// The split of this launch: sh = log2(n_queues), n16 = its groups of 16 blocks.
+__device__ __forceinline__ void queue_split(const KParams& p, uint32_t& sh, uint32_t& n16) {
+    sh = (uint32_t)p.n_queues == (uint32_t)kMaxQueues ? (uint32_t)kMaxQueuesShift : 0u;
+    n16 = ray_groups16(p.total_rays);
 }
 
 // A wave's next private range [lo, hi) of ray slots, or lo == hi when there is nothing left for it.
@@ -323,15 +336,16 @@ __device__ __forceinline__ uint32_t queue_first_block(uint32_t n_groups16, uint3
 __device__ __forceinline__ void grab_chunk(const KParams& p, int lane, uint32_t& lo, uint32_t& hi) {
     lo = hi = 0;
     if (lane == 0) {
-        const uint32_t nq = (uint32_t)p.n_queues;  // 1 or 8
-        const uint32_t sh = nq == 8u ? 3u : 0u;
-        const uint32_t n16 = ((p.total_rays >> 6) + 15u) >> 4;
+        const uint32_t nq = (uint32_t)p.n_queues;  // 1 or kMaxQueues
+        uint32_t sh, n16;
+        queue_split(p, sh, n16);
         const uint32_t mine = blockIdx.x & (nq - 1u);
         const uint32_t waves_per_q = (gridDim.x + nq - 1u) >> sh;
         for (uint32_t a = 0; a < nq; ++a) {
             const uint32_t x = (mine + a) & (nq - 1u);
-            uint32_t* head = p.queue_head + x * kQueueStride;
-            const uint32_t len = head[1];  // rays of this queue (written by raygen_kernel, constant here)
+            uint32_t* const q = p.queue_head + x * kQueueStride;
+            uint32_t* const head = q + kQueueHead;
+            const uint32_t len = q[kQueueCount];  // rays of this queue (written by raygen_kernel, constant here)
             const uint32_t seen = __hip_atomic_load(head, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (seen >= len) continue;
             if (a != 0u && gridDim.x >= nq &&

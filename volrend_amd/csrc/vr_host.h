@@ -56,7 +56,6 @@ struct Tuning {
 Tuning default_tuning();  // the process defaults, for a tree being uploaded
 
 constexpr unsigned kLaunchSlots = 8;
-constexpr unsigned kSlotWords = 160;  // [16 + 16*x] queue x (x < 8): rays handed out, rays stored
 
 // Per-launch scratch that a kernel reads while it runs: frame table, queue heads, ray count,
 // ray buffer, probe coefficients.  `done` is recorded on the launch's stream behind its last
@@ -90,12 +89,12 @@ struct TreeShape {
 struct VrTreeOpaque : TreeShape {
     int device = 0;
     DeviceBuffer arrays[4];      // TreeArray: leaves (uint16_t), nodes (uint32_t), top (uint2), bricks (uint32_t)
-    DeviceBuffer extra, status, sched_stats;  // float, uint32_t, 8 x u64 (vr_sched_stats)
+    DeviceBuffer extra, status, sched_stats;  // float, uint32_t, vr::kSchedStats x u64 (vr_sched_stats)
     DeviceBuffer touch[4];       // distinct-line bitmaps of the arrays (vr_touch_enable)
     DeviceBuffer touch_out;      // 4 x u64
     DeviceBuffer probe_buf;      // kLaunchSlots x data_dim floats: the lumisphere at opt.probe
     DeviceBuffer slot_frames;    // kLaunchSlots x kMaxBatch vr::FrameDesc
-    DeviceBuffer slot_heads;     // kLaunchSlots x kSlotWords uint32_t
+    DeviceBuffer slot_heads;     // kLaunchSlots x vr::kSlotWords uint32_t
     LaunchSlot slots[kLaunchSlots];
     unsigned launch_seq = 0;
     std::mutex launch_mutex;  // slot bookkeeping + enqueue order of one launch; guards `tn`

@@ -13,6 +13,83 @@ constexpr int kTableChunk = 48;  // frames per prepare_launch_kernel call (4 KB 
 constexpr int kTouchLeafShift = 7;  // log2 of the bytes one bit of the records' distinct-line bitmap stands for
                                     // (layout studies patch it: 6 = one bit per 64-byte SH9 record slot)
 
+// ---------------------------------------------------------------------------
+// The launch contract: what the host sizes and the kernels of a launch write and read.
+// ---------------------------------------------------------------------------
+// Basis flavour of a tree: the render_kernel<BASIS> instantiation that shades it, and with it what
+// a ray carries.  The reference's switch only knows 25/16/9/4 (rt_core.cuh:132-160); every other
+// basis size reads the first coefficient of each channel.
+enum { BASIS_RGBA = -1, BASIS_1 = 1, BASIS_4 = 4, BASIS_9 = 9, BASIS_16 = 16, BASIS_25 = 25 };
+__host__ __device__ inline int basis_flavour(int format, int basis_dim) {
+    if (format == VR_FORMAT_RGBA || basis_dim < 0) return BASIS_RGBA;
+    switch (basis_dim) {
+        case 25: return BASIS_25;
+        case 16: return BASIS_16;
+        case 9: return BASIS_9;
+        case 4: return BASIS_4;
+        default: return BASIS_1;
+    }
+}
+// basis_fn values the kernel flavour reads per ray (KParams.basis_words)
+__host__ __device__ inline int basis_words(int flavour) { return flavour == BASIS_RGBA ? 0 : flavour; }
+// SH trees with a basis size the kernel knows: the ray record carries the view direction (3 words)
+// and the lane that takes the ray evaluates the basis; everything else carries the basis values
+__host__ __device__ inline bool ray_vdir(int format, int flavour) {
+    return format == VR_FORMAT_SH && basis_words(flavour) > 3;
+}
+__host__ __device__ inline int ray_tail_words(int format, int flavour) {
+    return ray_vdir(format, flavour) ? 3 : basis_words(flavour);
+}
+
+// Ray record: the words of a ray in the ray buffer (written by raygen_kernel, read by render_kernel;
+// blocked structure of arrays, vr_dev_rays.h ray_slot).  The pixel travels as the 64-bit address of
+// its RGBA8, so that retiring a ray needs no frame-table lookup.
+enum {
+    kRayCen = 0,      // 3 words
+    kRayDir = 3,      // 3 words
+    kRayInvDir = 6,   // 3 words
+    kRayT = 9,
+    kRayTmax = 10,
+    kRayDeltaScale = 11,
+    kRayXy = 12,      // x | y << 16
+    kRayPixelLo = 13,
+    kRayPixelHi = 14,
+    kRayFrame = 15,
+    kRayWords = 16,   // the head; behind it ray_tail_words(): the view direction or basis_fn[0..nb)
+    kRayTail = kRayWords,
+};
+// The ray queues own whole groups of 16 blocks of 64 rays ("Ray queues", vr_dev_rays.h): the
+// number of such groups of a launch, and the ray slots its buffer holds.
+__host__ __device__ inline uint32_t ray_groups16(uint32_t total_rays) { return ((total_rays >> 6) + 15u) >> 4; }
+__host__ __device__ inline size_t ray_slots(uint32_t total_rays) { return (size_t)ray_groups16(total_rays) * 16 * 64; }
+
+// Ray queues of a launch slot (device words, KParams.queue_head points at queue 0): queue x sits
+// kQueueStride words behind queue x - 1 -- a 64-byte line each -- and uses two of them.
+constexpr int kMaxQueues = 8;        // one per XCD (KParams.n_queues is 1 or kMaxQueues)
+constexpr int kMaxQueuesShift = 3;
+constexpr int kQueueStride = 16;
+constexpr int kQueueHead = 0;        // rays handed out (render_kernel)
+constexpr int kQueueCount = 1;       // rays stored (raygen_kernel)
+constexpr int kSlotHeaderWords = 16; // the line in front of a slot's queues
+constexpr int kSlotWords = 160;      // allocated per launch slot
+static_assert(kMaxQueues == 1 << kMaxQueuesShift, "queues are picked with shifts and masks");
+static_assert(kSlotWords >= kSlotHeaderWords + kMaxQueues * kQueueStride, "a slot holds its header and every queue");
+
+// Scheduling tallies of the instrumented flavours: the words of KParams.sched_stats, in the order
+// vr_sched_stats documents them.
+enum {
+    kStatMarchRounds = 0,
+    kStatMarchLanes,
+    kStatShadeRounds,
+    kStatShadeLanes,
+    kStatDistinctLeaves,
+    kStatRetireRounds,
+    kStatRetiredRays,
+    kStatIterations,
+    kSchedStats
+};
+static_assert(kSchedStats == 8, "vr_sched_stats(out[8]) is public ABI");
+
 // Per-frame part of a launch: pose and buffers.  Lives in device memory (one
 // small table per launch slot) because lanes of one wave may hold rays of
 // different frames.
@@ -21,7 +98,7 @@ struct FrameDesc {
     uint8_t* rgba;
     float* accum;
     const float* depth;
-    unsigned long long* counters;  // optional VrCounters (7 x u64)
+    VrCounters* counters;  // optional
 };
 
 struct FrameTable {
@@ -84,13 +161,13 @@ struct KParams {
     int64_t n_wave_blocks;       // per frame: n_local_tiles * wblocks_per_tile
     uint32_t total_rays;         // n_frames * n_wave_blocks * 64
     // ---- persistent scheduling ----
-    uint32_t* queue_head;        // 8 x (head, count) word pairs, 16 words apart, reset by prepare_launch_kernel
-    int32_t n_queues;            // 1 or 8 (one ray-id range per XCD)
+    uint32_t* queue_head;        // kMaxQueues x (head, count), kQueueStride words apart, reset by prepare_launch_kernel
+    int32_t n_queues;            // 1 or kMaxQueues (one ray-id range per XCD)
     int32_t chunk_max;           // largest ray-id chunk a wave takes at once (multiple of 64)
     const uint32_t* ray_buf;     // rays (written by raygen_kernel), blocked SoA; queue x's rays compacted to the
     uint32_t* ray_buf_rw;        // front of its region (vr_dev_rays.h "Ray queues")
     int32_t basis_words;         // basis_fn values a ray carries in registers (0 for RGBA)
-    int32_t ray_tail_words;      // words of a ray record behind its 16-word head: the 3 words of the
+    int32_t ray_tail_words;      // words of a ray record behind its kRayWords head: the 3 words of the
                                  // view direction (ray_vdir) or the basis_words basis values
     int32_t ray_vdir;            // SH trees: the record carries the view direction, the basis is
                                  // evaluated when a lane takes the ray
@@ -105,7 +182,7 @@ struct KParams {
     int32_t frame_group;         // ray-id order: frames per group (block major, frame minor inside)
     int32_t super_block;         // ray-id order: blocks of a tile visited in SxS super-blocks
     uint32_t* status;            // device word: bit0 = iteration cap hit
-    unsigned long long* sched_stats;  // 8 x u64 scheduling tallies (instrumented flavours)
+    unsigned long long* sched_stats;  // kSchedStats scheduling tallies (instrumented flavours)
     // distinct-line meter (instrumented flavours, vr_touch_enable): one bit per 128-byte line of
     // leaves / nodes / top / bricks, set by every access; NULL when off
     uint32_t* touch[4];

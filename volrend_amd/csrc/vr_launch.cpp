@@ -24,25 +24,13 @@ float host_norm3(const float* d, int fma) {
     return std::sqrt(s);
 }
 
-// basis words kept per ray in the ray buffer: what the kernel flavour for this basis_dim reads
-int basis_words_of(const VrTreeOpaque* t) {
-    const int bd = t->desc.basis_dim;
-    if (t->desc.format == VR_FORMAT_RGBA || bd < 0) return 0;
-    return (bd == 4 || bd == 9 || bd == 16 || bd == 25) ? bd : 1;
+// what a ray of this tree carries behind the head of its record (vr_internal.h)
+int ray_tail_words_of(const VrTreeOpaque* t) {
+    return vr::ray_tail_words(t->desc.format, vr::basis_flavour(t->desc.format, t->desc.basis_dim));
 }
-
-// SH trees with a basis size the kernel knows: the ray record carries the view direction (3 words)
-// and the lane that takes the ray evaluates the basis; everything else carries the basis values
-bool ray_carries_vdir(const VrTreeOpaque* t) {
-    const int bw = basis_words_of(t);
-    return t->desc.format == VR_FORMAT_SH && bw > 3;
-}
-int ray_tail_words_of(const VrTreeOpaque* t) { return ray_carries_vdir(t) ? 3 : basis_words_of(t); }
 
 size_t ray_buffer_bytes(uint32_t total_rays, int tail_words) {
-    // the ray queues own whole groups of 16 blocks of 64 rays (vr_dev_rays.h "Ray queues")
-    const size_t slots = (((size_t)total_rays / 64 + 15) / 16) * 16 * 64;
-    return slots * (16 + (size_t)tail_words) * sizeof(uint32_t);  // kRayWords + tail
+    return vr::ray_slots(total_rays) * (vr::kRayWords + (size_t)tail_words) * sizeof(uint32_t);
 }
 
 // Replaces the ray buffer of a slot the caller owns (it holds the launch mutex, or has marked the
@@ -125,10 +113,12 @@ int launch_geometry(int width, int height, int tile_w, int tile_h, int rank, int
     return VR_OK;
 }
 
-extern "C" {
+namespace {  // the steps of vr_render_batch
 
-int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
-                    const VrFrame* frames, void* stream) {
+// One launch shares everything but the pose and the buffers: checks the batch against its first
+// frame and leaves in `k` what the checks compute -- the launch geometry, pitch, instrumented, any_accum.
+int validate_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                   const VrFrame* frames, vr::KParams& k) {
     if (!t || !cams || !opt || !frames) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (n_frames < 1 || n_frames > VR_MAX_BATCH)
         return fail(VR_ERR_INVALID_ARGUMENT, "n_frames=%d outside [1,%d]", n_frames, VR_MAX_BATCH);
@@ -141,16 +131,12 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     const int world = f->world < 1 ? 1 : f->world;
     if (f->rank < 0 || f->rank >= world)
         return fail(VR_ERR_INVALID_ARGUMENT, "rank %d outside world %d", f->rank, world);
-    vr::KParams k;
-    memset(&k, 0, sizeof(k));
     if (int rc = launch_geometry(cam->width, cam->height, f->tile_w, f->tile_h, f->rank, world, n_frames, k))
         return rc;
-    {
-        const int64_t pitch = f->pitch ? f->pitch : (int64_t)cam->width * 4;
-        if (pitch < (int64_t)cam->width * 4 || pitch * cam->height >= (1ll << 32))
-            return fail(VR_ERR_INVALID_ARGUMENT, "pitch %lld unusable for a %dx%d frame",
-                        (long long)pitch, cam->width, cam->height);
-    }
+    k.pitch = f->pitch ? f->pitch : (int64_t)cam->width * 4;
+    if (k.pitch < (int64_t)cam->width * 4 || k.pitch * cam->height >= (1ll << 32))
+        return fail(VR_ERR_INVALID_ARGUMENT, "pitch %lld unusable for a %dx%d frame",
+                    (long long)k.pitch, cam->width, cam->height);
     if (!(cam->fx != 0.f) || !(cam->fy != 0.f))
         return fail(VR_ERR_INVALID_ARGUMENT, "focal length must be non-zero");
 
@@ -176,8 +162,15 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     if (!(opt->step_size > 0.f))
         return fail(VR_ERR_INVALID_ARGUMENT, "step_size must be positive (got %g)",
                     (double)opt->step_size);
+    k.n_frames = n_frames;
+    k.instrumented = instrumented ? 1 : 0;
+    k.any_accum = any_accum ? 1 : 0;
+    return VR_OK;
+}
 
-    DeviceGuard device_guard(t->device);
+// The part of KParams that comes from the caller: intrinsics, options, the launch-uniform half of
+// the view-direction rotation, and how the frames are written (`f` = the first frame).
+void fill_caller_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptions* opt, const VrFrame* f) {
     k.width = cam->width;
     k.height = cam->height;
     k.fx = cam->fx;
@@ -204,16 +197,13 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
         k.rot_cos = cosf(angle);
         k.rot_sin = sinf(angle);
     }
-    k.n_frames = n_frames;
-    k.pitch = f->pitch ? f->pitch : (int64_t)cam->width * 4;
     k.offscreen = f->offscreen != 0;
     k.layout = f->layout;
-    k.instrumented = instrumented ? 1 : 0;
-    k.any_accum = any_accum ? 1 : 0;
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    std::unique_lock<std::mutex> guard(t->launch_mutex);
-    fill_tree_params(k, t);  // (under the mutex: vr_touch_enable / vr_touch_count (re)allocate the bitmaps)
-    const Tuning tn = t->tn;  // (a copy: the mutex is dropped once below, while a slot grows)
+}
+
+// The part of KParams that comes from the tree's knobs and from what its basis flavour makes a ray
+// carry.  Under the launch mutex, from the copy of the knobs the launch goes by.
+void fill_tuning_params(vr::KParams& k, const VrTreeOpaque* t, const Tuning& tn) {
     // lookup structure (top + bricks) beyond 4x the aggregate L2 (8 x 4 MiB on MI355X): the record
     // stream would keep evicting it -- see the DMA loads in vr_render.hip
     k.records_nt = tn.records_nt >= 0 ? tn.records_nt
@@ -222,11 +212,23 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     k.refill_min = tn.refill_min;
     k.drain_flush = tn.drain_flush;
     k.max_iter = tn.max_iter;
-    k.frame_group = tn.frame_group < 1 || tn.frame_group > n_frames ? n_frames : tn.frame_group;
+    k.frame_group = tn.frame_group < 1 || tn.frame_group > k.n_frames ? k.n_frames : tn.frame_group;
     k.super_block = tn.super_block;
-    // launch slot: per-launch scratch in device memory (ring, see LaunchSlot)
-    const size_t need = ray_buffer_bytes(k.total_rays, ray_tail_words_of(t));
-    unsigned slot = kLaunchSlots;
+    k.n_queues = tn.xcd_queues ? vr::kMaxQueues : 1;
+    k.chunk_max = tn.chunk_max;
+    const int flavour = vr::basis_flavour(t->desc.format, t->desc.basis_dim);
+    k.basis_words = vr::basis_words(flavour);
+    k.ray_tail_words = vr::ray_tail_words(t->desc.format, flavour);
+    k.ray_vdir = vr::ray_vdir(t->desc.format, flavour) ? 1 : 0;
+}
+
+// Launch slot: per-launch scratch in device memory (ring, see LaunchSlot).  Picks the slot of this
+// launch, points `k` at its scratch and makes its ray buffer large enough.  `guard` holds the
+// launch mutex on entry and on return.
+int acquire_slot(VrTreeOpaque* t, std::unique_lock<std::mutex>& guard, hipStream_t hs, vr::KParams& k,
+                 unsigned& slot) {
+    const size_t need = ray_buffer_bytes(k.total_rays, k.ray_tail_words);
+    slot = kLaunchSlots;
     for (int want_fit = 1; want_fit >= 0 && slot == kLaunchSlots; --want_fit) {
         for (int pass = 0; pass < 2 && slot == kLaunchSlots; ++pass)
             for (unsigned i = 0; i < kLaunchSlots; ++i) {
@@ -250,12 +252,8 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     t->launch_seq++;
     LaunchSlot& ls = t->slots[slot];
     k.frames = t->slot_frames.get<vr::FrameDesc>() + (size_t)slot * vr::kMaxBatch;
-    k.queue_head = t->slot_heads.get<uint32_t>() + kSlotWords * slot + 16;
-    k.n_queues = tn.xcd_queues ? 8 : 1;
-    k.chunk_max = tn.chunk_max;
-    k.basis_words = basis_words_of(t);
-    k.ray_tail_words = ray_tail_words_of(t);
-    k.ray_vdir = ray_carries_vdir(t) ? 1 : 0;
+    k.queue_head = t->slot_heads.get<uint32_t>() + vr::kSlotWords * slot + vr::kSlotHeaderWords;
+    k.probe_coeffs = t->probe_buf.get<float>() + (size_t)slot * (size_t)t->desc.data_dim;
     if (ls.rays.bytes() < need) {
         // First use of the slot, or a larger batch than any before: (re)allocate.  This is the
         // one place where an enqueue-only call may block -- on THIS slot's previous launch
@@ -268,12 +266,19 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
         const hipError_t ge = replace_ray_buffer(ls, need);
         guard.lock();
         ls.growing = false;
-        fill_tree_params(k, t);  // (the mutex was dropped: see above)
+        fill_tree_params(k, t);  // (the mutex was dropped: vr_touch_enable / vr_touch_count (re)allocate the bitmaps)
         if (ge != hipSuccess)
             return fail(hip_code(ge), "ray buffer of %zu bytes: %s", need, hipGetErrorString(ge));
     }
     k.ray_buf_rw = ls.rays.get<uint32_t>();
     k.ray_buf = k.ray_buf_rw;
+    return VR_OK;
+}
+
+// Puts the kernels of the launch into the stream, behind the slot's previous launch: the probe
+// pre-kernel, the frame table, ray generation + render.
+int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, const Tuning& tn,
+                   const VrCamera* cams, const VrRenderOptions* opt, const VrFrame* frames, hipStream_t hs) {
     // whoever used this slot last (any stream) must have finished before its scratch is rewritten
     if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
     // From here on kernels of this launch may be in the stream: whatever happens below (a later
@@ -291,22 +296,21 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
             }
         }
     } seal{ls, hs};
-    k.probe_coeffs = t->probe_buf.get<float>() + (size_t)slot * (size_t)t->desc.data_dim;
     if (k.enable_probe)  // launch_renderer's pre-kernel, volrend.cu:202-209
         HIP_TRY(vr::launch_probe(k, opt->probe, const_cast<float*>(k.probe_coeffs), hs));
 
     // frame table -> device memory, kTableChunk poses per (tiny) kernel
-    for (int first = 0; first < n_frames; first += vr::kTableChunk) {
+    for (int first = 0; first < k.n_frames; first += vr::kTableChunk) {
         vr::FrameTable tbl;
         memset(&tbl, 0, sizeof(tbl));
         tbl.first = first;
-        tbl.n = n_frames - first < vr::kTableChunk ? n_frames - first : vr::kTableChunk;
+        tbl.n = k.n_frames - first < vr::kTableChunk ? k.n_frames - first : vr::kTableChunk;
         for (int i = 0; i < tbl.n; ++i) {
             memcpy(tbl.f[i].xf, cams[first + i].transform, sizeof(tbl.f[i].xf));
             tbl.f[i].rgba = static_cast<uint8_t*>(frames[first + i].rgba);
             tbl.f[i].accum = frames[first + i].accum;
             tbl.f[i].depth = frames[first + i].depth;
-            tbl.f[i].counters = reinterpret_cast<unsigned long long*>(frames[first + i].counters);
+            tbl.f[i].counters = reinterpret_cast<VrCounters*>(frames[first + i].counters);
         }
         HIP_TRY(vr::launch_prepare(k, tbl, hs));
     }
@@ -315,9 +319,30 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     // 4 waves find room there much earlier (vr_render.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
     // two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
     // 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
-    const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
-    HIP_TRY(vr::launch_render(k, f->fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
+    const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (k.n_frames <= 2 ? 4 : 16);
+    HIP_TRY(vr::launch_render(k, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
     return VR_OK;  // (`seal` records the slot's event)
+}
+
+}  // namespace
+
+extern "C" {
+
+int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                    const VrFrame* frames, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = validate_batch(t, n_frames, cams, opt, frames, k)) return rc;
+    DeviceGuard device_guard(t->device);
+    fill_caller_params(k, &cams[0], opt, &frames[0]);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    std::unique_lock<std::mutex> guard(t->launch_mutex);
+    fill_tree_params(k, t);  // (under the mutex: vr_touch_enable / vr_touch_count (re)allocate the bitmaps)
+    const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
+    fill_tuning_params(k, t, tn);
+    unsigned slot;
+    if (int rc = acquire_slot(t, guard, hs, k, slot)) return rc;
+    return enqueue_launch(t, t->slots[slot], k, tn, cams, opt, frames, hs);
 }
 
 int vr_reserve_tiles(vr_tree_t t, int width, int height, int n_frames, int tile_w, int tile_h,

@@ -33,9 +33,6 @@ constexpr int kSh9Waves = 7;    // 72 VGPRs without scratch since the lane's ray
                                 // counters in scalar registers (round 5; C3 -1...-3 % against 6)
 constexpr int kSh16Rows = 64;   // SH16 items per shade round (56 fits 24 waves per CU into the LDS, but measured
                                 // slower: 0.275 against 0.265 ms per C1 frame)
-// Guard against rays that never end (upstream would spin forever): KParams.max_iter march rounds
-// of a wave since its last retire / refill pass that retired a ray, default 2^22 (tuning key
-// `max_iter`, for tests).
 
 // ---------------------------------------------------------------------------
 // render_kernel: render_kernel + trace_ray of the reference
@@ -129,11 +126,10 @@ __device__ __forceinline__ void issue_records(const KParams& p, char* stage, con
     }
 }
 
-// Register budget of the fused FAST flavours (waves per SIMD), from their natural register use:
-// SH16 96 VGPRs -> kSh16Waves = 5 (20 waves per CU; 6 needs <= 80 and spills), SH9 <= 72 ->
-// kSh9Waves = 7, SH25 <= 128 -> 4 (it gathers its 25 basis values up front), the small
-// records 8.  The instrumented / lobe / generic flavours keep their wider state in registers at
-// 4 waves per SIMD (3 for SH25).  No render flavour uses scratch.
+// Waves per SIMD a flavour is compiled for: the fused FAST flavours their budgets above (SH25
+// gathers its 25 basis values up front), the small records 8.  The instrumented / lobe / generic
+// flavours keep their wider state in registers at 4 waves per SIMD (3 for SH25).  No render
+// flavour uses scratch.
 template <int BASIS, int MODE>
 constexpr int min_waves_per_eu() {
     if (MODE != MODE_FAST) return BASIS == BASIS_25 ? 3 : 4;  // SH25 + counters needs > 128 VGPRs
@@ -344,11 +340,11 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
             ray.stopped = ray.tmax < 0.f;  // (read before a new ray's tmax lands in the register)
             if (done) {
                 const uint32_t* rs = ray_slot(p.ray_buf, wpr, ray_ids[lane_id_now()]);
-                px_lo = ray_word(rs, 13);
-                px_hi = ray_word(rs, 14);
+                px_lo = ray_word(rs, kRayPixelLo);
+                px_hi = ray_word(rs, kRayPixelHi);
                 if (COUNT || p.any_accum) {
-                    fin_xy = ray_word(rs, 12);
-                    fin_frame = ray_word(rs, 15);
+                    fin_xy = ray_word(rs, kRayXy);
+                    fin_frame = ray_word(rs, kRayFrame);
                 }
             }
             const bool vacant = done || !ray.active;
@@ -378,9 +374,7 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
             }
             if (!exhausted) {
                 const unsigned long long idle = m_done | m_free;
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi(
-                    (uint32_t)(idle >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)idle, 0u));
-                const uint32_t r = chunk_next + rank;
+                const uint32_t r = chunk_next + lane_rank(idle);
                 const uint32_t c_end = chunk_end;
                 const uint32_t left = chunk_end - chunk_next;
                 chunk_next += (uint32_t)n_avail < left ? (uint32_t)n_avail : left;
@@ -389,13 +383,13 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
                     const uint32_t* rs = ray_slot(p.ray_buf, wpr, r);
 #pragma unroll
                     for (int i = 0; i < 3; ++i) {
-                        ray.cen[i] = u2f(ray_word(rs, 0 + i));
-                        ray.dir[i] = u2f(ray_word(rs, 3 + i));
-                        ray.invdir[i] = u2f(ray_word(rs, 6 + i));
+                        ray.cen[i] = u2f(ray_word(rs, kRayCen + i));
+                        ray.dir[i] = u2f(ray_word(rs, kRayDir + i));
+                        ray.invdir[i] = u2f(ray_word(rs, kRayInvDir + i));
                     }
-                    ray.t = u2f(ray_word(rs, 9));
-                    ray.tmax = u2f(ray_word(rs, 10));
-                    ray.delta_scale = u2f(ray_word(rs, 11));
+                    ray.t = u2f(ray_word(rs, kRayT));
+                    ray.tmax = u2f(ray_word(rs, kRayTmax));
+                    ray.delta_scale = u2f(ray_word(rs, kRayDeltaScale));
                     ray_ids[lane_id_now()] = r;
                     if (HAS_BASIS) {
                         if (BASIS > 1 && p.ray_vdir) {
@@ -404,7 +398,7 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
                             // here, by the lane that takes the ray, from 3 words of the record
                             float vd[3];
 #pragma unroll
-                            for (int i = 0; i < 3; ++i) vd[i] = u2f(ray_word(rs, kRayWords + i));
+                            for (int i = 0; i < 3; ++i) vd[i] = u2f(ray_word(rs, kRayTail + i));
                             precalc_basis<FMA, false, (BASIS > 1 ? BASIS : 1)>(p, vd, mybasis);
 #pragma unroll
                             for (int i = 0; i < NB; ++i)
@@ -412,7 +406,7 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
                         } else {
 #pragma unroll
                             for (int i = 0; i < NB; ++i)
-                                mybasis[i] = u2f(ray_word(rs, kRayWords + i));
+                                mybasis[i] = u2f(ray_word(rs, kRayTail + i));
                         }
                     }
                 }
@@ -443,7 +437,8 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
 
         // ---- march: lanes with a live ray and room for another outstanding item ----
         // Guard against rays that never end (not in the reference, which would spin): when the
-        // wave has marched p.max_iter rounds since its last retire / refill pass that retired a ray
+        // wave has marched p.max_iter rounds (tuning key `max_iter`, for tests) since its last
+        // retire / refill pass that retired a ray
         // (progress_round above: with the default of 2^22 rounds the difference to "without a
         // retired ray" is nil; a lowered max_iter trips earlier the larger refill_min is), whatever is still
         // marching is cut and reported (sticky status bit 0: the host layers fail loudly on it;
@@ -528,10 +523,7 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
             const unsigned long long m_push = __builtin_amdgcn_ballot_w64(push);
             if (m_push != 0ull) {
                 if (push) {
-                    const uint32_t seq =
-                        ring_tail + __builtin_amdgcn_mbcnt_hi(
-                                        (uint32_t)(m_push >> 32),
-                                        __builtin_amdgcn_mbcnt_lo((uint32_t)m_push, 0u));
+                    const uint32_t seq = ring_tail + lane_rank(m_push);
                     const uint32_t j = seq & (kRing - 1);
                     it_leaf[j] = leaf;
                     it_w[j] = weight;
@@ -571,14 +563,14 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
         }
     }
     if (COUNT && p.sched_stats && lane == 0) {
-        atomicAdd(&p.sched_stats[0], (unsigned long long)st_march_r);
-        atomicAdd(&p.sched_stats[1], (unsigned long long)st_march_l);
-        atomicAdd(&p.sched_stats[2], (unsigned long long)st_shade_r);
-        atomicAdd(&p.sched_stats[3], (unsigned long long)st_shade_l);
-        atomicAdd(&p.sched_stats[4], (unsigned long long)st_distinct);
-        atomicAdd(&p.sched_stats[5], (unsigned long long)st_fin_r);
-        atomicAdd(&p.sched_stats[6], (unsigned long long)st_fin_l);
-        atomicAdd(&p.sched_stats[7], (unsigned long long)st_iter);
+        atomicAdd(&p.sched_stats[kStatMarchRounds], (unsigned long long)st_march_r);
+        atomicAdd(&p.sched_stats[kStatMarchLanes], (unsigned long long)st_march_l);
+        atomicAdd(&p.sched_stats[kStatShadeRounds], (unsigned long long)st_shade_r);
+        atomicAdd(&p.sched_stats[kStatShadeLanes], (unsigned long long)st_shade_l);
+        atomicAdd(&p.sched_stats[kStatDistinctLeaves], (unsigned long long)st_distinct);
+        atomicAdd(&p.sched_stats[kStatRetireRounds], (unsigned long long)st_fin_r);
+        atomicAdd(&p.sched_stats[kStatRetiredRays], (unsigned long long)st_fin_l);
+        atomicAdd(&p.sched_stats[kStatIterations], (unsigned long long)st_iter);
     }
 }
 
@@ -636,13 +628,14 @@ __global__ __launch_bounds__(kWave* GW) void raygen_kernel(const KParams p) {
     // single word only sustains ~90 returning atomics per microsecond chip-wide; workgroups never
     // straddle a queue boundary: those lie at multiples of 16 blocks).
     const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
-    const uint32_t nq = (uint32_t)p.n_queues, sh = nq == 8u ? 3u : 0u;
-    const uint32_t n16 = ((p.total_rays >> 6) + 15u) >> 4;
+    const uint32_t nq = (uint32_t)p.n_queues;
+    uint32_t sh, n16;
+    queue_split(p, sh, n16);
     const uint32_t g16 = (uint32_t)(((int64_t)blockIdx.x * GW) >> 4);  // this workgroup's group of 16 blocks
     uint32_t qx = (uint32_t)(((uint64_t)g16 << sh) / n16);               // its queue: first guess, then exact
     while (qx + 1u < nq && (queue_first_block(n16, qx + 1u, sh) >> 4) <= g16) ++qx;
     while (qx > 0u && (queue_first_block(n16, qx, sh) >> 4) > g16) --qx;
-    uint32_t* const q_count = p.queue_head + qx * kQueueStride + 1;
+    uint32_t* const q_count = p.queue_head + qx * kQueueStride + kQueueCount;
     const uint32_t q_base = queue_first_block(n16, qx, sh) << 6;
     uint32_t my_base;
     if constexpr (GW == 1) {
@@ -668,29 +661,26 @@ __global__ __launch_bounds__(kWave* GW) void raygen_kernel(const KParams p) {
         my_base = wave_base[wave];
     }
     if (!valid) return;
-    const uint32_t slot =
-        my_base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m_valid >> 32),
-                                            __builtin_amdgcn_mbcnt_lo((uint32_t)m_valid, 0u));
+    const uint32_t slot = my_base + lane_rank(m_valid);
     uint32_t* rb = ray_slot(p.ray_buf_rw, kRayWords + p.ray_tail_words, slot);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        rb[(0 + i) * 64] = f2u(nr.cen[i]);
-        rb[(3 + i) * 64] = f2u(nr.dir[i]);
-        rb[(6 + i) * 64] = f2u(nr.invdir[i]);
+        ray_word(rb, kRayCen + i) = f2u(nr.cen[i]);
+        ray_word(rb, kRayDir + i) = f2u(nr.dir[i]);
+        ray_word(rb, kRayInvDir + i) = f2u(nr.invdir[i]);
     }
-    rb[9 * 64] = f2u(nr.t);
-    rb[10 * 64] = f2u(nr.tmax);
-    rb[11 * 64] = f2u(nr.delta_scale);
-    rb[12 * 64] = xy;
-    rb[13 * 64] = (uint32_t)reinterpret_cast<uint64_t>(px);
-    rb[14 * 64] = (uint32_t)(reinterpret_cast<uint64_t>(px) >> 32);
-    rb[15 * 64] = (uint32_t)frame;
+    ray_word(rb, kRayT) = f2u(nr.t);
+    ray_word(rb, kRayTmax) = f2u(nr.tmax);
+    ray_word(rb, kRayDeltaScale) = f2u(nr.delta_scale);
+    ray_word(rb, kRayXy) = xy;
+    ray_word(rb, kRayPixelLo) = (uint32_t)reinterpret_cast<uint64_t>(px);
+    ray_word(rb, kRayPixelHi) = (uint32_t)(reinterpret_cast<uint64_t>(px) >> 32);
+    ray_word(rb, kRayFrame) = (uint32_t)frame;
     if (p.ray_vdir) {
         // SH trees: the (rotated) view direction travels, its basis is evaluated when a lane takes
         // the ray (3 words instead of up to 25: the ray buffer is written and read once per ray)
-        rb[(kRayWords + 0) * 64] = f2u(vdir[0]);
-        rb[(kRayWords + 1) * 64] = f2u(vdir[1]);
-        rb[(kRayWords + 2) * 64] = f2u(vdir[2]);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) ray_word(rb, kRayTail + i) = f2u(vdir[i]);
     } else if (p.basis_words > 0) {
         // rt_core.cuh:96-103: basis of the view direction, zeroed outside basis_minmax
         float b[VR_MAX_BASIS];
@@ -700,8 +690,7 @@ __global__ __launch_bounds__(kWave* GW) void raygen_kernel(const KParams p) {
 #pragma unroll
         for (int i = 0; i < VR_MAX_BASIS; ++i)
             if (i < p.basis_words)
-                rb[(kRayWords + i) * 64] =
-                    f2u((i < p.basis_min || i > p.basis_max) ? 0.f : b[i]);
+                ray_word(rb, kRayTail + i) = f2u((i < p.basis_min || i > p.basis_max) ? 0.f : b[i]);
     }
 }
 
@@ -710,9 +699,9 @@ __global__ __launch_bounds__(kWave* GW) void raygen_kernel(const KParams p) {
 __global__ void prepare_launch_kernel(FrameTable tbl, FrameDesc* frames, uint32_t* queue_head) {
     const int i = threadIdx.x;
     if (i < tbl.n) frames[tbl.first + i] = tbl.f[i];
-    if (tbl.first == 0 && i < 8) {
-        queue_head[i * kQueueStride] = 0u;      // rays handed out
-        queue_head[i * kQueueStride + 1] = 0u;  // rays stored
+    if (tbl.first == 0 && i < kMaxQueues) {
+        queue_head[i * kQueueStride + kQueueHead] = 0u;
+        queue_head[i * kQueueStride + kQueueCount] = 0u;
     }
 }
 
@@ -768,14 +757,7 @@ __global__ void probe_overlay_kernel(const KParams p) {
     const FrameDesc& fd = p.frames[blockIdx.y];
     if (fd.accum) reinterpret_cast<float4*>(fd.accum)[pix] = make_float4(out[0], out[1], out[2], out[3]);
     // nalpha = 1 - out[3] = 0: the composite adds (+0 * anything) and leaves out[] as is
-    uint8_t* px;
-    if (p.layout == VR_LAYOUT_COMPACT) {
-        const int k = tile / p.world;
-        const int lx = x - tx * p.tile_w, ly = y - ty * p.tile_h;
-        px = fd.rgba + ((int64_t)k * p.tile_w * p.tile_h + (int64_t)ly * p.tile_w + lx) * 4;
-    } else {
-        px = fd.rgba + (int64_t)y * p.pitch + (int64_t)x * 4;
-    }
+    uint8_t* const px = pixel_address(p, fd, tile / p.world, x - tx * p.tile_w, y - ty * p.tile_h, x, y);
     *reinterpret_cast<uint32_t*>(px) =
         quant8(out[0]) | (quant8(out[1]) << 8) | (quant8(out[2]) << 16) | 0xFF000000u;
 }
@@ -804,18 +786,6 @@ bool needs_full(const KParams& p) {
 template <int FMA, int MODE>
 hipError_t launch_basis(const KParams& p, int64_t want, int n_cus, int waves_override, hipStream_t s) {
     const dim3 block(kWave);
-    int b;
-    if (p.basis_dim < 0 || p.format == VR_FORMAT_RGBA) {
-        b = BASIS_RGBA;
-    } else {
-        switch (p.basis_dim) {  // the reference's switch only knows 25/16/9/4 (rt_core.cuh:132-160)
-            case 25: b = BASIS_25; break;
-            case 16: b = BASIS_16; break;
-            case 9: b = BASIS_9; break;
-            case 4: b = BASIS_4; break;
-            default: b = BASIS_1; break;
-        }
-    }
 #define VR_LAUNCH(B)                                                                         \
     do {                                                                                     \
         const int64_t cap_ = (int64_t)n_cus * (waves_override > 0 ? waves_override           \
@@ -826,7 +796,7 @@ hipError_t launch_basis(const KParams& p, int64_t want, int n_cus, int waves_ove
         else                                                                                 \
             hipLaunchKernelGGL((render_kernel<FMA, B, MODE, false>), grid, block, 0, s, p);  \
     } while (0)
-    switch (b) {
+    switch (basis_flavour(p.format, p.basis_dim)) {
         case BASIS_RGBA: VR_LAUNCH(BASIS_RGBA); break;
         case BASIS_25: VR_LAUNCH(BASIS_25); break;
         case BASIS_16: VR_LAUNCH(BASIS_16); break;

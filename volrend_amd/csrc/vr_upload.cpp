@@ -434,12 +434,12 @@ int check_tree_desc(const VrTreeDesc* d, bool need_data) {
 hipError_t alloc_launch_scratch(VrTreeOpaque* t) {
     hipError_t e = t->status.alloc(sizeof(uint32_t));
     if (e == hipSuccess) e = hipMemset(t->status.get(), 0, sizeof(uint32_t));
-    if (e == hipSuccess) e = t->sched_stats.alloc(8 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMemset(t->sched_stats.get(), 0, 8 * sizeof(unsigned long long));
+    if (e == hipSuccess) e = t->sched_stats.alloc(vr::kSchedStats * sizeof(unsigned long long));
+    if (e == hipSuccess) e = hipMemset(t->sched_stats.get(), 0, vr::kSchedStats * sizeof(unsigned long long));
     if (e == hipSuccess) e = t->probe_buf.alloc(sizeof(float) * (size_t)t->desc.data_dim * kLaunchSlots);
     for (unsigned i = 0; i < kLaunchSlots && e == hipSuccess; ++i) e = t->slots[i].done.create();
     if (e == hipSuccess) e = t->slot_frames.alloc(sizeof(vr::FrameDesc) * vr::kMaxBatch * kLaunchSlots);
-    if (e == hipSuccess) e = t->slot_heads.alloc(sizeof(uint32_t) * kSlotWords * kLaunchSlots);
+    if (e == hipSuccess) e = t->slot_heads.alloc(sizeof(uint32_t) * vr::kSlotWords * kLaunchSlots);
     int cus = 0;
     if (e == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess &&
         cus > 0)
