@@ -18,6 +18,10 @@
  *                                   device::render_kernel              include/volrend/cuda/renderer_kernel.hpp:9-12,
  *                                                                      src/cuda/volrend.cu:78-173,195-245
  *   vr_probe_coeffs                 retrieve_cursor_lumisphere_kernel  src/cuda/volrend.cu:175-191
+ *   vr_query_points / vr_query_grid the same for many points per launch
+ *                                   (query_single_from_root + one
+ *                                   sample's colour)                   include/volrend/internal/n3tree_query.hpp:13-48,
+ *                                                                      include/volrend/cuda/rt_core.cuh:125-163
  *   vr_read_back                    cudaMemcpy2DFromArrayAsync         main_headless.cpp:217-219
  *   vr_last_error / return codes    cuda_assert (print+exit) becomes
  *                                   an error code, the library never
@@ -320,6 +324,55 @@ int vr_assemble_tiles_batch(void* frames_rgba, int64_t frame_stride, int64_t pit
                             void* stream);
 /* out_dev: device float[data_dim-1]; the lumisphere at opt->probe. */
 int vr_probe_coeffs(vr_tree_t tree, const VrRenderOptions* opt, float* out_dev, void* stream);
+
+/* ---- bulk point queries ------------------------------------------------ */
+/* What the uploaded tree holds at many points at once: query_single_from_root
+ * (n3tree_query.hpp:13-48) per point, the record of the leaf it finds, and the colour a sample
+ * there has along a direction (rt_core.cuh:125-163) -- vr_probe_coeffs for n points in one launch,
+ * through the lookup structure of the tree where upload built one.  Every output is a pure
+ * function of one point (and one direction), bit-identical to the reference's arithmetic.
+ *
+ * Both calls only enqueue on `stream`, run on the tree's device whatever the thread's current
+ * device is, take no launch slot, hold no per-call scratch and only read the tree: any number of
+ * them may run beside each other and beside vr_render* launches, on any streams and host threads.
+ *
+ * Position.  VR_SPACE_WORLD: tree coordinate = offset + scale * x (one rounding per operator, as
+ * vr_probe_coeffs); VR_SPACE_TREE: x is a tree coordinate already.  The tree coordinate is clamped
+ * as the reference writes it, max(min(x, 1 - 1e-6f), 0), so every input is defined: NaN goes to
+ * 1 - 1e-6f, -0 to +0, +-inf to the ends.  (The render kernels clamp with one median instruction,
+ * which sends NaN to 0; a point query pays the second instruction.)
+ *
+ * rgb.  SH trees: 1 / (1 + exp(-tmp)) per channel, tmp the basis-weighted sum of the channel's
+ * coefficients in the reference's association (groups 25, 16, 9, 4, each left to right), over
+ * the whole basis (no basis_minmax, no rot_dirs); basis sizes other than 4 / 9 / 16 / 25 use the
+ * first coefficient of each channel, as vr_render does.  RGBA trees: the first three entries of
+ * the record.  The basis is evaluated at dirs[i] AS GIVEN: the library does not normalise it (the
+ * reference normalises a ray's direction before it becomes the view direction; pass a unit vector
+ * to get a sample's colour).  Evaluated in the VR_FP_STRICT model only, independent of sigma (no
+ * sigma_thresh).  SG / ASG trees: VR_ERR_UNSUPPORTED when rgb is asked for; the other outputs work. */
+enum { VR_SPACE_WORLD = 0, VR_SPACE_TREE = 1 };
+
+typedef struct VrQueryOut {   /* device pointers; NULL = not wanted; at least one non-NULL */
+    float* sigma;    /* [n]             density of the leaf (fp16 -> fp32, exact) */
+    int32_t* depth;  /* [n]             depth of the leaf as VrTreeInfo.max_depth counts it (child words read - 1) */
+    float* local;    /* [n][3]          leaf-local coordinate: xyz as query_single_from_root leaves it */
+    float* coeffs;   /* [n][data_dim-1] the record (fp16 -> fp32, exact): what vr_probe_coeffs gives */
+    float* rgb;      /* [n][3]          colour of a sample at the point along dirs[i]; needs directions */
+} VrQueryOut;
+
+/* xyz_dev [n][3], dirs_dev [n][3] or NULL: device float32.  n == 0 is VR_OK and launches nothing.
+ * VR_ERR_INVALID_ARGUMENT: NULL tree / xyz / out, every output NULL, rgb without dirs, n < 0,
+ * unknown space. */
+int vr_query_points(vr_tree_t tree, int64_t n, const float* xyz_dev, const float* dirs_dev, int space,
+                    const VrQueryOut* out, void* stream);
+/* The same for the res[0] * res[1] * res[2] cell centres of the box lo..hi (host arrays), generated
+ * on the device: cell (i, j, k) has output index (i * res[1] + j) * res[2] + k and per axis the
+ * coordinate lo + ((float)i + 0.5f) * ((hi - lo) / (float)res) in binary32, one rounding per
+ * operator.  dir: one direction for all cells, or NULL.  Also VR_ERR_INVALID_ARGUMENT: NULL lo /
+ * hi / res, a res[i] < 1, more than 2^40 cells. */
+int vr_query_grid(vr_tree_t tree, const float lo[3], const float hi[3], const int32_t res[3],
+                  const float dir[3], int space, const VrQueryOut* out, void* stream);
+
 /* Async D2H of a pitched RGBA8 frame into tightly packed host memory. */
 int vr_read_back(void* host_rgba, const void* dev_rgba, int64_t pitch, int width, int height,
                  void* stream);

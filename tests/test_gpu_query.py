@@ -1,0 +1,575 @@
+"""-m gpu: bulk point queries (vr_query_points / vr_query_grid, volrend_amd/csrc/vr_query.hip)
+against the CPU oracle.
+
+Reference: query_single_from_root (n3tree_query.hpp:13-48), retrieve_cursor_lumisphere_kernel
+(volrend.cu:175-191) and the colour of one sample (rt_core.cuh:125-171).  Bar: every 32-bit word of
+every output equal to the oracle's (or_query, or_probe_coeffs, and for the colour the recomposition
+tests/test_query_host.py pins to or_render); a NaN output must be a NaN in the same place, with any
+payload (tests/common.assert_same_values).  No test drops or masks points.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import common, query_util as qu
+from tests.common import ob
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU visible")
+    return torch
+
+
+# name -> (tree factory, seed of the point set, points by depth); the seeds were chosen on the CPU so
+# that the oracle alone meets the conditions of query_util.check_point_set
+# (tests/test_query_host.py::test_point_sets_meet_their_conditions_on_the_oracle)
+POINT_TREES = {
+    "SH4_d5": (lambda: common.small_scene(depth=5, basis_dim=4, seed=11), 101, False),
+    "SH16_d6": (lambda: common.small_scene(depth=6, basis_dim=16, seed=12), 102, False),
+    "SH1": (lambda: common.small_scene(depth=5, basis_dim=1, seed=13), 103, False),
+    "SH9": (lambda: common.small_scene(depth=5, basis_dim=9, seed=14), 104, False),
+    "SH25": (lambda: common.small_scene(depth=5, basis_dim=25, seed=15), 105, False),
+    "RGBA": (lambda: common.small_scene(depth=5, basis_dim=0, fmt="RGBA", seed=16), 106, False),
+    "SG7": (lambda: common.small_scene(depth=5, basis_dim=7, fmt="SG", seed=17), 107, False),
+    "ASG4": (lambda: common.small_scene(depth=5, basis_dim=4, fmt="ASG", seed=18), 108, False),
+    "edge_SH9": (lambda: common.value_edge_tree("SH", 9, seed=3), 109, False),
+    "fog_SH16": (lambda: common.fog_tree("SH", 16, seed=5, depth=5), 110, False),
+    "N3": (lambda: common.random_tree_general_n(N=3, depth=4, basis_dim=4, seed=21), 111, False),
+    "N4": (lambda: common.random_tree_general_n(N=4, depth=3, basis_dim=9, seed=22), 112, False),
+    "chain28": (lambda: common.deep_chain_tree_n2(28, basis_dim=4, seed=2)[0], 113, True),
+}
+
+
+def make_point_tree(name, n=100_000):
+    factory, seed, by_depth = POINT_TREES[name]
+    tree = factory()
+    return tree, qu.point_set(tree, n, seed, by_depth=by_depth)
+
+
+def same_words(got, want, what):
+    """Bit equality of 32-bit words; a NaN must meet a NaN (any payload)."""
+    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} vs {want.shape}"
+    if got.dtype == np.float32:
+        ng, nw = np.isnan(got), np.isnan(want)
+        assert np.array_equal(ng, nw), f"{what}: NaN in {int((ng & ~nw).sum())} kernel / {int((nw & ~ng).sum())} oracle words only"
+        diff = (got.view(np.uint32) != want.view(np.uint32)) & ~nw
+    else:
+        diff = got != want
+    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} words differ (first at {np.argwhere(diff)[0].tolist()})"
+
+
+def gpu_query(torch, t, pts, dirs=None, want=("sigma", "depth", "local", "coeffs"), space="tree", stream=None):
+    p = torch.from_numpy(np.ascontiguousarray(pts, np.float32)).cuda()
+    d = None if dirs is None else torch.from_numpy(np.ascontiguousarray(dirs, np.float32)).cuda()
+    out = t.query(p, d, want=want, space=space, stream=stream)
+    torch.cuda.synchronize()
+    return {k: v.cpu().numpy() for k, v in out.items()}
+
+
+def check_against_oracle(torch, t, tree, th, pts, space, what, ans=None):
+    ans = ans or qu.oracle_answers(tree, th, pts, space)
+    got = gpu_query(torch, t, pts, space=space)
+    for k in ("sigma", "depth", "local", "coeffs"):
+        same_words(got[k], ans[k], f"{what} {space} {k}")
+    return ans
+
+
+# ---- sigma / depth / local / coeffs ------------------------------------------------------------
+@pytest.mark.parametrize("name", list(POINT_TREES))
+def test_points_match_oracle_in_both_spaces(torch_cuda, name):
+    from volrend_amd import api
+    tree, pts = make_point_tree(name)
+    th = ob.TreeHandle(tree)
+    ans = qu.oracle_answers(tree, th, pts, "tree")
+    qu.check_point_set(tree, ans, name)           # on the oracle's answers, before the kernel is looked at
+    t = api.N3Tree.from_synth(tree)
+    info = t.info()
+    assert info["query_mode"] == (_mode_of(name)), info
+    check_against_oracle(torch_cuda, t, tree, th, pts, "tree", name, ans)
+    world = qu.to_world(tree, pts)
+    ans_w = check_against_oracle(torch_cuda, t, tree, th, world, "world", name)
+    # the record of a world point IS what or_probe_coeffs gives there, point by point
+    step = 1 if name in ("SH4_d5", "SH16_d6") else 8
+    same_words(ans_w["coeffs"][::step], qu.probe_coeffs(th, tree, world[::step]), f"{name}: or_probe_coeffs")
+    t.free_device()
+
+
+def _mode_of(name):
+    from volrend_amd import _abi
+    return _abi.QUERY_DESCENT if name in ("N3", "N4", "chain28") else _abi.QUERY_LOOKUP
+
+
+def test_quantised_upload_answers_like_the_decoded_tree(torch_cuda, tmp_path):
+    from volrend_amd import api
+    tree = common.small_scene(depth=5, basis_dim=4, seed=19)
+    path = str(tmp_path / "q.npz")
+    common.write_quantised_npz(tree, path, n_retain=1)
+    t = api.N3Tree(path)
+    assert t.data_ is None, "the tree must have gone through the device decode"
+    pts = qu.point_set(tree, 100_000, 114)
+    th = ob.TreeHandle(tree)
+    ans = qu.oracle_answers(tree, th, pts, "tree")
+    qu.check_point_set(tree, ans, "quantised")
+    check_against_oracle(torch_cuda, t, tree, th, pts, "tree", "quantised", ans)
+    check_against_oracle(torch_cuda, t, tree, th, qu.to_world(tree, pts), "world", "quantised")
+    t.free_device()
+
+
+def special_points(tree, seed):
+    """NaN, +-inf, -0, negatives, >= 1, 1 - 1e-6f and both neighbours, subnormals -- one, two and three
+    at a time -- and on N = 2 trees the cell faces k / 2^d of every depth present with their float
+    neighbours."""
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    hi = qu.HI
+    spec = np.array([np.nan, np.inf, -np.inf, -0.0, 0.0, -1e-3, -7.5, 1.0, 1.5, 3e38, hi,
+                     np.nextafter(hi, f32(0)), np.nextafter(hi, f32(2)), 1e-45, -1e-45, 1e-39, 5.8e-39,
+                     0.5, np.nextafter(f32(1), f32(0))], f32)
+    sets = []
+    for axis_count in (1, 2, 3):
+        p = rng.random((60 * spec.size, 3)).astype(f32)
+        for row in p:
+            axes = rng.choice(3, axis_count, replace=False)
+            row[axes] = spec[rng.integers(spec.size, size=axis_count)]
+        sets.append(p)
+    sets.append(np.stack(np.meshgrid(spec, spec, spec[:6]), -1).reshape(-1, 3))
+    if tree.N == 2:
+        for d in np.unique(qu.leaf_boxes(tree)[2]) + 1:
+            d = int(min(d, 30))
+            k = rng.integers(0, 2 ** d + 1, size=(300, 3)).astype(np.float64) / 2.0 ** d
+            face = k.astype(f32)
+            p = rng.random((300, 3)).astype(f32)
+            axes = rng.integers(3, size=300)
+            for off in (None, f32(0), f32(2)):
+                v = face if off is None else np.nextafter(face, off)
+                q = p.copy()
+                q[np.arange(300), axes] = v[np.arange(300), axes]
+                sets.append(q)
+                sets.append(v.copy())
+    return np.concatenate(sets).astype(f32)
+
+
+@pytest.mark.parametrize("name", ["SH4_d5", "edge_SH9", "N3", "chain28"])
+def test_special_coordinates(torch_cuda, name):
+    from volrend_amd import api
+    tree = POINT_TREES[name][0]()
+    pts = special_points(tree, 300 + len(name))
+    th = ob.TreeHandle(tree)
+    t = api.N3Tree.from_synth(tree)
+    ans = check_against_oracle(torch_cuda, t, tree, th, pts, "tree", f"{name} special")
+    assert np.isnan(pts).any() and not np.isnan(ans["local"]).any()
+    # world space: the special value goes through offset + scale * x first (NaN and inf survive it)
+    check_against_oracle(torch_cuda, t, tree, th, pts, "world", f"{name} special")
+    t.free_device()
+
+
+# ---- colour ---------------------------------------------------------------------------------------
+def direction_set(n, seed):
+    """Unit vectors, un-normalised ones (x 0.3, x 3), exact axes and zero directions."""
+    rng = np.random.default_rng(seed)
+    d = rng.standard_normal((n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    d[1::4] *= 0.3
+    d[2::4] *= 3.0
+    d[3::64] = 0.0
+    d[5::64] = (0.0, 0.0, -1.0)
+    d[7::64] = (1.0, 0.0, 0.0)
+    return d.astype(np.float32)
+
+
+RGB_TREES = ["SH1", "SH4_d5", "SH9", "SH16_d6", "SH25", "RGBA", "edge_SH9", "edge_SH16", "edge_RGBA", "N3"]
+
+
+@pytest.mark.parametrize("name", RGB_TREES)
+def test_rgb_matches_the_recomposition(torch_cuda, name):
+    from volrend_amd import api
+    if name == "edge_SH16":
+        tree = common.value_edge_tree("SH", 16, seed=4)
+    elif name == "edge_RGBA":
+        tree = common.value_edge_tree("RGBA", 0, seed=6)
+    else:
+        tree = POINT_TREES[name][0]()
+    n = 40_000
+    pts = qu.point_set(tree, n, 500 + len(name))
+    dirs = direction_set(n, 600 + len(name))
+    th = ob.TreeHandle(tree)
+    ans = qu.oracle_answers(tree, th, pts, "tree")
+    assert (ans["sigma"] > 0).mean() >= 0.25
+    want = qu.recompose_rgb(tree, th, ans["coeffs"], dirs)
+    if name.startswith("edge_SH"):
+        assert np.isnan(want).any(), "the value-edge tree should produce NaN colours"
+    t = api.N3Tree.from_synth(tree)
+    got = gpu_query(torch_cuda, t, pts, dirs, want=("rgb", "sigma", "coeffs"))
+    same_words(got["rgb"], want, f"{name} rgb")
+    same_words(got["sigma"], ans["sigma"], f"{name} sigma next to rgb")
+    same_words(got["coeffs"], ans["coeffs"], f"{name} coeffs next to rgb")
+    only = gpu_query(torch_cuda, t, qu.to_world(tree, pts), dirs, want=("rgb",), space="world")
+    ans_w = qu.oracle_answers(tree, th, qu.to_world(tree, pts), "world")
+    same_words(only["rgb"], qu.recompose_rgb(tree, th, ans_w["coeffs"], dirs), f"{name} rgb alone, world")
+    t.free_device()
+
+
+@pytest.mark.parametrize("fmt,basis_dim", [("SH", 1), ("SH", 4), ("SH", 9), ("SH", 16), ("SH", 25), ("RGBA", 0)],
+                         ids=["SH1", "SH4", "SH9", "SH16", "SH25", "RGBA"])
+def test_rgb_equals_or_render_on_one_sample_scenes(torch_cuda, fmt, basis_dim):
+    """The kernel fed the restated pixel directions gives or_render's accumulators (first sample
+    opaque: weight 1) -- the inputs of tests/test_query_host.py (b)."""
+    from volrend_amd import api
+    tree = qu.one_sample_tree(basis_dim, fmt, seed=40 + basis_dim)
+    tr, w, h, f = common.axis_camera(size=33, focal=40.0, dist=4.0)
+    _, acc, cnt = common.oracle_frame(tree, tr, w, h, f, ob.FP_STRICT)
+    assert (acc[..., 3] == 1.0).all() and cnt["rays_hit_box"] == w * h, "every pixel must be a hit"
+    dirs = qu.pixel_dirs(w, h, f, f).reshape(-1, 3)
+    pts = np.random.default_rng(3).uniform(-0.9, 0.9, size=(w * h, 3)).astype(np.float32)
+    t = api.N3Tree.from_synth(tree)
+    got = gpu_query(torch_cuda, t, pts, dirs, want=("rgb",), space="world")
+    same_words(got["rgb"], np.ascontiguousarray(acc[..., :3]).reshape(-1, 3), f"{fmt}{basis_dim}")
+    t.free_device()
+
+
+# ---- grid ------------------------------------------------------------------------------------------
+def grid_coords(lo, hi, res):
+    """lo + ((float)i + 0.5f) * ((hi - lo) / (float)res) per axis in float32 -> [r0, r1, r2, 3]."""
+    f32 = np.float32
+    lo, hi = np.asarray(lo, f32), np.asarray(hi, f32)
+    ax = []
+    for a in range(3):
+        cell = (hi[a] - lo[a]) / f32(res[a])
+        ax.append(lo[a] + (np.arange(res[a]).astype(f32) + f32(0.5)) * cell)
+    g = np.stack(np.meshgrid(*ax, indexing="ij"), -1)
+    assert g.dtype == f32
+    return np.ascontiguousarray(g)
+
+
+GRID_CASES = [
+    ((0.1, 0.2, 0.15), (0.8, 0.9, 0.7), (37, 5, 64), "tree"),        # inside
+    ((-0.3, 0.4, -0.2), (0.6, 1.4, 1.3), (37, 5, 64), "tree"),       # straddling
+    ((1.5, -3.0, 2.0), (2.5, -2.0, 9.0), (5, 3, 7), "tree"),         # outside
+    ((-0.9, -0.9, -0.9), (0.9, 0.9, 0.9), (3, 70, 130), "world"),    # rows of 2 full chunks + 2 cells
+    ((0.7, -0.2, 0.1), (-0.4, 0.5, 0.1), (1, 129, 63), "world"),     # hi < lo, and a flat axis
+]
+
+
+@pytest.mark.parametrize("name", ["SH16_d6", "RGBA", "N3"])
+def test_grid_equals_points(torch_cuda, name):
+    torch = torch_cuda
+    from volrend_amd import api
+    tree = POINT_TREES[name][0]()
+    th = ob.TreeHandle(tree)
+    t = api.N3Tree.from_synth(tree)
+    want_all = ("sigma", "depth", "local", "coeffs", "rgb")
+    direction = (0.3, -0.5, 0.8)
+    for lo, hi, res, space in GRID_CASES:
+        g = t.query_grid(lo, hi, res, direction, want=want_all, space=space)
+        torch.cuda.synchronize()
+        coords = grid_coords(lo, hi, res)
+        n = coords.size // 3
+        dirs = np.broadcast_to(np.float32(direction), (n, 3))
+        p = gpu_query(torch, t, coords.reshape(-1, 3), dirs, want=want_all, space=space)
+        for k in want_all:
+            got = g[k].cpu().numpy()
+            assert got.shape[:3] == tuple(res), (k, got.shape)
+            same_words(got.reshape(p[k].shape), p[k], f"{name} grid {res} {k}")
+        ans = qu.oracle_answers(tree, th, coords.reshape(-1, 3), space)
+        same_words(g["sigma"].cpu().numpy().reshape(-1), ans["sigma"], f"{name} grid {res} sigma vs oracle")
+        same_words(g["depth"].cpu().numpy().reshape(-1), ans["depth"], f"{name} grid {res} depth vs oracle")
+    # sigma alone (the occupancy-grid use), no direction
+    g = t.query_grid((0, 0, 0), (1, 1, 1), (64, 64, 64), space="tree")
+    torch.cuda.synchronize()
+    ans = qu.oracle_answers(tree, th, grid_coords((0, 0, 0), (1, 1, 1), (64, 64, 64)).reshape(-1, 3), "tree")
+    assert set(g) == {"sigma"} and (ans["sigma"] > 0).any()
+    same_words(g["sigma"].cpu().numpy().reshape(-1), ans["sigma"], f"{name} 64^3 sigma")
+    t.free_device()
+
+
+# ---- layout independence ---------------------------------------------------------------------------
+def test_outputs_do_not_depend_on_the_lookup_layout(torch_cuda):
+    from volrend_amd import api
+    tree = common.small_scene(depth=7, basis_dim=4, seed=1201)
+    pts = np.concatenate([qu.point_set(tree, 60_000, 700), special_points(tree, 701)])
+    dirs = direction_set(pts.shape[0], 702)
+    th = ob.TreeHandle(tree)
+    ans = qu.oracle_answers(tree, th, pts, "tree")
+    assert set(np.unique(ans["depth"]).tolist()) == set(np.unique(qu.leaf_boxes(tree)[2]).tolist())
+    rgb = qu.recompose_rgb(tree, th, ans["coeffs"], dirs)
+    seen = set()
+    try:
+        for top, brick, blocked in [(0, 3, -1), (1, 3, 0), (2, 2, 0), (3, 3, 0), (4, 1, 0), (6, 3, 0), (8, 3, 0),
+                                    (2, 3, 1), (4, 3, 1), (6, 3, 1), (2, 4, 1)]:
+            api.set_tuning(top_levels=top, brick_levels=brick, brick_blocked=blocked)
+            t = api.N3Tree.from_synth(tree)
+            info = t.info()
+            seen.add((info["top_levels"], info["brick_levels"], info["brick_blocked"]))
+            got = gpu_query(torch_cuda, t, pts, dirs, want=("sigma", "depth", "local", "coeffs", "rgb"))
+            what = f"top {top} brick {brick} blocked {blocked}"
+            for k in ("sigma", "depth", "local", "coeffs"):
+                same_words(got[k], ans[k], f"{what} {k}")
+            same_words(got["rgb"], rgb, f"{what} rgb")
+            t.free_device()
+    finally:
+        api.set_tuning(top_levels=0, brick_levels=3, brick_blocked=-1)
+    assert len(seen) >= 8 and any(s[2] for s in seen), seen
+
+
+# ---- large n -----------------------------------------------------------------------------------------
+def numpy_descent(tree, pts):
+    """query_single_from_root (n3tree_query.hpp:13-48) for all points at once, float32 numpy
+    -> (leaf slot int64 [n], depth int32 [n], local float32 [n, 3])."""
+    f32 = np.float32
+    N = tree.N
+    N3 = N ** 3
+    child = tree.child.reshape(-1).astype(np.int64)
+    x = np.ascontiguousarray(pts, f32).copy()
+    with np.errstate(invalid="ignore"):
+        x = np.where(x < qu.HI, x, qu.HI)     # VOLREND_MIN(xyz, 1 - 1e-6f): NaN -> the bound
+        x = np.where(x > 0, x, f32(0))        # VOLREND_MAX(.., 0): -0 -> +0
+    n = x.shape[0]
+    ptr = np.zeros(n, np.int64)
+    leaf = np.full(n, -1, np.int64)
+    depth = np.zeros(n, np.int32)
+    live = np.arange(n)
+    fN = f32(N)
+    level = 0
+    while live.size:
+        xl = x[live] * fN
+        k = np.floor(xl)
+        xl = xl - k
+        x[live] = xl
+        index = (k[:, 0] * fN + k[:, 1]) * fN + k[:, 2]
+        sub = ptr[live] + index.astype(np.int64)
+        skip = child[sub]
+        done = skip == 0
+        leaf[live[done]] = sub[done]
+        depth[live[done]] = level
+        ptr[live[~done]] = ptr[live[~done]] + skip[~done] * N3
+        live = live[~done]
+        level += 1
+    return leaf, depth, x
+
+
+def test_large_n(torch_cuda):
+    torch = torch_cuda
+    from volrend_amd import api
+    tree = common.small_scene(depth=6, basis_dim=4, seed=12)
+    n = 2 ** 22 + 77
+    rng = np.random.default_rng(800)
+    pts = np.concatenate([qu.point_set(tree, n - 4096, 801), special_points(tree, 802)[:4096]]).astype(np.float32)
+    pts = pts[rng.permutation(n)]
+    assert pts.shape == (n, 3)
+    th = ob.TreeHandle(tree)
+    leaf, depth, local = numpy_descent(tree, pts)
+    sub = slice(5, None, 64)                       # the fixed 1-in-64 subset
+    ans = qu.oracle_answers(tree, th, pts[sub], "tree")
+    assert np.array_equal(leaf[sub], ans["leaf"]) and np.array_equal(depth[sub], ans["depth"])
+    same_words(local[sub], ans["local"], "numpy descent vs or_query")
+    rec = qu.records(tree)
+    t = api.N3Tree.from_synth(tree)
+    p = torch.from_numpy(pts).cuda()
+    out = t.query(p, want=("sigma", "depth", "local"), space="tree")
+    torch.cuda.synchronize()
+    same_words(out["sigma"].cpu().numpy(), rec[leaf, -1], "large n sigma")
+    same_words(out["depth"].cpu().numpy(), depth, "large n depth")
+    same_words(out["local"].cpu().numpy(), local, "large n local")
+    del out
+    out = t.query(p, want=("coeffs",), space="tree")
+    torch.cuda.synchronize()
+    same_words(out["coeffs"].cpu().numpy(), rec[leaf, :-1], "large n coeffs")
+    same_words(out["coeffs"].cpu().numpy()[sub], ans["coeffs"], "large n coeffs vs oracle subset")
+    t.free_device()
+
+
+# ---- beside rendering ----------------------------------------------------------------------------------
+def test_queries_beside_render_launches(torch_cuda):
+    torch = torch_cuda
+    from volrend_amd import api
+    tree = common.small_scene(depth=6, basis_dim=9, seed=31)
+    th = ob.TreeHandle(tree)
+    w = h = 64
+    f = w * 1111.111 / 800.0
+    poses = [common.camera_for(pose_idx=i, size=w)[0] for i in (0, 2, 5)]
+    frames_o = [common.oracle_frame(tree, tr, w, h, f, ob.FP_STRICT) for tr in poses]
+    pts = qu.point_set(tree, 50_000, 900)
+    dirs = direction_set(pts.shape[0], 901)
+    ans = qu.oracle_answers(tree, th, pts, "tree")
+    rgb = qu.recompose_rgb(tree, th, ans["coeffs"], dirs)
+    t = api.N3Tree.from_synth(tree)
+    cam = api.Camera(w, h, f, f)
+    sa, sb = torch.cuda.Stream(), torch.cuda.Stream()
+    p, d = torch.from_numpy(pts).cuda(), torch.from_numpy(dirs).cuda()
+    torch.cuda.synchronize()
+    rounds = []
+    for r in range(6):
+        imgs = torch.zeros((len(poses), h, w, 4), dtype=torch.uint8, device="cuda")
+        accs = torch.zeros((len(poses), h, w, 4), dtype=torch.float32, device="cuda")
+        torch.cuda.synchronize()
+        api.launch_renderer_batch(t, cam, poses, api.RenderOptions(), list(imgs), sb, True, accums=list(accs))
+        q = t.query(p, d, want=("sigma", "depth", "local", "coeffs", "rgb"), space="tree", stream=sa)
+        g = t.query_grid((0, 0, 0), (1, 1, 1), (32, 32, 32), want=("sigma",), space="tree", stream=sa)
+        api.launch_renderer_batch(t, cam, poses, api.RenderOptions(), list(imgs), sb, True, accums=list(accs))
+        rounds.append((imgs, accs, q, g))
+    sa.synchronize()
+    sb.synchronize()
+    torch.cuda.synchronize()
+    assert t.status() == 0
+    grid_ans = qu.oracle_answers(tree, th, grid_coords((0, 0, 0), (1, 1, 1), (32, 32, 32)).reshape(-1, 3), "tree")
+    for r, (imgs, accs, q, g) in enumerate(rounds):
+        for i, (rgba_o, acc_o, _) in enumerate(frames_o):
+            assert np.array_equal(imgs[i].cpu().numpy(), rgba_o), (r, i)
+            assert np.array_equal(accs[i].cpu().numpy().view(np.uint32), acc_o.view(np.uint32)), (r, i)
+        for k in ("sigma", "depth", "local", "coeffs"):
+            same_words(q[k].cpu().numpy(), ans[k], f"round {r} {k}")
+        same_words(q["rgb"].cpu().numpy(), rgb, f"round {r} rgb")
+        same_words(g["sigma"].cpu().numpy().reshape(-1), grid_ans["sigma"], f"round {r} grid")
+    t.free_device()
+
+
+# ---- errors, wrappers, the old call ------------------------------------------------------------------------
+def test_error_codes_on_a_live_tree(torch_cuda):
+    torch = torch_cuda
+    from volrend_amd import _abi, api
+    L = _abi.lib()
+    t = api.N3Tree.from_synth(common.small_scene(depth=4, basis_dim=4, seed=41))
+    sg = api.N3Tree.from_synth(common.small_scene(depth=4, basis_dim=7, fmt="SG", seed=42))
+    n = 100
+    pts = torch.rand((n, 3), device="cuda") - 0.5
+    buf = torch.full((n, 3), -7.0, device="cuda")
+    sig = torch.full((n,), -7.0, device="cuda")
+
+    def out(**kw):
+        o = _abi.VrQueryOut()
+        for k, v in kw.items():
+            setattr(o, k, v.data_ptr())
+        return o
+
+    f3 = (C.c_float * 3)
+    lo, hi, d = f3(0, 0, 0), f3(1, 1, 1), f3(0, 0, 1)
+
+    def grid(tree, res, direction, o, space=0):
+        return L.vr_query_grid(tree.handle, C.byref(lo), C.byref(hi), C.byref((C.c_int32 * 3)(*res)),
+                               direction, space, C.byref(o) if o is not None else None, None)
+
+    INVALID, UNSUPPORTED = 1, 5
+    o_sigma, o_rgb, o_none = out(sigma=sig), out(rgb=buf), out()
+    assert L.vr_query_points(t.handle, n, pts.data_ptr(), None, 0, C.byref(o_rgb), None) == INVALID
+    assert b"directions" in L.vr_last_error()
+    assert L.vr_query_points(t.handle, n, pts.data_ptr(), None, 0, C.byref(o_none), None) == INVALID
+    assert L.vr_query_points(t.handle, n, pts.data_ptr(), None, 0, None, None) == INVALID
+    assert L.vr_query_points(t.handle, n, None, None, 0, C.byref(o_sigma), None) == INVALID
+    assert L.vr_query_points(t.handle, -1, pts.data_ptr(), None, 0, C.byref(o_sigma), None) == INVALID
+    assert L.vr_query_points(t.handle, n, pts.data_ptr(), None, 2, C.byref(o_sigma), None) == INVALID
+    assert L.vr_query_points(sg.handle, n, pts.data_ptr(), pts.data_ptr(), 0, C.byref(o_rgb), None) == UNSUPPORTED
+    assert grid(t, (4, 0, 4), None, o_sigma) == INVALID
+    assert grid(t, (4, 4, -1), None, o_sigma) == INVALID
+    assert grid(t, (1 << 14, 1 << 14, (1 << 12) + 1), None, o_sigma) == INVALID     # > 2^40 cells
+    assert grid(t, (2 ** 31 - 1, 2 ** 31 - 1, 2 ** 31 - 1), None, o_sigma) == INVALID
+    assert grid(t, (4, 4, 4), None, o_rgb) == INVALID
+    assert grid(t, (4, 4, 4), None, o_none) == INVALID
+    assert grid(t, (4, 4, 4), None, None) == INVALID
+    assert grid(t, (4, 4, 4), None, o_sigma, space=-1) == INVALID
+    assert grid(sg, (4, 4, 4), C.byref(d), o_rgb) == UNSUPPORTED
+    torch.cuda.synchronize()
+    assert (buf == -7.0).all() and (sig == -7.0).all(), "a refused call wrote to an output"
+    # n == 0 is fine and launches nothing; everything but rgb works on an SG tree
+    assert L.vr_query_points(t.handle, 0, pts.data_ptr(), None, 0, C.byref(o_sigma), None) == 0
+    torch.cuda.synchronize()
+    assert (sig == -7.0).all()
+    empty = t.query(torch.zeros((0, 3), device="cuda"), want=("sigma", "coeffs"))
+    assert empty["sigma"].shape == (0,) and empty["coeffs"].shape == (0, 12)
+    assert L.vr_query_points(sg.handle, n, pts.data_ptr(), None, 0, C.byref(o_sigma), None) == 0
+    torch.cuda.synchronize()
+    assert (sig != -7.0).all()
+    # the Python wrappers refuse bad tensors with ValueError before any C call
+    for bad in (pts.double(), pts.cpu(), pts[:, :2], pts.t(), torch.rand((3, n), device="cuda").t(), pts.reshape(-1)):
+        with pytest.raises(ValueError):
+            t.query(bad)
+    with pytest.raises(ValueError):
+        t.query(pts, pts[:50].contiguous(), want=("rgb",))
+    with pytest.raises(ValueError):
+        t.query(pts, want=("rgb",))
+    with pytest.raises(ValueError):
+        t.query(pts, want=("alpha",))
+    with pytest.raises(ValueError):
+        t.query(pts, want=())
+    with pytest.raises(ValueError):
+        t.query(pts, space="ndc")
+    with pytest.raises(ValueError):
+        sg.query(pts, pts, want=("rgb",))
+    for res in ((4, 0, 4), (4, 4), (1 << 14, 1 << 14, (1 << 12) + 1), (2.5, 4, 4)):
+        with pytest.raises(ValueError):
+            t.query_grid((0, 0, 0), (1, 1, 1), res)
+    with pytest.raises(ValueError):
+        t.query_grid((0, 0), (1, 1, 1), (4, 4, 4))
+    with pytest.raises(ValueError):
+        t.query_grid((0, 0, 0), (1, 1, 1), (4, 4, 4), want=("rgb",))
+    t.free_device()
+    sg.free_device()
+
+
+@pytest.mark.parametrize("fmt,basis_dim", [("SH", 16), ("SH", 25), ("RGBA", 0), ("SG", 4)])
+def test_coeffs_agree_with_vr_probe_coeffs(torch_cuda, fmt, basis_dim):
+    torch = torch_cuda
+    from volrend_amd import _abi, api
+    tree = common.small_scene(depth=6, basis_dim=basis_dim, fmt=fmt, seed=189)
+    t = api.N3Tree.from_synth(tree)
+    rng = np.random.default_rng(17)
+    pts = np.array([(0.0, 0.0, 0.0), (0.37, -0.41, 0.12)] + [tuple(rng.uniform(-0.6, 0.6, 3)) for _ in range(30)],
+                   np.float32)
+    k = tree.data_dim - 1
+    nonzero = 0
+    for p in pts:
+        old = torch.full((k,), -7.0, dtype=torch.float32, device="cuda")
+        o = api.RenderOptions(enable_probe=True, probe=tuple(float(v) for v in p)).to_c()
+        _abi.check(_abi.lib().vr_probe_coeffs(t.handle, C.byref(o), old.data_ptr(), None))
+        new = t.query(torch.from_numpy(p[None, :].copy()).cuda(), want=("coeffs",), space="world")["coeffs"]
+        torch.cuda.synchronize()
+        same_words(new.cpu().numpy()[0], old.cpu().numpy(), f"{fmt}{basis_dim} {p}")
+        nonzero += int((old != 0).any())
+    assert nonzero > 3
+    t.free_device()
+
+
+@pytest.mark.parametrize("basis_dim", [4, 16, 9])
+def test_coeffs_into_a_buffer_that_is_only_4_byte_aligned(torch_cuda, basis_dim):
+    """SH4 / SH16 records leave as 16-byte stores when the output allows it: a caller's buffer that is
+    only float-aligned gets the same words."""
+    torch = torch_cuda
+    from volrend_amd import _abi, api
+    tree = common.small_scene(depth=5, basis_dim=basis_dim, seed=61)
+    th = ob.TreeHandle(tree)
+    n, k = 10_007, tree.data_dim - 1
+    pts = qu.point_set(tree, n, 62)
+    ans = qu.oracle_answers(tree, th, pts, "tree")
+    t = api.N3Tree.from_synth(tree)
+    p = torch.from_numpy(pts).cuda()
+    for shift in (1, 2, 3, 0):
+        buf = torch.full((n * k + 8,), -7.0, device="cuda")
+        view = buf[shift:shift + n * k]
+        assert view.data_ptr() % 16 == (4 * shift) % 16
+        o = _abi.VrQueryOut()
+        o.coeffs = view.data_ptr()
+        _abi.check(_abi.lib().vr_query_points(t.handle, n, p.data_ptr(), None, _abi.SPACE_TREE, C.byref(o), None))
+        torch.cuda.synchronize()
+        same_words(view.cpu().numpy().reshape(n, k), ans["coeffs"], f"SH{basis_dim} shift {shift}")
+        rest = torch.cat([buf[:shift], buf[shift + n * k:]])
+        assert (rest == -7.0).all(), "wrote outside the output"
+    t.free_device()
+
+
+def test_query_runs_on_the_trees_device_and_leaves_the_current_one(torch_cuda):
+    torch = torch_cuda
+    from volrend_amd import api
+    tree = common.small_scene(depth=4, basis_dim=4, seed=51)
+    t = api.N3Tree.from_synth(tree)
+    before = torch.cuda.current_device()
+    out = t.query(torch.zeros((10, 3), device=f"cuda:{t.info()['device']}"), want=("sigma", "depth"))
+    torch.cuda.synchronize()
+    assert torch.cuda.current_device() == before
+    assert out["sigma"].device.index == t.info()["device"] and out["depth"].dtype == torch.int32
+    t.free_device()

@@ -20,6 +20,8 @@ FORMATS = {"RGBA": FORMAT_RGBA, "SH": FORMAT_SH, "SG": FORMAT_SG, "ASG": FORMAT_
 FP_STRICT, FP_FMA = 0, 1
 QUERY_LOOKUP, QUERY_DESCENT = 0, 1  # VrTreeInfo.query_mode
 LAYOUT_FRAME, LAYOUT_COMPACT = 0, 1
+SPACE_WORLD, SPACE_TREE = 0, 1  # vr_query_points / vr_query_grid
+SPACES = {"world": SPACE_WORLD, "tree": SPACE_TREE}
 MAX_BASIS = 25
 
 
@@ -64,6 +66,11 @@ class VrFrame(C.Structure):
                 ("tile_w", C.c_int32), ("tile_h", C.c_int32), ("rank", C.c_int32),
                 ("world", C.c_int32), ("fp_mode", C.c_int32), ("reserved", C.c_int32),
                 ("counters", C.c_void_p)]
+
+
+class VrQueryOut(C.Structure):
+    _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
+                ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
 
 
 ABI_VERSION = 3  # VR_ABI_VERSION of include/volrend_hip.h
@@ -114,6 +121,11 @@ PROTOTYPES = {
                                           C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                           C.c_int, C.c_void_p]),
     "vr_probe_coeffs": (C.c_int, [C.c_void_p, C.POINTER(VrRenderOptions), C.c_void_p, C.c_void_p]),
+    "vr_query_points": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int,
+                                  C.POINTER(VrQueryOut), C.c_void_p]),
+    "vr_query_grid": (C.c_int, [C.c_void_p, C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 3),
+                                C.POINTER(C.c_int32 * 3), C.POINTER(C.c_float * 3), C.c_int,
+                                C.POINTER(VrQueryOut), C.c_void_p]),
     "vr_read_back": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_void_p]),
     "vr_stream_sync": (C.c_int, [C.c_void_p]),
 }

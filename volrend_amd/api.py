@@ -371,6 +371,97 @@ class N3Tree:
             _abi.check(_abi.lib().vr_tree_status(self.handle, C.byref(out), 1 if reset else 0))
         return int(out.value)
 
+    # ---- bulk point queries (vr_query_points / vr_query_grid) --------------
+    def _query_outputs(self, want, shape, have_dirs: bool, space: str):
+        """Checks ``want`` / ``space`` and allocates the outputs [*shape(, k)] on the tree's device
+        -> (dict of tensors, VrQueryOut, space code).  Raises ValueError before any C call."""
+        import torch
+        want = (want,) if isinstance(want, str) else tuple(want)
+        widths = {"sigma": 0, "depth": 0, "local": 3, "coeffs": self.data_dim - 1, "rgb": 3}
+        if not want or any(w not in widths for w in want) or len(set(want)) != len(want):
+            raise ValueError(f"want must name at least one of {sorted(widths)}, each once: {want!r}")
+        if space not in _abi.SPACES:
+            raise ValueError(f"space must be 'world' or 'tree', not {space!r}")
+        if "rgb" in want and not have_dirs:
+            raise ValueError("rgb needs directions")
+        if "rgb" in want and self.data_format[0] in ("SG", "ASG"):
+            raise ValueError("rgb of SG / ASG trees is not supported by the point queries")
+        dev = torch.device("cuda", self.info()["device"])
+        res, out = {}, _abi.VrQueryOut()
+        for w in want:
+            k = widths[w]
+            res[w] = torch.empty(tuple(shape) + ((k,) if k else ()), device=dev,
+                                 dtype=torch.int32 if w == "depth" else torch.float32)
+            setattr(out, w, res[w].data_ptr())
+        return res, out, _abi.SPACES[space]
+
+    def _query_input(self, x, what: str, n=None):
+        """A [n, 3] float32 contiguous tensor on the tree's device, or a raw pointer with ``n``
+        given -> (pointer, n)."""
+        if isinstance(x, int):
+            if n is None:
+                raise ValueError(f"{what} is a raw pointer: pass n")
+            return x, int(n)
+        import torch
+        if not isinstance(x, torch.Tensor):
+            raise ValueError(f"{what} must be a torch tensor or a raw pointer, got {type(x)}")
+        if x.dtype != torch.float32:
+            raise ValueError(f"{what} must be float32, not {x.dtype}")
+        if x.dim() != 2 or x.shape[1] != 3 or (n is not None and x.shape[0] != n):
+            raise ValueError(f"{what} must have shape [{'n' if n is None else n}, 3], not {tuple(x.shape)}")
+        if not x.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        dev = self.info()["device"]
+        if not x.is_cuda or x.device.index != dev:
+            raise ValueError(f"{what} must be on the tree's device cuda:{dev}, not {x.device}")
+        return int(x.data_ptr()), int(x.shape[0])
+
+    def query(self, points, dirs=None, *, want=("sigma",), space: str = "world", stream=None, n=None) -> dict:
+        """What the tree holds at ``points`` [n, 3] (float32, contiguous, on the tree's device; or a
+        raw device pointer with ``n``) -- vr_query_points, one launch, enqueued on ``stream``.
+
+        ``want``: any of "sigma" [n], "depth" [n] int32, "local" [n, 3], "coeffs" [n, data_dim - 1],
+        "rgb" [n, 3] (needs ``dirs`` [n, 3]; evaluated at the direction AS GIVEN, not normalised;
+        strict model).  ``space``: "world" (offset + scale * x is applied) or "tree".  Returns a dict
+        of torch tensors on the tree's device."""
+        handle = self.handle
+        xyz, n = self._query_input(points, "points", n)
+        if n < 0:
+            raise ValueError("n is negative")
+        d = None if dirs is None else self._query_input(dirs, "dirs", n)[0]
+        res, out, sp = self._query_outputs(want, (n,), d is not None, space)
+        if n == 0:  # (empty tensors have no address to pass)
+            return res
+        _abi.check(_abi.lib().vr_query_points(handle, n, xyz, d, sp, C.byref(out), _stream_ptr(stream)))
+        return res
+
+    def query_grid(self, lo, hi, res, dir=None, *, want=("sigma",), space: str = "world", stream=None) -> dict:
+        """The same at the res[0] x res[1] x res[2] cell centres of the box ``lo``..``hi``, generated
+        on the device (vr_query_grid): cell (i, j, k) sits at lo + (i + 0.5) * ((hi - lo) / res) per
+        axis, in float32.  ``dir``: one direction for all cells (needed for "rgb").  Returns tensors
+        shaped [res0, res1, res2(, k)]."""
+        handle = self.handle
+        vals = []
+        for name, v, dt in (("lo", lo, np.float32), ("hi", hi, np.float32), ("res", res, np.int64),
+                            ("dir", dir, np.float32)):
+            if v is None and name == "dir":
+                vals.append(None)
+                continue
+            a = np.asarray(v)
+            if a.shape != (3,) or (name == "res" and not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError(f"{name} must be 3 {'integers' if name == 'res' else 'numbers'}")
+            vals.append(a.astype(dt))
+        lo_a, hi_a, res_a, dir_a = vals
+        if (res_a < 1).any() or (res_a > 2 ** 31 - 1).any() or int(res_a.prod(dtype=object)) > 2 ** 40:
+            raise ValueError(f"res must be positive with at most 2^40 cells in all: {tuple(res_a)}")
+        out_t, out, sp = self._query_outputs(want, tuple(int(r) for r in res_a), dir_a is not None, space)
+        c_lo, c_hi = (C.c_float * 3)(*map(float, lo_a)), (C.c_float * 3)(*map(float, hi_a))
+        c_res = (C.c_int32 * 3)(*[int(r) for r in res_a])
+        c_dir = None if dir_a is None else C.byref((C.c_float * 3)(*map(float, dir_a)))
+        _abi.check(_abi.lib().vr_query_grid(handle, C.byref(c_lo), C.byref(c_hi), C.byref(c_res), c_dir,
+                                            sp, C.byref(out), _stream_ptr(stream)))
+        return out_t
+
     def info(self) -> dict:
         i = _abi.VrTreeInfo()
         _abi.check(_abi.lib().vr_tree_info(self._handle, C.byref(i)))
