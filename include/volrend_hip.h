@@ -250,6 +250,44 @@ int vr_render(vr_tree_t tree, const VrCamera* cam, const VrRenderOptions* opt,
 #define VR_MAX_BATCH 512
 int vr_render_batch(vr_tree_t tree, int n_frames, const VrCamera* cams,
                     const VrRenderOptions* opt, const VrFrame* frames, void* stream);
+/* ---- AOV planes: depth and transmittance from the colour launch ---------- */
+/* vr_render_batch that ALSO writes, per pixel, two float planes ("AOV" = an extra per-pixel plane
+ * of a render launch) from the same march -- no second pass.  With t, weight, light_intensity and
+ * delta_scale exactly as trace_ray (rt_core.cuh:66-196) forms them, in the launch's FP model:
+ *   D = sum over the samples with sigma > sigma_thresh, in order, of weight * t: D = weight * t + D
+ *       (STRICT: two roundings; FMA: one fused operation) -- what the reference's depth mode holds in
+ *       out[0] BEFORE its min(. * 0.3f, 1) and before the early-stop rescale.  t is the distance
+ *       along the normalised tree-space direction.
+ *   T = light_intensity when the ray leaves the loop, through t >= tmax or through stop_thresh (it
+ *       is NOT forced to 0 or 1 at an early stop).
+ * A ray that takes no sample -- it misses render_bbox, a mesh depth in VrFrame.depth (offscreen = 0)
+ * cuts it off in front of the box, or the tree has N <= 0 -- gives D = 0, T = 1.
+ *   depth plane          VR_DEPTH_TREE : D
+ *                        VR_DEPTH_WORLD: D * delta_scale (one more rounding): the length the
+ *                        attenuation uses (rt_core.cuh:119).  For an NDC tree (ndc_width > 0) that is a
+ *                        length in NDC space, not in the scene's world space.
+ *   transmittance plane  T
+ * The expected depth of what the ray hit is depth / (1 - T) (undefined where T == 1); the library
+ * does not form it.
+ * Colour, accum and everything else are exactly what vr_render_batch produces for the same
+ * arguments, and the contract is the same: enqueue only, launch slots, one frame size / intrinsics /
+ * layout / sharding / fp_mode (and one AOV pitch) per launch, <= VR_MAX_BATCH frames, vr_reserve*
+ * covers it (the launch's table of plane pointers lives in the launch slot from upload on).
+ * The planes are ALWAYS addressed in frame position, plane + y * pitch + 4 * x, whatever
+ * VrFrame.layout says; a tile-sharded rank writes only the pixels of its own tiles.
+ * VR_ERR_INVALID_ARGUMENT: everything vr_render_batch refuses, NULL aovs, an entry with both planes
+ * NULL, unknown depth_units, a pitch below width * 4 or not a multiple of 4 (or differing within the
+ * batch).  VR_ERR_UNSUPPORTED: opt->render_depth (the depth visualisation already is that launch),
+ * opt->enable_probe (pixels under the probe disc are not traced), a frame with counters (the
+ * instrumented flavour).  All checked before any device work. */
+enum { VR_DEPTH_TREE = 0, VR_DEPTH_WORLD = 1 };
+typedef struct VrAov {        /* device pointers of ONE frame; NULL = not wanted, at least one non-NULL */
+    float*  depth;            /* [height] rows of width floats */
+    float*  transmittance;
+    int64_t pitch;            /* bytes per row of both planes; 0 = width*4 */
+} VrAov;
+int vr_render_aov(vr_tree_t tree, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                  const VrFrame* frames, const VrAov* aovs, int depth_units, void* stream);
 /* Pre-allocates the ray buffers of two launch slots for batches of up to n_frames whole
  * width x height frames (128-228 bytes per ray): a render loop on one stream lives in one slot,
  * two alternating streams in two, so no later vr_render / vr_render_batch of that size (or

@@ -22,6 +22,8 @@ QUERY_LOOKUP, QUERY_DESCENT = 0, 1  # VrTreeInfo.query_mode
 LAYOUT_FRAME, LAYOUT_COMPACT = 0, 1
 SPACE_WORLD, SPACE_TREE = 0, 1  # vr_query_points / vr_query_grid
 SPACES = {"world": SPACE_WORLD, "tree": SPACE_TREE}
+DEPTH_TREE, DEPTH_WORLD = 0, 1  # vr_render_aov depth_units
+DEPTH_UNITS = {"tree": DEPTH_TREE, "world": DEPTH_WORLD}
 MAX_BASIS = 25
 
 
@@ -68,6 +70,10 @@ class VrFrame(C.Structure):
                 ("counters", C.c_void_p)]
 
 
+class VrAov(C.Structure):
+    _fields_ = [("depth", C.c_void_p), ("transmittance", C.c_void_p), ("pitch", C.c_int64)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -103,6 +109,8 @@ PROTOTYPES = {
                             C.POINTER(VrFrame), C.c_void_p]),
     "vr_render_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera),
                                   C.POINTER(VrRenderOptions), C.POINTER(VrFrame), C.c_void_p]),
+    "vr_render_aov": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
+                                C.POINTER(VrFrame), C.POINTER(VrAov), C.c_int, C.c_void_p]),
     "vr_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "vr_reserve_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int]),

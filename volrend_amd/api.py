@@ -560,15 +560,48 @@ class TileShard:
     compact: bool = False
 
 
+@dataclass
+class AovPlanes:
+    """The extra float planes of ONE frame of an AOV launch (``vr_render_aov``): device float32
+    [H,W] tensors or raw pointers, ``None`` = not wanted (at least one of the two); ``pitch``: bytes
+    per row of both, 0 = width * 4.  Always addressed in frame position, whatever the shard's layout.
+    ``depth`` holds D = sum of weight * t (``depth_units="tree"``) or D * delta_scale (``"world"``),
+    ``transmittance`` the light the ray left the loop with; the expected depth of what a ray hit is
+    ``depth / (1 - transmittance)``."""
+    depth: object = None
+    transmittance: object = None
+    pitch: int = 0
+
+    def to_c(self) -> "_abi.VrAov":
+        a = _abi.VrAov()
+        a.depth, a.transmittance, a.pitch = _ptr(self.depth), _ptr(self.transmittance), int(self.pitch)
+        return a
+
+
+def _aov_c(aov) -> "_abi.VrAov":
+    """AovPlanes, or a (depth, transmittance[, pitch]) tuple."""
+    return (aov if isinstance(aov, AovPlanes) else AovPlanes(*aov)).to_c()
+
+
+def _depth_units(depth_units) -> int:
+    if isinstance(depth_units, str):
+        if depth_units not in _abi.DEPTH_UNITS:
+            raise ValueError(f"depth_units must be one of {sorted(_abi.DEPTH_UNITS)}, got {depth_units!r}")
+        return _abi.DEPTH_UNITS[depth_units]
+    return int(depth_units)
+
+
 def launch_renderer(tree: N3Tree, cam: Camera, options: RenderOptions, image, depth=None,
                     stream=None, offscreen: bool = False, *, accum=None, pitch: int = 0,
                     shard: TileShard | None = None, fp_mode: int = _abi.FP_STRICT,
-                    counters=None) -> None:
+                    counters=None, aov=None, depth_units="tree") -> None:
     """Enqueue one frame on ``stream`` (asynchronous, like the reference).
 
     ``image``: device RGBA8 buffer (``torch.uint8`` [H,W,4] or a raw pointer);
     ``depth``: device R32F mesh depth or None; ``offscreen=True`` is the
     ``volrend_headless`` mode (background_brightness composite).
+    ``aov``: ``AovPlanes`` (or a (depth, transmittance[, pitch]) tuple): the same launch also writes
+    the depth / transmittance planes (``vr_render_aov``), ``depth_units`` "tree" or "world".
     """
     f = _abi.VrFrame()
     L = _abi.lib()
@@ -585,6 +618,11 @@ def launch_renderer(tree: N3Tree, cam: Camera, options: RenderOptions, image, de
         f.layout = _abi.LAYOUT_COMPACT if shard.compact else _abi.LAYOUT_FRAME
     c = cam.to_c()
     o = options.to_c()
+    if aov is not None:
+        a = _aov_c(aov)
+        _abi.check(L.vr_render_aov(tree.handle, 1, C.byref(c), C.byref(o), C.byref(f), C.byref(a),
+                                   _depth_units(depth_units), _stream_ptr(stream)))
+        return
     _abi.check(L.vr_render(tree.handle, C.byref(c), C.byref(o), C.byref(f), _stream_ptr(stream)))
 
 
@@ -596,15 +634,24 @@ class PreparedBatch:
 
     def __init__(self, tree: N3Tree, cam: Camera, transforms, options: RenderOptions, images,
                  offscreen: bool = True, *, accums=None, depths=None, pitch: int = 0,
-                 shard: TileShard | None = None, fp_mode: int = _abi.FP_STRICT, counters=None):
+                 shard: TileShard | None = None, fp_mode: int = _abi.FP_STRICT, counters=None,
+                 aov=None, depth_units="tree"):
         n = len(transforms)
         if n != len(images):
             raise ValueError("one image per pose")
+        if aov is not None and len(aov) != n:
+            raise ValueError("one AovPlanes per pose")
         L = _abi.lib()
         self.tree, self.n = tree, n
         self.cams = (_abi.VrCamera * n)()
         self.frames = (_abi.VrFrame * n)()
-        self._keep = (images, accums, depths, counters)  # the buffers must outlive the launch
+        self._keep = (images, accums, depths, counters, aov)  # the buffers must outlive the launch
+        # aov: one AovPlanes per pose -> launch() is vr_render_aov instead of vr_render_batch
+        self.aovs, self.depth_units = None, _depth_units(depth_units)
+        if aov is not None:
+            self.aovs = (_abi.VrAov * n)()
+            for i in range(n):
+                self.aovs[i] = _aov_c(aov[i])
         for i in range(n):
             cam.transform = np.asarray(transforms[i], dtype=np.float32)
             self.cams[i] = cam.to_c()
@@ -624,6 +671,10 @@ class PreparedBatch:
         self.opts = options.to_c()
 
     def launch(self, stream=None) -> None:
+        if self.aovs is not None:
+            _abi.check(_abi.lib().vr_render_aov(self.tree.handle, self.n, self.cams, C.byref(self.opts),
+                                                self.frames, self.aovs, self.depth_units, _stream_ptr(stream)))
+            return
         _abi.check(_abi.lib().vr_render_batch(self.tree.handle, self.n, self.cams,
                                               C.byref(self.opts), self.frames, _stream_ptr(stream)))
 
@@ -631,14 +682,17 @@ class PreparedBatch:
 def launch_renderer_batch(tree: N3Tree, cam: Camera, transforms, options: RenderOptions, images,
                           stream=None, offscreen: bool = True, *, accums=None, depths=None,
                           pitch: int = 0, shard: TileShard | None = None,
-                          fp_mode: int = _abi.FP_STRICT, counters=None) -> None:
+                          fp_mode: int = _abi.FP_STRICT, counters=None, aov=None,
+                          depth_units="tree") -> None:
     """Several poses in ONE launch: ``transforms[i]`` (12-float c2w) -> ``images[i]``.
+    ``aov``: one ``AovPlanes`` per pose -- the launch also writes their planes (``vr_render_aov``).
 
     The pose loop of ``volrend_headless`` (main_headless.cpp:207-225) with the
     poses known up front; intrinsics / options / sharding are shared.  ``counters``:
     optional list of device int64[7] tensors (instrumented flavour)."""
     PreparedBatch(tree, cam, transforms, options, images, offscreen, accums=accums, depths=depths,
-                  pitch=pitch, shard=shard, fp_mode=fp_mode, counters=counters).launch(stream)
+                  pitch=pitch, shard=shard, fp_mode=fp_mode, counters=counters, aov=aov,
+                  depth_units=depth_units).launch(stream)
 
 
 def set_tuning(**kw) -> None:

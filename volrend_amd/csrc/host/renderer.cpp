@@ -1,7 +1,8 @@
-// renderer.cpp -- volrend::launch_renderer over vr_render / vr_render_batch.
+// renderer.cpp -- volrend::launch_renderer[_aov] over vr_render / vr_render_batch / vr_render_aov.
 #include <stdexcept>
 #include <string>
 
+#include "volrend/aov.hpp"
 #include "volrend/internal/check.hpp"
 #include "volrend/renderer_kernel.hpp"
 
@@ -72,6 +73,54 @@ void launch_renderer_batch(const N3Tree& tree, const Camera& cam,
             frames[i].offscreen = offscreen ? 1 : 0;
         }
         internal::vr_check(vr_render_batch(tree.device, n, cams, &o, frames, stream), "vr_render_batch");
+    }
+}
+
+namespace {
+VrAov to_c(const AovPlanes& a) {
+    VrAov c;
+    c.depth = a.depth;
+    c.transmittance = a.transmittance;
+    c.pitch = a.pitch;
+    return c;
+}
+}  // namespace
+
+void launch_renderer_aov(const N3Tree& tree, const Camera& cam, const RenderOptions& options,
+                         void* image_rgba8_dev, const float* depth_dev, const AovPlanes& aov,
+                         DepthUnits depth_units, void* stream, bool offscreen) {
+    const VrCamera c = to_c(cam, glm::value_ptr(cam.transform));
+    const VrRenderOptions o = to_c(options);
+    const VrAov a = to_c(aov);
+    VrFrame f;
+    vr_default_frame(&f);
+    f.rgba = image_rgba8_dev;
+    f.depth = depth_dev;
+    f.offscreen = offscreen ? 1 : 0;
+    internal::vr_check(vr_render_aov(tree.device, 1, &c, &o, &f, &a, (int)depth_units, stream), "vr_render_aov");
+}
+
+void launch_renderer_aov_batch(const N3Tree& tree, const Camera& cam,
+                               const std::vector<const float*>& transforms, const RenderOptions& options,
+                               const std::vector<void*>& images, const std::vector<AovPlanes>& aovs,
+                               DepthUnits depth_units, void* stream, bool offscreen) {
+    if (transforms.size() != images.size() || transforms.size() != aovs.size())
+        throw std::invalid_argument("launch_renderer_aov_batch: one image and one AovPlanes per pose");
+    const VrRenderOptions o = to_c(options);
+    for (size_t first = 0; first < transforms.size(); first += VR_MAX_BATCH) {
+        const int n = (int)std::min<size_t>(VR_MAX_BATCH, transforms.size() - first);
+        VrCamera cams[VR_MAX_BATCH];
+        VrFrame frames[VR_MAX_BATCH];
+        std::vector<VrAov> planes((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            cams[i] = to_c(cam, transforms[first + i]);
+            vr_default_frame(&frames[i]);
+            frames[i].rgba = images[first + i];
+            frames[i].offscreen = offscreen ? 1 : 0;
+            planes[(size_t)i] = to_c(aovs[first + i]);
+        }
+        internal::vr_check(vr_render_aov(tree.device, n, cams, &o, frames, planes.data(), (int)depth_units, stream),
+                           "vr_render_aov");
     }
 }
 

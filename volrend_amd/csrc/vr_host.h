@@ -95,6 +95,7 @@ struct VrTreeOpaque : TreeShape {
     DeviceBuffer probe_buf;      // kLaunchSlots x data_dim floats: the lumisphere at opt.probe
     DeviceBuffer slot_frames;    // kLaunchSlots x kMaxBatch vr::FrameDesc
     DeviceBuffer slot_heads;     // kLaunchSlots x vr::kSlotWords uint32_t
+    DeviceBuffer slot_aovs;      // kLaunchSlots x kMaxBatch vr::AovDesc: the plane pointers of an AOV launch
     LaunchSlot slots[kLaunchSlots];
     unsigned launch_seq = 0;
     std::mutex launch_mutex;  // slot bookkeeping + enqueue order of one launch; guards `tn`

@@ -188,7 +188,30 @@ struct KParams {
     uint32_t* touch[4];
 };
 
+// ---------------------------------------------------------------------------
+// AOV launches (vr_render_aov): extra per-pixel float planes next to the colour.  The AOV kernel
+// flavours take KParams unchanged plus this second argument; the per-frame plane pointers sit in a
+// table of their own in the launch slot (entry i = frame i), written by prepare_aov_kernel.
+// ---------------------------------------------------------------------------
+struct AovDesc {
+    float* depth;          // NULL = not wanted
+    float* transmittance;  // NULL = not wanted
+};
+struct AovParams {
+    const AovDesc* planes;  // device table, n_frames entries
+    int64_t pitch;          // bytes per row of both planes (always frame position, whatever the layout)
+    int32_t depth_world;    // VR_DEPTH_WORLD: the depth plane holds D * delta_scale
+};
+struct AovTable {
+    int32_t first;  // index of f[0] in the device table
+    int32_t n;
+    AovDesc f[kTableChunk];
+};
+
 // vr_render.hip: the kernels of a launch
+hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream);
+hipError_t launch_render_aov(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
+                             int gen_waves, hipStream_t stream);
 hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream);
 hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
                          hipStream_t stream);

@@ -275,10 +275,41 @@ int acquire_slot(VrTreeOpaque* t, std::unique_lock<std::mutex>& guard, hipStream
     return VR_OK;
 }
 
+// What vr_render_aov adds to the checks of a batch; leaves pitch and depth_world in `a`.
+int validate_aov(int n_frames, const VrCamera* cams, const VrRenderOptions* opt, const VrFrame* frames,
+                 const VrAov* aovs, int depth_units, vr::AovParams& a) {
+    if (!aovs) return fail(VR_ERR_INVALID_ARGUMENT, "aovs is NULL");
+    if (depth_units != VR_DEPTH_TREE && depth_units != VR_DEPTH_WORLD)
+        return fail(VR_ERR_INVALID_ARGUMENT, "unknown depth_units %d", depth_units);
+    const int64_t row = (int64_t)cams[0].width * 4;
+    const int64_t pitch = aovs[0].pitch ? aovs[0].pitch : row;
+    for (int i = 0; i < n_frames; ++i) {
+        if (!aovs[i].depth && !aovs[i].transmittance)
+            return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: both AOV planes are NULL", i);
+        const int64_t pi = aovs[i].pitch ? aovs[i].pitch : row;
+        if (pi < row || (pi & 3))
+            return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: AOV pitch %lld unusable for rows of %d floats", i,
+                        (long long)aovs[i].pitch, cams[0].width);
+        if (pi != pitch) return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: AOV pitch differs within the batch", i);
+    }
+    if (opt->render_depth)
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_aov with render_depth: the depth visualisation already is that launch");
+    if (opt->enable_probe)
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_aov with enable_probe: pixels under the probe disc are not traced");
+    for (int i = 0; i < n_frames; ++i)
+        if (frames[i].counters)
+            return fail(VR_ERR_UNSUPPORTED, "frame %d: vr_render_aov has no instrumented flavour (counters)", i);
+    a.pitch = pitch;
+    a.depth_world = depth_units == VR_DEPTH_WORLD;
+    return VR_OK;
+}
+
 // Puts the kernels of the launch into the stream, behind the slot's previous launch: the probe
-// pre-kernel, the frame table, ray generation + render.
+// pre-kernel, the frame table (for an AOV launch also the plane table), ray generation + render.
+// aovs = NULL: a colour launch, `a` is not read.
 int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, const Tuning& tn,
-                   const VrCamera* cams, const VrRenderOptions* opt, const VrFrame* frames, hipStream_t hs) {
+                   const VrCamera* cams, const VrRenderOptions* opt, const VrFrame* frames, hipStream_t hs,
+                   const VrAov* aovs = nullptr, const vr::AovParams& a = vr::AovParams{}) {
     // whoever used this slot last (any stream) must have finished before its scratch is rewritten
     if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
     // From here on kernels of this launch may be in the stream: whatever happens below (a later
@@ -313,6 +344,17 @@ int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, 
             tbl.f[i].counters = reinterpret_cast<VrCounters*>(frames[first + i].counters);
         }
         HIP_TRY(vr::launch_prepare(k, tbl, hs));
+        if (aovs) {
+            vr::AovTable at;
+            memset(&at, 0, sizeof(at));
+            at.first = first;
+            at.n = tbl.n;
+            for (int i = 0; i < at.n; ++i) {
+                at.f[i].depth = aovs[first + i].depth;
+                at.f[i].transmittance = aovs[first + i].transmittance;
+            }
+            HIP_TRY(vr::launch_prepare_aov(a, at, hs));
+        }
     }
     // waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
     // two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
@@ -320,19 +362,23 @@ int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, 
     // two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
     // 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
     const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (k.n_frames <= 2 ? 4 : 16);
-    HIP_TRY(vr::launch_render(k, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
+    if (aovs)
+        HIP_TRY(vr::launch_render_aov(k, a, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
+    else
+        HIP_TRY(vr::launch_render(k, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
     return VR_OK;  // (`seal` records the slot's event)
 }
 
-}  // namespace
-
-extern "C" {
-
-int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
-                    const VrFrame* frames, void* stream) {
+// vr_render_batch (aovs = NULL) and vr_render_aov: one launch, in steps.
+int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                  const VrFrame* frames, const VrAov* aovs, int depth_units, bool want_aov, void* stream) {
     vr::KParams k;
     memset(&k, 0, sizeof(k));
+    vr::AovParams a;
+    memset(&a, 0, sizeof(a));
     if (int rc = validate_batch(t, n_frames, cams, opt, frames, k)) return rc;
+    if (want_aov)
+        if (int rc = validate_aov(n_frames, cams, opt, frames, aovs, depth_units, a)) return rc;
     DeviceGuard device_guard(t->device);
     fill_caller_params(k, &cams[0], opt, &frames[0]);
     hipStream_t hs = static_cast<hipStream_t>(stream);
@@ -342,7 +388,22 @@ int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
     fill_tuning_params(k, t, tn);
     unsigned slot;
     if (int rc = acquire_slot(t, guard, hs, k, slot)) return rc;
-    return enqueue_launch(t, t->slots[slot], k, tn, cams, opt, frames, hs);
+    a.planes = t->slot_aovs.get<vr::AovDesc>() + (size_t)slot * vr::kMaxBatch;
+    return enqueue_launch(t, t->slots[slot], k, tn, cams, opt, frames, hs, want_aov ? aovs : nullptr, a);
+}
+
+}  // namespace
+
+extern "C" {
+
+int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                    const VrFrame* frames, void* stream) {
+    return render_launch(t, n_frames, cams, opt, frames, nullptr, 0, false, stream);
+}
+
+int vr_render_aov(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                  const VrFrame* frames, const VrAov* aovs, int depth_units, void* stream) {
+    return render_launch(t, n_frames, cams, opt, frames, aovs, depth_units, true, stream);
 }
 
 int vr_reserve_tiles(vr_tree_t t, int width, int height, int n_frames, int tile_w, int tile_h,

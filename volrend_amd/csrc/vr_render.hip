@@ -15,6 +15,13 @@
 // This file: the kernels of a launch (ray generation, the persistent render kernel, the frame-table
 // write, the probe) and their launchers.  Layout, colour, point query and rays: vr_dev_*.h; the
 // upload-time build kernels: vr_tree_kernels.hip.
+// The text of the two big kernels (render_kernel, raygen_kernel) is compiled TWICE, under two pairs of
+// names: once as it stands, and once more -- as render_aov_kernel / raygen_aov_kernel, with a second
+// kernel argument -- through the #include of this very file behind raygen_kernel.  That inner pass
+// (VR_KERNEL_PASS_AOV) skips everything but the two kernels.  Two kernels over one text rather than
+// over one inlined function: the colour kernels keep the very machine code they had before the AOV
+// pair existed (tools/kernel_digest.py).
+#ifndef VR_KERNEL_PASS_AOV
 #include "vr_device_math.h"
 #include "vr_internal.h"
 #include "vr_dev_layout.h"
@@ -136,16 +143,42 @@ constexpr int min_waves_per_eu() {
     return BASIS == BASIS_25 ? kSh25Waves : BASIS == BASIS_16 ? kSh16Waves : BASIS == BASIS_9 ? kSh9Waves : 8;
 }
 // Waves one CU holds of a flavour: the register bound above or the LDS bound (512-byte granules).
+// The AOV flavours of SH9 / SH16 / SH25 sit on their register steps (one more live register spills in
+// the FMA SH9 flavour and costs the other two a wave): they keep the depth sum in one more LDS word per lane.
 template <int BASIS, int MODE>
+constexpr bool aov_depth_in_lds() {
+    return MODE == MODE_FAST && (BASIS == BASIS_9 || BASIS == BASIS_16 || BASIS == BASIS_25);
+}
+template <int BASIS, int MODE, bool AOV = false>
 constexpr int waves_per_cu() {
-    const int lds = ((kRing * 9 + kWave * 4 + Stage<BASIS>::kBytes + 511) / 512) * 512;
+    const int lds = ((kRing * 9 + kWave * 4 + (AOV && aov_depth_in_lds<BASIS, MODE>() ? kWave * 4 : 0) +
+                      Stage<BASIS>::kBytes + 511) / 512) * 512;
     const int by_lds = 163840 / lds, by_reg = 4 * min_waves_per_eu<BASIS, MODE>();
     return by_lds < by_reg ? by_lds : by_reg;
 }
 
+// The planes of one retired ray (vr_render_aov), always in frame position: D (times delta_scale for
+// VR_DEPTH_WORLD, formed by the caller) and the transmittance the ray left the loop with.
+__device__ __forceinline__ void store_aov(const AovParams& a, int frame, uint32_t xy, float d, float tr) {
+    const AovDesc pl = a.planes[frame];
+    const int64_t off = (int64_t)(xy >> 16) * a.pitch + (int64_t)(xy & 0xFFFFu) * 4;
+    typedef __attribute__((address_space(1))) float vr_gfloat_t;
+    if (pl.depth) *(vr_gfloat_t*)(reinterpret_cast<char*>(pl.depth) + off) = d;
+    if (pl.transmittance) *(vr_gfloat_t*)(reinterpret_cast<char*>(pl.transmittance) + off) = tr;
+}
+
+// names and arguments of the kernel pair of this pass (the colour pair; the AOV pair: behind raygen_kernel)
+#define VR_RENDER_KERNEL render_kernel
+#define VR_RAYGEN_KERNEL raygen_kernel
+#define VR_KERNEL_ARGS const KParams p
+#define VR_KERNEL_AOV false
+#define VR_KERNEL_AOV_LOCAL const AovParams aov{};  // (never read)
+#endif  // VR_KERNEL_PASS_AOV
+
 template <int FMA, int BASIS, int MODE, bool BLK = false>
-__global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void render_kernel(
-    const KParams p) {
+__global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void VR_RENDER_KERNEL(VR_KERNEL_ARGS) {
+    constexpr bool AOV = VR_KERNEL_AOV;
+    VR_KERNEL_AOV_LOCAL
     using P = Policy<FMA>;
     constexpr bool N2 = MODE != MODE_GENERIC;
     constexpr bool LOBES = MODE != MODE_FAST;
@@ -193,6 +226,23 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
     // scheduling statistics (instrumented flavours only): rounds and busy lanes per phase
     uint32_t st_march_r = 0, st_march_l = 0, st_shade_r = 0, st_shade_l = 0, st_distinct = 0,
              st_fin_r = 0, st_fin_l = 0, st_iter = 0;
+    // AOV flavours: D of the lane's ray -- a register where the flavour has one to spare, else a
+    // per-lane LDS word (read, multiply-add, write per hit sample: the rounding of either FP model)
+    constexpr bool D_LDS = AOV && aov_depth_in_lds<BASIS, MODE>();
+    float d_reg = 0.f;
+    float* d_lds = nullptr;
+    if constexpr (D_LDS) {
+        __shared__ float d_words[kWave];
+        d_lds = d_words;
+    }
+    auto depth_get = [&]() -> float {
+        if constexpr (D_LDS) return d_lds[lane_id_now()];
+        else return d_reg;
+    };
+    auto depth_set = [&](float v) {
+        if constexpr (D_LDS) d_lds[lane_id_now()] = v;
+        else d_reg = v;
+    };
 
     // Colour evaluation of up to 64 queued items, one per lane, whoever owns them;
     // afterwards every owner adds the contributions of its own items, oldest first
@@ -337,14 +387,19 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
             // composited and stored once everything has landed (their colour state does not
             // overlap the registers the new rays load into).
             uint32_t px_lo = 0, px_hi = 0, fin_xy = 0, fin_frame = 0;
+            float fin_d = 0.f;  // (AOV) the depth plane's value, formed before a new ray's delta_scale lands
             ray.stopped = ray.tmax < 0.f;  // (read before a new ray's tmax lands in the register)
             if (done) {
                 const uint32_t* rs = ray_slot(p.ray_buf, wpr, ray_ids[lane_id_now()]);
                 px_lo = ray_word(rs, kRayPixelLo);
                 px_hi = ray_word(rs, kRayPixelHi);
-                if (COUNT || p.any_accum) {
+                if (COUNT || p.any_accum || AOV) {
                     fin_xy = ray_word(rs, kRayXy);
                     fin_frame = ray_word(rs, kRayFrame);
+                }
+                if constexpr (AOV) {
+                    fin_d = depth_get();
+                    if (aov.depth_world) fin_d = fin_d * ray.delta_scale;
                 }
             }
             const bool vacant = done || !ray.active;
@@ -416,6 +471,10 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
                     p, ray, rc,
                     reinterpret_cast<uint8_t*>(((uint64_t)px_hi << 32) | (uint64_t)px_lo), fin_xy,
                     (int)fin_frame);
+            if constexpr (AOV) {
+                if (done) store_aov(aov, (int)fin_frame, fin_xy, fin_d, ray.light);
+                if (vacant) depth_set(0.f);
+            }
             if (vacant) {
                 ray.active = ray.entered = take;
                 if (!take) {  // (no ray: not alive)
@@ -505,6 +564,7 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
                     // delta_t * delta_scale below 2^-150 could meet an infinite sigma as 0 * inf.)
                     const float att = vr_expf_nonan(-delta_t * ray.delta_scale * sigma);
                     weight = ray.light * (1.f - att);
+                    if constexpr (AOV) depth_set(P::madd(weight, ray.t, depth_get()));
                     if (COUNT && p.render_depth)  // (depth launches take the FULL flavour)
                         ray.out[0] = P::madd(weight, ray.t, ray.out[0]);
                     else
@@ -595,7 +655,9 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void rend
 // atomics: at 4 waves a 64-frame launch is 4 % slower, at 1 wave 35 % (profiles/r06_raygen_waves.jsonl).
 
 template <int FMA, bool FULL, int GW>
-__global__ __launch_bounds__(kWave* GW) void raygen_kernel(const KParams p) {
+__global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
+    constexpr bool AOV = VR_KERNEL_AOV;
+    VR_KERNEL_AOV_LOCAL
     __shared__ uint32_t wave_count[GW];
     __shared__ uint32_t wave_base[GW];
     const int lane = threadIdx.x & (kWave - 1);
@@ -620,6 +682,7 @@ __global__ __launch_bounds__(kWave* GW) void raygen_kernel(const KParams p) {
             } else {
                 RayCounters z;  // a ray without a single sample
                 finish_ray<FMA, FULL>(p, nr, z, px, xy, frame);
+                if constexpr (AOV) store_aov(aov, frame, xy, 0.f, 1.f);  // no sample: D = 0, T = 1
             }
         }
     }
@@ -694,6 +757,27 @@ __global__ __launch_bounds__(kWave* GW) void raygen_kernel(const KParams p) {
     }
 }
 
+#ifndef VR_KERNEL_PASS_AOV
+#undef VR_RENDER_KERNEL
+#undef VR_RAYGEN_KERNEL
+#undef VR_KERNEL_ARGS
+#undef VR_KERNEL_AOV
+#undef VR_KERNEL_AOV_LOCAL
+// the AOV pair (vr_render_aov): the same text once more
+#define VR_KERNEL_PASS_AOV
+#define VR_RENDER_KERNEL render_aov_kernel
+#define VR_RAYGEN_KERNEL raygen_aov_kernel
+#define VR_KERNEL_ARGS const KParams p, const AovParams aov
+#define VR_KERNEL_AOV true
+#define VR_KERNEL_AOV_LOCAL
+#include "vr_render.hip"
+#undef VR_KERNEL_PASS_AOV
+#undef VR_RENDER_KERNEL
+#undef VR_RAYGEN_KERNEL
+#undef VR_KERNEL_ARGS
+#undef VR_KERNEL_AOV
+#undef VR_KERNEL_AOV_LOCAL
+
 // Writes the per-launch frame table into device memory and resets the ray queue.
 // (Stream-ordered replacement for a pinned-memory H2D copy + memset.)
 __global__ void prepare_launch_kernel(FrameTable tbl, FrameDesc* frames, uint32_t* queue_head) {
@@ -703,6 +787,12 @@ __global__ void prepare_launch_kernel(FrameTable tbl, FrameDesc* frames, uint32_
         queue_head[i * kQueueStride + kQueueHead] = 0u;
         queue_head[i * kQueueStride + kQueueCount] = 0u;
     }
+}
+
+// The plane pointers of an AOV launch, into the slot's table.
+__global__ void prepare_aov_kernel(AovTable tbl, AovDesc* planes) {
+    const int i = threadIdx.x;
+    if (i < tbl.n) planes[tbl.first + i] = tbl.f[i];
 }
 
 // Probe circle overlay, volrend.cu:100-134.  Pixels inside the circle skip the
@@ -783,16 +873,23 @@ bool needs_full(const KParams& p) {
 
 // grid = the persistent waves: as many as the chip holds of this flavour (or the tuning
 // override), but no more than about one wave per 128 rays of a small launch
-template <int FMA, int MODE>
-hipError_t launch_basis(const KParams& p, int64_t want, int n_cus, int waves_override, hipStream_t s) {
+template <int FMA, int MODE, bool AOV>
+hipError_t launch_basis(const KParams& p, const AovParams& a, int64_t want, int n_cus, int waves_override,
+                        hipStream_t s) {
     const dim3 block(kWave);
 #define VR_LAUNCH(B)                                                                         \
     do {                                                                                     \
         const int64_t cap_ = (int64_t)n_cus * (waves_override > 0 ? waves_override           \
-                                                                  : waves_per_cu<B, MODE>()); \
+                                                                  : waves_per_cu<B, MODE, AOV>()); \
         const dim3 grid((unsigned)(want < cap_ ? want : cap_));                              \
-        if (MODE == MODE_FAST && p.brick_blocked)                                            \
-            hipLaunchKernelGGL((render_kernel<FMA, B, MODE, MODE == MODE_FAST>), grid, block, 0, s, p); \
+        constexpr bool kBlk = MODE == MODE_FAST;                                             \
+        if constexpr (AOV) {                                                                 \
+            if (kBlk && p.brick_blocked)                                                     \
+                hipLaunchKernelGGL((render_aov_kernel<FMA, B, MODE, kBlk>), grid, block, 0, s, p, a); \
+            else                                                                             \
+                hipLaunchKernelGGL((render_aov_kernel<FMA, B, MODE, false>), grid, block, 0, s, p, a); \
+        } else if (kBlk && p.brick_blocked)                                                  \
+            hipLaunchKernelGGL((render_kernel<FMA, B, MODE, kBlk>), grid, block, 0, s, p);   \
         else                                                                                 \
             hipLaunchKernelGGL((render_kernel<FMA, B, MODE, false>), grid, block, 0, s, p);  \
     } while (0)
@@ -808,31 +905,28 @@ hipError_t launch_basis(const KParams& p, int64_t want, int n_cus, int waves_ove
     return hipGetLastError();
 }
 
-template <int FMA>
-hipError_t launch_fp(const KParams& p, int64_t want, int n_cus, int waves_override, hipStream_t s) {
+template <int FMA, bool AOV>
+hipError_t launch_fp(const KParams& p, const AovParams& a, int64_t want, int n_cus, int waves_override,
+                     hipStream_t s) {
     const bool n2 = (p.N == 2) && p.top_levels > 0;  // built at upload when the tree qualifies
-    if (!n2) return launch_basis<FMA, MODE_GENERIC>(p, want, n_cus, waves_override, s);
-    if (needs_full(p)) return launch_basis<FMA, MODE_FULL>(p, want, n_cus, waves_override, s);
-    return launch_basis<FMA, MODE_FAST>(p, want, n_cus, waves_override, s);
+    if (!n2) return launch_basis<FMA, MODE_GENERIC, AOV>(p, a, want, n_cus, waves_override, s);
+    if (needs_full(p)) return launch_basis<FMA, MODE_FULL, AOV>(p, a, want, n_cus, waves_override, s);
+    return launch_basis<FMA, MODE_FAST, AOV>(p, a, want, n_cus, waves_override, s);
 }
 
-}  // namespace
-
-hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream) {
-    hipLaunchKernelGGL(prepare_launch_kernel, dim3(1), dim3(64), 0, stream, tbl,
-                       const_cast<FrameDesc*>(p.frames), p.queue_head);
-    return hipGetLastError();
-}
-
-hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
-                         hipStream_t stream) {
-    if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
+// Ray generation + the persistent march of one launch (the probe overlay is launch_render's own).
+template <bool AOV>
+hipError_t launch_march(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
+                        int gen_waves, hipStream_t stream) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
     {   // ray generation: gen_waves wave blocks (8x8 pixels each) per workgroup
         const bool full = needs_full(p);
 #define VR_GEN(FMA_, FULL_, GW_)                                                                    \
-    hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_>),                                           \
-                       dim3((unsigned)((total_blocks + GW_ - 1) / GW_)), dim3(kWave * GW_), 0, stream, p)
+    do {                                                                                            \
+        const dim3 grid_((unsigned)((total_blocks + GW_ - 1) / GW_)), block_(kWave * GW_);          \
+        if constexpr (AOV) hipLaunchKernelGGL((raygen_aov_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, a); \
+        else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p);    \
+    } while (0)
 #define VR_GEN_GW(FMA_, FULL_)                                                                      \
     do {                                                                                            \
         if (gen_waves >= 16) VR_GEN(FMA_, FULL_, 16);                                               \
@@ -852,9 +946,22 @@ hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_ove
     int64_t want = total_blocks / 2;  // about one wave per 64 rays that enter the volume
     if (want < 256) want = 256;
     if (want > total_blocks) want = total_blocks;
-    const hipError_t e = fp_mode == VR_FP_FMA
-                             ? launch_fp<1>(p, want, n_cus, waves_override, stream)
-                             : launch_fp<0>(p, want, n_cus, waves_override, stream);
+    return fp_mode == VR_FP_FMA ? launch_fp<1, AOV>(p, a, want, n_cus, waves_override, stream)
+                                : launch_fp<0, AOV>(p, a, want, n_cus, waves_override, stream);
+}
+
+}  // namespace
+
+hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream) {
+    hipLaunchKernelGGL(prepare_launch_kernel, dim3(1), dim3(64), 0, stream, tbl,
+                       const_cast<FrameDesc*>(p.frames), p.queue_head);
+    return hipGetLastError();
+}
+
+hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
+                         hipStream_t stream) {
+    if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
+    const hipError_t e = launch_march<false>(p, AovParams{}, fp_mode, n_cus, waves_override, gen_waves, stream);
     if (e != hipSuccess || !p.enable_probe || p.probe_disp_size <= 0) return e;
     const int side = p.probe_disp_size + 5;
     const dim3 pgrid((unsigned)((side * side + 255) / 256), (unsigned)p.n_frames);
@@ -865,6 +972,18 @@ hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_ove
     return hipGetLastError();
 }
 
+hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream) {
+    hipLaunchKernelGGL(prepare_aov_kernel, dim3(1), dim3(64), 0, stream, tbl, const_cast<AovDesc*>(a.planes));
+    return hipGetLastError();
+}
+
+// (no probe overlay: vr_render_aov refuses enable_probe)
+hipError_t launch_render_aov(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
+                             int gen_waves, hipStream_t stream) {
+    if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
+    return launch_march<true>(p, a, fp_mode, n_cus, waves_override, gen_waves, stream);
+}
+
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
                         hipStream_t stream) {
     hipLaunchKernelGGL(probe_kernel, dim3(1), dim3(64), 0, stream, p, probe[0], probe[1],
@@ -873,3 +992,4 @@ hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
 }
 
 }  // namespace vr
+#endif  // VR_KERNEL_PASS_AOV

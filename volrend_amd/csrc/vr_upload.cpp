@@ -440,6 +440,7 @@ hipError_t alloc_launch_scratch(VrTreeOpaque* t) {
     for (unsigned i = 0; i < kLaunchSlots && e == hipSuccess; ++i) e = t->slots[i].done.create();
     if (e == hipSuccess) e = t->slot_frames.alloc(sizeof(vr::FrameDesc) * vr::kMaxBatch * kLaunchSlots);
     if (e == hipSuccess) e = t->slot_heads.alloc(sizeof(uint32_t) * vr::kSlotWords * kLaunchSlots);
+    if (e == hipSuccess) e = t->slot_aovs.alloc(sizeof(vr::AovDesc) * vr::kMaxBatch * kLaunchSlots);
     int cus = 0;
     if (e == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, t->device) == hipSuccess &&
         cus > 0)
