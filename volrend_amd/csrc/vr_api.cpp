@@ -1,6 +1,7 @@
 // vr_api.cpp -- the C ABI of libvolrend_hip.so (include/volrend_hip.h), host side: version, errors,
 // devices, defaults, tuning, statistics and touch bitmaps, tile assembly, probe, read-back.
-// Upload, clone and free are in vr_upload.cpp, launches in vr_launch.cpp.
+// Upload, clone and free are in vr_upload.cpp (its host walks in vr_tree_walk.cpp, its copy pipeline in
+// vr_h2d.cpp), launches in vr_launch.cpp.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -11,6 +12,7 @@
 #include <mutex>
 
 #include "vr_host.h"
+#include "vr_tree_walk.h"
 
 namespace {
 
@@ -150,7 +152,7 @@ int vr_tree_info(vr_tree_t t, VrTreeInfo* info) {
 // The integer lookup needs exact digits of a binary32 coordinate (leaves within 24 levels: child
 // words read <= 24) and 32-bit byte offsets into the node array (node * 8 + slot words < 2^30).
 int vr_query_mode_for(int N, int max_depth, int64_t capacity) {
-    return (N == 2 && max_depth <= 23 && capacity < (1ll << 27)) ? VR_QUERY_LOOKUP : VR_QUERY_DESCENT;
+    return lookup_applies(N, max_depth, capacity) ? VR_QUERY_LOOKUP : VR_QUERY_DESCENT;
 }
 
 void vr_default_options(VrRenderOptions* o) {

@@ -1,5 +1,7 @@
 // vr_host.h -- shared by the host sources of libvolrend_hip.so (vr_api.cpp, vr_upload.cpp,
-// vr_launch.cpp).  Host only (not for the .hip units); nothing here is exported from the library.
+// vr_launch.cpp, vr_query.cpp).  Host only (not for the .hip units); nothing here is exported from the
+// library.  Two host units stand beside it with headers of their own: vr_tree_walk.{h,cpp} (the walks
+// of an upload over the child array; no HIP) and vr_h2d.{h,cpp} (the upload's staged copy pipeline).
 #pragma once
 #include <hip/hip_runtime.h>
 
