@@ -288,6 +288,38 @@ typedef struct VrAov {        /* device pointers of ONE frame; NULL = not wanted
 } VrAov;
 int vr_render_aov(vr_tree_t tree, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
                   const VrFrame* frames, const VrAov* aovs, int depth_units, void* stream);
+/* ---- Leaf weights: per leaf, the largest ray weight over a set of views ---- */
+/* What PlenOctree extraction and pruning threshold on (svox: accumulate_weights): for every pixel of
+ * every camera the ray of trace_ray (rt_core.cuh:66-196) is marched exactly as vr_render_batch marches
+ * it, in FP model fp_mode, as an offscreen frame (no mesh depth: tmax comes from render_bbox alone), and
+ * for each sample with sigma > sigma_thresh, in the leaf slot s the point query returns:
+ *   hits[s] += 1 (modulo 2^32);
+ *   if weight > 0: max_weight[s] = max(max_weight[s], weight)   (weight <= 0 or NaN only counts in hits)
+ * with weight = light_intensity * (1.f - att) as the reference forms it -- the sample that then trips
+ * stop_thresh included.  No colour is formed: the tree's format and basis do not matter.
+ * The call accumulates INTO the buffers; the caller zeroes them once.  A maximum and a count are
+ * order-independent: any split of a pose set into calls, batches, streams or devices (followed by an
+ * element-wise max / sum) gives the same bits.  On entry max_weight must hold non-negative, non-NaN
+ * floats (on that domain the float maximum is the unsigned maximum of the bit patterns).
+ * Of opt only step_size, sigma_thresh, stop_thresh and render_bbox are read.
+ * Contract: that of vr_render_batch -- enqueue only, one image size and one set of intrinsics per call,
+ * <= VR_MAX_BATCH frames, a launch slot (the ray record is shorter than a colour ray's: vr_reserve of the
+ * same shape covers it), step_size <= 0 / NaN refused, the sample guard reports through vr_tree_status.
+ * The first call of a tree uploads a 4-bytes-per-node table (device node -> file node) under the tree's
+ * mutex -- the call's one host-blocking step; from then on it counts in VrTreeInfo.device_bytes.
+ * n_frames == 0 does just that and launches nothing (the warm-up call).  Apart from that table the call
+ * only reads the tree: any number of calls may run beside each other, render launches and queries.
+ * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed or any device call: NULL tree / cams (when
+ * n_frames > 0) / opt / out, both outputs NULL, unknown fp_mode, n_frames < 0 or > VR_MAX_BATCH, cameras
+ * that differ in size or intrinsics. */
+typedef struct VrLeafWeights {  /* device pointers; NULL = not wanted; at least one non-NULL.
+                                   Both [capacity * N^3], indexed as VrTreeDesc.child / data are:
+                                   node * N^3 + child slot IN THE FILE'S node numbering */
+    float*    max_weight;
+    uint32_t* hits;
+} VrLeafWeights;
+int vr_accumulate_weights(vr_tree_t tree, int n_frames, const VrCamera* cams,
+                          const VrRenderOptions* opt, int fp_mode, const VrLeafWeights* out, void* stream);
 /* Pre-allocates the ray buffers of two launch slots for batches of up to n_frames whole
  * width x height frames (128-228 bytes per ray): a render loop on one stream lives in one slot,
  * two alternating streams in two, so no later vr_render / vr_render_batch of that size (or

@@ -74,6 +74,10 @@ class VrAov(C.Structure):
     _fields_ = [("depth", C.c_void_p), ("transmittance", C.c_void_p), ("pitch", C.c_int64)]
 
 
+class VrLeafWeights(C.Structure):
+    _fields_ = [("max_weight", C.c_void_p), ("hits", C.c_void_p)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -111,6 +115,8 @@ PROTOTYPES = {
                                   C.POINTER(VrRenderOptions), C.POINTER(VrFrame), C.c_void_p]),
     "vr_render_aov": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
                                 C.POINTER(VrFrame), C.POINTER(VrAov), C.c_int, C.c_void_p]),
+    "vr_accumulate_weights": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
+                                        C.c_int, C.POINTER(VrLeafWeights), C.c_void_p]),
     "vr_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "vr_reserve_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int]),

@@ -462,6 +462,23 @@ class N3Tree:
                                             sp, C.byref(out), _stream_ptr(stream)))
         return out_t
 
+    # ---- per-leaf ray weights (vr_accumulate_weights) -----------------------
+    def accumulate_weights(self, cam: "Camera", transforms, options: "RenderOptions", *, max_weight=None,
+                           hits=None, want=("max_weight",), fp_mode: int = _abi.FP_STRICT, stream=None) -> dict:
+        """Per leaf slot, over every pixel of every pose of ``transforms`` (12 floats each, as
+        ``launch_renderer_batch`` takes them): the largest compositing weight a sample in the slot received
+        ("max_weight", float32) and the number of hit samples in it ("hits", a uint32 count held in an int32
+        tensor) -- vr_accumulate_weights, enqueued on ``stream``, one launch per 512 poses.
+
+        Returns a dict of torch tensors shaped [capacity, N, N, N], indexed like the file's ``child`` /
+        ``data`` arrays.  ``want`` names the outputs; a tensor passed as ``max_weight`` / ``hits`` is wanted
+        too and is ACCUMULATED INTO (it must be contiguous, on the tree's device, and -- max_weight -- hold
+        non-negative, non-NaN floats); the others are allocated zeroed.  Any split of a pose set into calls
+        gives the same bits.  Of ``options`` only step_size, sigma_thresh, stop_thresh and render_bbox are
+        read.  No poses: only the tree's file-order table is put on the device (the warm-up call)."""
+        return accumulate_weights(self, cam, transforms, options, max_weight=max_weight, hits=hits, want=want,
+                                  fp_mode=fp_mode, stream=stream)
+
     def info(self) -> dict:
         i = _abi.VrTreeInfo()
         _abi.check(_abi.lib().vr_tree_info(self._handle, C.byref(i)))
@@ -693,6 +710,45 @@ def launch_renderer_batch(tree: N3Tree, cam: Camera, transforms, options: Render
     PreparedBatch(tree, cam, transforms, options, images, offscreen, accums=accums, depths=depths,
                   pitch=pitch, shard=shard, fp_mode=fp_mode, counters=counters, aov=aov,
                   depth_units=depth_units).launch(stream)
+
+
+def accumulate_weights(tree, cam: Camera, transforms, options: RenderOptions, *, max_weight=None, hits=None,
+                       want=("max_weight",), fp_mode: int = _abi.FP_STRICT, stream=None) -> dict:
+    """``N3Tree.accumulate_weights`` (documented there).  Outputs the caller passes may also be raw device
+    pointers; they are returned as passed."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in ("max_weight", "hits") for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"want names 'max_weight' and / or 'hits', each once: {want!r}")
+    given = {"max_weight": max_weight, "hits": hits}
+    res = {}
+    for name in ("max_weight", "hits"):
+        buf = given[name]
+        if buf is None and name in want:
+            import torch
+            dev = torch.device("cuda", tree.info()["device"])
+            buf = torch.zeros((tree.capacity, tree.N, tree.N, tree.N), device=dev,
+                              dtype=torch.float32 if name == "max_weight" else torch.int32)
+        elif buf is not None and not isinstance(buf, int):
+            shape, dt = (tree.capacity, tree.N, tree.N, tree.N), str(buf.dtype)
+            if tuple(buf.shape) != shape or not buf.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous tensor of shape {shape}, not {tuple(buf.shape)}")
+            if dt != ("torch.float32" if name == "max_weight" else "torch.int32"):
+                raise ValueError(f"{name} must be {'float32' if name == 'max_weight' else 'int32'}, not {dt}")
+        if buf is not None:
+            res[name] = buf
+    out = _abi.VrLeafWeights()
+    out.max_weight, out.hits = _ptr(res.get("max_weight")), _ptr(res.get("hits"))
+    L, o = _abi.lib(), options.to_c()
+    n = len(transforms)
+    for first in range(0, max(n, 1), _abi.MAX_BATCH):
+        m = min(_abi.MAX_BATCH, n - first)
+        cams = (_abi.VrCamera * m)() if m else None
+        for i in range(m):
+            cam.transform = np.asarray(transforms[first + i], dtype=np.float32)
+            cams[i] = cam.to_c()
+        _abi.check(L.vr_accumulate_weights(tree.handle, m, cams, C.byref(o), int(fp_mode), C.byref(out),
+                                           _stream_ptr(stream)))
+    return res
 
 
 def set_tuning(**kw) -> None:

@@ -1,10 +1,12 @@
-// renderer.cpp -- volrend::launch_renderer[_aov] over vr_render / vr_render_batch / vr_render_aov.
+// renderer.cpp -- volrend::launch_renderer[_aov] over vr_render / vr_render_batch / vr_render_aov, and
+// volrend::accumulate_weights over vr_accumulate_weights (the same poses, cameras and options).
 #include <stdexcept>
 #include <string>
 
 #include "volrend/aov.hpp"
 #include "volrend/internal/check.hpp"
 #include "volrend/renderer_kernel.hpp"
+#include "volrend/weights.hpp"
 
 namespace volrend {
 namespace {
@@ -74,6 +76,20 @@ void launch_renderer_batch(const N3Tree& tree, const Camera& cam,
         }
         internal::vr_check(vr_render_batch(tree.device, n, cams, &o, frames, stream), "vr_render_batch");
     }
+}
+
+void accumulate_weights(const N3Tree& tree, const Camera& cam, const std::vector<const float*>& transforms,
+                        const RenderOptions& options, const LeafWeights& out, void* stream, int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    size_t first = 0;
+    do {  // (no pose at all: one call with n = 0, the warm-up)
+        const int n = (int)std::min<size_t>(VR_MAX_BATCH, transforms.size() - first);
+        std::vector<VrCamera> cams((size_t)n);
+        for (int i = 0; i < n; ++i) cams[(size_t)i] = to_c(cam, transforms[first + i]);
+        internal::vr_check(vr_accumulate_weights(tree.device, n, n ? cams.data() : nullptr, &o, fp_mode, &out, stream),
+                           "vr_accumulate_weights");
+        first += VR_MAX_BATCH;
+    } while (first < transforms.size());
 }
 
 namespace {

@@ -39,6 +39,7 @@ const Knob kKnobs[] = {
     {"brick_levels", "VR_BRICK_LEVELS", &Tuning::brick_levels, kClamp, INT_MIN, INT_MAX, true},
     {"brick_blocked", "VR_BRICK_BLOCKED", &Tuning::brick_blocked, kAutoFlag, 0, 0, true},
     {"max_iter", "VR_MAX_ITER", &Tuning::max_iter, kClamp, 1, INT_MAX, false},
+    {"weights_check", "VR_WEIGHTS_CHECK", &Tuning::weights_check, kFlag, 0, 0, false},
 };
 
 const Knob* find_knob(const char* key) {

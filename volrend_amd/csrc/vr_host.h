@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <mutex>
+#include <vector>
 
 #include "vr_internal.h"
 
@@ -54,6 +55,8 @@ struct Tuning {
     int brick_blocked = -1;  // 8^3 bricks in 4 x 4 x 2 line blocks: -1 = when the lookup structure exceeds 128 MB, 0 / 1 = forced
     int max_iter = 1 << 22;  // the sample guard (vr_render.hip); the one knob that is NOT scheduling-only:
                              // a launch that trips it reports through vr_tree_status (tests lower it)
+    int weights_check = 1;   // vr_accumulate_weights: read max_weight[slot] first and issue the atomic max only
+                             // for a larger weight (0: one atomic per positive weight; vr_weights.hip, EXPERIMENTS.md)
 };
 Tuning default_tuning();  // the process defaults, for a tree being uploaded
 
@@ -98,6 +101,8 @@ struct VrTreeOpaque : TreeShape {
     DeviceBuffer slot_frames;    // kLaunchSlots x kMaxBatch vr::FrameDesc
     DeviceBuffer slot_heads;     // kLaunchSlots x vr::kSlotWords uint32_t
     DeviceBuffer slot_aovs;      // kLaunchSlots x kMaxBatch vr::AovDesc: the plane pointers of an AOV launch
+    std::vector<int32_t> file_node;  // device node -> the file's node: the inverse of the upload's renumbering (host)
+    DeviceBuffer file_node_dev;  // its device copy, made by the first vr_accumulate_weights (then in device_bytes)
     LaunchSlot slots[kLaunchSlots];
     unsigned launch_seq = 0;
     std::mutex launch_mutex;  // slot bookkeeping + enqueue order of one launch; guards `tn`

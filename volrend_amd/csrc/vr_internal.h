@@ -1,5 +1,5 @@
 // vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp, vr_upload.cpp, vr_launch.cpp) and
-// the gfx950 kernels (vr_render.hip, vr_tree_kernels.hip).  Not part of the public ABI.
+// the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_tree_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -207,6 +207,24 @@ struct AovTable {
     int32_t n;
     AovDesc f[kTableChunk];
 };
+
+// ---------------------------------------------------------------------------
+// Leaf-weight launches (vr_accumulate_weights): the march without records or shading.  The kernels of
+// vr_weights.hip take KParams unchanged plus this second argument.  Their ray record is the march state
+// alone -- the words kRayCen .. kRayDeltaScale of the colour record, nothing behind them.
+// ---------------------------------------------------------------------------
+constexpr int kWeightRayWords = kRayDeltaScale + 1;  // 12: cen, dir, invdir, t, tmax, delta_scale
+static_assert(kWeightRayWords <= kRayWords, "a slot reserved for colour rays holds the weight rays of the same shape");
+struct WeightParams {
+    uint32_t* max_weight;       // [capacity * N3] bit patterns of non-negative floats, file order; NULL = not wanted
+    uint32_t* hits;             // [capacity * N3], file order; NULL = not wanted
+    const int32_t* file_node;   // device node -> the file's node (VrTreeOpaque.file_node)
+};
+
+// vr_weights.hip: ray generation + the persistent march of a leaf-weight launch (the frame table and the
+// queue reset are launch_prepare's).  check_first: the max reads the word before it issues the atomic.
+hipError_t launch_weights(const KParams& p, const WeightParams& w, int fp_mode, int n_cus, int waves_override,
+                          int gen_waves, bool check_first, hipStream_t stream);
 
 // vr_render.hip: the kernels of a launch
 hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream);

@@ -1,4 +1,5 @@
-// vr_launch.cpp -- launches (include/volrend_hip.h): vr_render_batch, vr_reserve*, vr_tree_status*,
+// vr_launch.cpp -- launches (include/volrend_hip.h): vr_render_batch, vr_render_aov, vr_accumulate_weights,
+// vr_reserve*, vr_tree_status*,
 // the launch geometry and the launch-slot ring.  Built with -ffp-contract=off (the host-side
 // Rodrigues pre-computation below must round like the oracle).
 #include <hip/hip_runtime.h>
@@ -223,11 +224,10 @@ void fill_tuning_params(vr::KParams& k, const VrTreeOpaque* t, const Tuning& tn)
 }
 
 // Launch slot: per-launch scratch in device memory (ring, see LaunchSlot).  Picks the slot of this
-// launch, points `k` at its scratch and makes its ray buffer large enough.  `guard` holds the
+// launch, points `k` at its scratch and makes its ray buffer large enough (`need` bytes).  `guard` holds the
 // launch mutex on entry and on return.
 int acquire_slot(VrTreeOpaque* t, std::unique_lock<std::mutex>& guard, hipStream_t hs, vr::KParams& k,
-                 unsigned& slot) {
-    const size_t need = ray_buffer_bytes(k.total_rays, k.ray_tail_words);
+                 size_t need, unsigned& slot) {
     slot = kLaunchSlots;
     for (int want_fit = 1; want_fit >= 0 && slot == kLaunchSlots; --want_fit) {
         for (int pass = 0; pass < 2 && slot == kLaunchSlots; ++pass)
@@ -304,6 +304,22 @@ int validate_aov(int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
     return VR_OK;
 }
 
+// From its construction on kernels of a launch may be in the stream: whatever happens afterwards (a later
+// enqueue failing), the slot's event is recorded behind them and the slot is marked used, so
+// that the next user of the slot -- any stream -- waits for whatever did get enqueued.
+struct SlotSeal {
+    LaunchSlot& ls;
+    hipStream_t hs;
+    ~SlotSeal() {
+        if (hipEventRecord(ls.done.get(), hs) == hipSuccess) {
+            ls.used = true;
+            ls.last_stream = hs;
+        } else {
+            (void)hipGetLastError();
+        }
+    }
+};
+
 // Puts the kernels of the launch into the stream, behind the slot's previous launch: the probe
 // pre-kernel, the frame table (for an AOV launch also the plane table), ray generation + render.
 // aovs = NULL: a colour launch, `a` is not read.
@@ -312,21 +328,7 @@ int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, 
                    const VrAov* aovs = nullptr, const vr::AovParams& a = vr::AovParams{}) {
     // whoever used this slot last (any stream) must have finished before its scratch is rewritten
     if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
-    // From here on kernels of this launch may be in the stream: whatever happens below (a later
-    // enqueue failing), the slot's event is recorded behind them and the slot is marked used, so
-    // that the next user of the slot -- any stream -- waits for whatever did get enqueued.
-    struct SlotSeal {
-        LaunchSlot& ls;
-        hipStream_t hs;
-        ~SlotSeal() {
-            if (hipEventRecord(ls.done.get(), hs) == hipSuccess) {
-                ls.used = true;
-                ls.last_stream = hs;
-            } else {
-                (void)hipGetLastError();
-            }
-        }
-    } seal{ls, hs};
+    SlotSeal seal{ls, hs};
     if (k.enable_probe)  // launch_renderer's pre-kernel, volrend.cu:202-209
         HIP_TRY(vr::launch_probe(k, opt->probe, const_cast<float*>(k.probe_coeffs), hs));
 
@@ -387,14 +389,112 @@ int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRende
     const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
     fill_tuning_params(k, t, tn);
     unsigned slot;
-    if (int rc = acquire_slot(t, guard, hs, k, slot)) return rc;
+    if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, k.ray_tail_words), slot)) return rc;
     a.planes = t->slot_aovs.get<vr::AovDesc>() + (size_t)slot * vr::kMaxBatch;
     return enqueue_launch(t, t->slots[slot], k, tn, cams, opt, frames, hs, want_aov ? aovs : nullptr, a);
+}
+
+// ---- vr_accumulate_weights ----
+
+// Everything that can be refused without following the tree handle.  Leaves the launch geometry in `k`.
+int validate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                     const VrLeafWeights* out, vr::KParams& k) {
+    if (!t || !opt || !out || (n_frames > 0 && !cams)) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!out->max_weight && !out->hits) return fail(VR_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+    if (fp_mode != VR_FP_STRICT && fp_mode != VR_FP_FMA)
+        return fail(VR_ERR_INVALID_ARGUMENT, "unknown fp_mode %d", fp_mode);
+    if (n_frames < 0 || n_frames > VR_MAX_BATCH)
+        return fail(VR_ERR_INVALID_ARGUMENT, "n_frames=%d outside [0,%d]", n_frames, VR_MAX_BATCH);
+    // (as vr_render_batch: the march would never advance past a leaf face)
+    if (!(opt->step_size > 0.f))
+        return fail(VR_ERR_INVALID_ARGUMENT, "step_size must be positive (got %g)", (double)opt->step_size);
+    if (n_frames == 0) return VR_OK;
+    const VrCamera* cam = &cams[0];
+    if (int rc = launch_geometry(cam->width, cam->height, 0, 0, 0, 1, n_frames, k)) return rc;
+    if (!(cam->fx != 0.f) || !(cam->fy != 0.f))
+        return fail(VR_ERR_INVALID_ARGUMENT, "focal length must be non-zero");
+    for (int i = 1; i < n_frames; ++i)
+        if (cams[i].width != cam->width || cams[i].height != cam->height || cams[i].fx != cam->fx ||
+            cams[i].fy != cam->fy)
+            return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: intrinsics differ within the batch", i);
+    k.n_frames = n_frames;
+    return VR_OK;
+}
+
+// The device copy of the tree's device-node -> file-node table, made on the first call (under the launch
+// mutex; the call's one host-blocking step).
+int ensure_file_nodes(VrTreeOpaque* t) {
+    if (t->file_node_dev) return VR_OK;
+    const size_t bytes = t->file_node.size() * sizeof(int32_t);
+    if (bytes != (size_t)t->desc.capacity * sizeof(int32_t))
+        return fail(VR_ERR_HIP, "the tree carries no file-order table");
+    hipError_t e = t->file_node_dev.alloc(bytes);
+    if (e == hipSuccess) e = hipMemcpy(t->file_node_dev.get(), t->file_node.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)t->file_node_dev.reset();
+        return fail(hip_code(e), "file-order table of %zu bytes: %s", bytes, hipGetErrorString(e));
+    }
+    t->device_bytes += bytes;
+    return VR_OK;
+}
+
+int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                       const VrLeafWeights* out, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = validate_weights(t, n_frames, cams, opt, fp_mode, out, k)) return rc;
+    DeviceGuard device_guard(t->device);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    std::unique_lock<std::mutex> guard(t->launch_mutex);
+    if (int rc = ensure_file_nodes(t)) return rc;
+    if (n_frames == 0) return VR_OK;  // the warm-up call
+    // the caller's part: intrinsics and the four options the march reads; an offscreen frame without
+    // mesh depth, probe, depth mode or view-direction rotation
+    k.width = cams[0].width;
+    k.height = cams[0].height;
+    k.fx = cams[0].fx;
+    k.fy = cams[0].fy;
+    k.step_size = opt->step_size;
+    k.sigma_thresh = opt->sigma_thresh;
+    k.stop_thresh = opt->stop_thresh;
+    memcpy(k.bbox, opt->render_bbox, sizeof(k.bbox));
+    k.offscreen = 1;
+    k.layout = VR_LAYOUT_FRAME;
+    k.pitch = (int64_t)k.width * 4;
+    fill_tree_params(k, t);
+    const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
+    fill_tuning_params(k, t, tn);
+    unsigned slot;
+    const size_t need = vr::ray_slots(k.total_rays) * (size_t)vr::kWeightRayWords * sizeof(uint32_t);
+    if (int rc = acquire_slot(t, guard, hs, k, need, slot)) return rc;
+    LaunchSlot& ls = t->slots[slot];
+    if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
+    SlotSeal seal{ls, hs};
+    for (int first = 0; first < n_frames; first += vr::kTableChunk) {  // the poses (and the queue reset)
+        vr::FrameTable tbl;
+        memset(&tbl, 0, sizeof(tbl));
+        tbl.first = first;
+        tbl.n = n_frames - first < vr::kTableChunk ? n_frames - first : vr::kTableChunk;
+        for (int i = 0; i < tbl.n; ++i) memcpy(tbl.f[i].xf, cams[first + i].transform, sizeof(tbl.f[i].xf));
+        HIP_TRY(vr::launch_prepare(k, tbl, hs));
+    }
+    vr::WeightParams w;
+    w.max_weight = reinterpret_cast<uint32_t*>(out->max_weight);
+    w.hits = out->hits;
+    w.file_node = t->file_node_dev.get<int32_t>();
+    const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
+    HIP_TRY(vr::launch_weights(k, w, fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, tn.weights_check != 0, hs));
+    return VR_OK;  // (`seal` records the slot's event)
 }
 
 }  // namespace
 
 extern "C" {
+
+int vr_accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                          int fp_mode, const VrLeafWeights* out, void* stream) {
+    return accumulate_weights(t, n_frames, cams, opt, fp_mode, out, stream);
+}
 
 int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
                     const VrFrame* frames, void* stream) {

@@ -118,6 +118,12 @@ std::vector<int32_t> node_permutation(const int32_t* child, int64_t cap, int N3,
     return perm;
 }
 
+std::vector<int32_t> inverse_permutation(const std::vector<int32_t>& perm) {
+    std::vector<int32_t> inv(perm.size());
+    for (size_t i = 0; i < perm.size(); ++i) inv[(size_t)perm[i]] = (int32_t)i;
+    return inv;
+}
+
 bool lookup_applies(int N, int max_depth, int64_t capacity) {
     return N == 2 && max_depth <= 23 && capacity < (1ll << 27);
 }

@@ -29,6 +29,11 @@ std::vector<int32_t> node_permutation(const int32_t* child, int64_t cap, int N3,
                                       const std::vector<uint8_t>& level,
                                       std::vector<int32_t>& brick_roots);
 
+// The renumbering read the other way: result[new index] = old index.  vr_accumulate_weights reports per
+// leaf slot in the file's numbering, so an upload keeps this (unreachable nodes included: perm is a
+// permutation of [0, cap)).
+std::vector<int32_t> inverse_permutation(const std::vector<int32_t>& perm);
+
 // Which trees take the integer lookup (vr_query_mode_for, include/volrend_hip.h): N == 2, leaves
 // within 24 levels (exact integer digits of a binary32 coordinate), node * 8 + slot byte offsets
 // that fit 32 bits.  max_depth as validate_topology returns it.

@@ -317,6 +317,7 @@ int upload_steps(const UploadJob& j, vr_tree_t* out) {
     std::vector<int32_t> brick_roots;
     const std::vector<int32_t> perm =
         node_permutation(j.host_child, j.d->capacity, j.N3, plan.G0, plan.BL, w.level, brick_roots);
+    t->file_node = inverse_permutation(perm);  // what vr_accumulate_weights indexes its outputs by
     j.mark("host walks done");
 
     // the reference arrays are staged on the device now (unless they already were there);
@@ -414,6 +415,8 @@ int vr_tree_clone(vr_tree_t src, int device, vr_tree_t* out) {
     static_cast<TreeShape&>(*t) = *src;
     t->device = device;
     t->tn = src->tn;
+    t->file_node = src->file_node;  // (its device copy is made on the clone's first vr_accumulate_weights)
+    t->device_bytes -= src->file_node_dev.bytes();
     // the re-laid-out arrays travel device to device (over xGMI between two GPUs of a node):
     // no second pass over PCIe, no second re-layout
     // direct peer access (xGMI / PCIe P2P) when the two devices have it: hipMemcpyPeer then moves
