@@ -36,10 +36,10 @@ def lib():
     return _lib
 
 
-def restate(tree, transform, w, h, focal, fp_mode=0, ndc=None, offscreen=True, depth_init=None, **opt_kw):
+def restate(tree, transform, w, h, focal, fp_mode=0, ndc=None, offscreen=True, depth_init=None, fy=None, **opt_kw):
     """-> (D, T, delta_scale float32 [h,w], stopped bool [h,w]) of every pixel."""
     th = ob.TreeHandle(tree, ndc=ndc)
-    cam = ob.make_camera(transform, w, h, focal)
+    cam = ob.make_camera(transform, w, h, focal, fy)
     opt = ob.default_options(**opt_kw)
     D, T, ds = (np.zeros((h, w), np.float32) for _ in range(3))
     stop = np.zeros((h, w), np.uint8)

@@ -1,6 +1,7 @@
 """Shared helpers for the parity tests: seeded scenes + oracle/kernel runners."""
 from __future__ import annotations
 
+import dataclasses
 import hashlib
 import json
 import os
@@ -86,9 +87,9 @@ def camera_for(pose_idx=1, n_poses=8, size=96, focal=None, phi=-30.0, radius=4.0
 
 
 def oracle_frame(tree, transform, w, h, focal, fp_mode=ob.FP_STRICT, ndc=None, region=None,
-                 offscreen=True, rgba_init=None, depth_init=None, **opt_kw):
+                 offscreen=True, rgba_init=None, depth_init=None, fy=None, **opt_kw):
     th = ob.TreeHandle(tree, ndc=ndc)
-    cam = ob.make_camera(transform, w, h, focal)
+    cam = ob.make_camera(transform, w, h, focal, fy)
     opt = ob.default_options(**opt_kw)
     return ob.render(th, cam, opt, fp_mode, region=region, offscreen=offscreen,
                      rgba_init=rgba_init, depth_init=depth_init)
@@ -443,3 +444,61 @@ def edge_probe_point(tree, seed=0):
         if not np.isfinite(out[:3 * max(tree.basis_dim, 1)]).all():
             return p
     raise AssertionError("no leaf with a non-finite coefficient found")
+
+
+# ---- asymmetric geometry: no two of scale[3], offset[3], (fx, fy), (ndc width, height, focal) equal ----
+ASYM_FACTORS = (0.7, 1.3, 0.45)
+ASYM_OFFSET = (0.42, 0.55, 0.61)
+ASYM_FORMATS = [("SH", 1), ("SH", 9), ("SH", 16), ("SH", 25), ("RGBA", 0), ("SG", 4), ("ASG", 4)]
+ASYM_OPTIONS = {
+    "plain": {},
+    "rot_dirs": dict(rot_dirs=(0.3, -0.2, 0.9)),
+    "depth": dict(render_depth=1),
+    "bbox": dict(render_bbox=(0.1, 0.2, 0.0, 0.8, 0.9, 0.7)),
+}
+ASYM_PROBE = (0.1, -0.15, 0.2)
+
+
+def asymmetric(tree, factors=ASYM_FACTORS, offset=ASYM_OFFSET):
+    """``tree`` with a scale and an offset that differ on every axis: invradius3 * factors (float32, one
+    rounding) and the given offset.  Nodes and records are shared with ``tree``."""
+    scale = np.asarray(tree.invradius3, np.float32) * np.asarray(factors, np.float32)
+    return dataclasses.replace(tree, invradius3=scale.astype(np.float32), offset=np.asarray(offset, np.float32))
+
+
+def asymmetric_camera():
+    """-> (transform, w, h, fx, fy): pose 2 of the orbit on a 64 x 48 frame with fx = 1.2 f, fy = 0.7 f."""
+    tr, _, _, f = camera_for(pose_idx=2, size=64)
+    return tr, 64, 48, 1.2 * f, 0.7 * f
+
+
+def asymmetric_scene(fmt="SH", basis_dim=9, depth=5):
+    """The asymmetric tree of a format (a seeded small_scene) -- one per format for every test that names it."""
+    return asymmetric(small_scene(depth=depth, basis_dim=basis_dim, fmt=fmt, seed=300 + basis_dim))
+
+
+def asymmetric_ndc_case(basis_dim=4):
+    """-> (tree, transform, w, h, fx, fy, ndc): an NDC tree whose scale, offset, camera and NDC numbers all
+    differ from each other (ndc = width, height, focal; none is the camera's own)."""
+    from tests import aov_util
+    tree = dataclasses.replace(small_scene(depth=5, basis_dim=basis_dim, seed=351),
+                               invradius3=np.array([0.4, 0.55, 0.3], np.float32),
+                               offset=np.array([0.45, 0.52, 0.58], np.float32))
+    return tree, aov_util.NDC_TRANSFORM.copy(), 96, 72, 80.0, 65.0, (120.0, 60.0, 95.0)
+
+
+def non_orthonormal(transform):
+    """The pose mirrored (``right`` negated: a left-handed frame, as other pose conventions produce) and
+    sheared in length (``up`` x 1.7).  The reference normalises the direction after the matrix product."""
+    tr = np.array(transform, np.float32).copy()
+    tr[0:3] = -tr[0:3]
+    tr[3:6] = tr[3:6] * np.float32(1.7)
+    return tr
+
+
+def mesh_underlay(w, h, seed=5):
+    """-> (rgba uint8 [h, w, 4], depth float32 [h, w]): a frame to composite over and a mesh depth plane that
+    ends part of the rays inside the volume."""
+    rng = np.random.default_rng(seed)
+    return (rng.integers(0, 256, size=(h, w, 4), dtype=np.uint8),
+            rng.uniform(2.0, 6.0, size=(h, w)).astype(np.float32))

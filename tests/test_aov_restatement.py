@@ -15,14 +15,14 @@ from tests import common
 from tests.common import ob
 
 
-def tie(tree, tr, w, h, f, fp_mode, ndc=None, offscreen=True, depth_init=None, **kw):
+def tie(tree, tr, w, h, f, fp_mode, ndc=None, offscreen=True, depth_init=None, fy=None, **kw):
     D, T, ds, stop = au.restate(tree, tr, w, h, f, fp_mode, ndc=ndc, offscreen=offscreen, depth_init=depth_init,
-                                **kw)
+                                fy=fy, **kw)
     init = np.zeros((h, w, 4), np.uint8) if not offscreen else None
     _, acc_d, _ = common.oracle_frame(tree, tr, w, h, f, fp_mode, ndc=ndc, offscreen=offscreen, rgba_init=init,
-                                      depth_init=depth_init, render_depth=1, **kw)
+                                      depth_init=depth_init, fy=fy, render_depth=1, **kw)
     _, acc_c, _ = common.oracle_frame(tree, tr, w, h, f, fp_mode, ndc=ndc, offscreen=offscreen, rgba_init=init,
-                                      depth_init=depth_init, **kw)
+                                      depth_init=depth_init, fy=fy, **kw)
     one = np.float32(1)
     with np.errstate(all="ignore"):
         v = np.fmin((D * np.float32(0.3)).astype(np.float32), one)   # the oracle's vr_minf: min(NaN, 1) = 1
@@ -65,3 +65,21 @@ def test_restatement_on_an_ndc_tree(fp_mode):
     tree = common.small_scene(depth=5, basis_dim=4, seed=51)
     D, T, stop = check(tree, au.NDC_TRANSFORM, 96, 72, 80.0, fp_mode, ndc=au.NDC)
     assert (D != 0).any()
+
+
+@pytest.mark.parametrize("fp_mode", [ob.FP_STRICT, ob.FP_FMA], ids=["strict", "fma"])
+def test_restatement_under_asymmetric_geometry(fp_mode):
+    """Scale and offset that differ per axis, fx != fy: delta_scale is a different number for every ray."""
+    tr, w, h, fx, fy = common.asymmetric_camera()
+    D, T, stop = check(common.asymmetric_scene(), tr, w, h, fx, fp_mode, fy=fy)
+    assert (D != 0).mean() >= 0.2 and stop.any()
+    init_depth = common.mesh_underlay(w, h)[1]
+    Dm, _, _ = check(common.asymmetric_scene(), tr, w, h, fx, fp_mode, fy=fy, offscreen=False, depth_init=init_depth)
+    assert not np.array_equal(Dm, D), "the mesh depth must cut some rays short"
+
+
+@pytest.mark.parametrize("fp_mode", [ob.FP_STRICT, ob.FP_FMA], ids=["strict", "fma"])
+def test_restatement_on_the_asymmetric_ndc_tree(fp_mode):
+    tree, tr, w, h, fx, fy, ndc = common.asymmetric_ndc_case()
+    D, T, stop = check(tree, tr, w, h, fx, fp_mode, fy=fy, ndc=ndc)
+    assert (D != 0).mean() >= 0.2

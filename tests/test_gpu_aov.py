@@ -30,13 +30,14 @@ def _f32(t):
 
 
 def render_both(torch, t, w, h, f, trs, fp_mode=0, units="tree", offscreen=True, rgba_init=None,
-                depth_init=None, shard=None, stream=None, want=("depth", "transmittance"), pad_words=0, **opt_kw):
+                depth_init=None, shard=None, stream=None, want=("depth", "transmittance"), pad_words=0, fy=None,
+                **opt_kw):
     """One vr_render_batch launch and one vr_render_aov launch of the same arguments.
     -> dict(img0, acc0, img1, acc1, depth, trans) as numpy arrays; planes [n, h, w + pad_words] float32
     (SENTINEL where never written), depth / trans None when not asked for."""
     from volrend_amd import api
     n = len(trs)
-    cam = api.Camera(w, h, f, f)
+    cam = api.Camera(w, h, f, f if fy is None else fy)
     opts = api.RenderOptions(**opt_kw)
     out = {}
     depths = None if depth_init is None else [torch.from_numpy(depth_init).cuda() for _ in range(n)]
@@ -69,17 +70,18 @@ def assert_colour_unchanged(r, what=""):
 
 
 def check(torch, tree, trs, w, h, f, fp_mode=0, ndc=None, units=("tree", "world"), offscreen=True,
-          rgba_init=None, depth_init=None, tree_tuning=None, **opt_kw):
+          rgba_init=None, depth_init=None, tree_tuning=None, fy=None, **opt_kw):
     """Upload, launch per depth unit, compare every pixel of every frame with the restatement."""
     from volrend_amd import api
     t = api.N3Tree.from_synth(tree, ndc=ndc)
     if tree_tuning:
         t.set_tuning(**tree_tuning)
-    want = [au.restate(tree, tr, w, h, f, fp_mode, ndc=ndc, offscreen=offscreen, depth_init=depth_init, **opt_kw)
+    want = [au.restate(tree, tr, w, h, f, fp_mode, ndc=ndc, offscreen=offscreen, depth_init=depth_init, fy=fy,
+                       **opt_kw)
             for tr in trs]
     try:
         for u in units:
-            r = render_both(torch, t, w, h, f, trs, fp_mode, u, offscreen, rgba_init, depth_init, **opt_kw)
+            r = render_both(torch, t, w, h, f, trs, fp_mode, u, offscreen, rgba_init, depth_init, fy=fy, **opt_kw)
             assert_colour_unchanged(r, u)
             for i, (D, T, ds, _) in enumerate(want):
                 au.assert_same_bits(r["depth"][i], D if u == "tree" else au.world_depth(D, ds), f"depth[{u}] frame {i}")

@@ -141,3 +141,43 @@ def test_headless_cli_tile_shard(cli, tmp_path):
         r = subprocess.run([cli, npz, paths[0], "-w", "64", "-h", "64", "--gpus", "2"],
                            capture_output=True, text=True, timeout=120)
         assert r.returncode == 1 and "need more GPUs" in r.stderr
+
+
+def test_headless_cli_asymmetric_geometry(cli, tmp_path):
+    """A tree.npz with three distinct invradius3 values and an offset that differs per axis; an intrinsics.txt
+    whose K[1][1] is not K[0][0]; then --fx / --fy with --scale 0.5 down to a 64 x 48 frame from sizes the
+    scale does not divide (fx and fy are rescaled by different factors)."""
+    from PIL import Image
+    tree = common.asymmetric_scene()
+    assert len(set(tree.invradius3.tolist())) == 3 and len(set(tree.offset.tolist())) == 3
+    npz = str(tmp_path / "tree.npz")
+    synth.save_npz(tree, npz, compressed=True)
+    poses = synth.make_poses(8)[1:4]
+    w, h, fx, fy = 64, 48, 1.2 * 90.0, 0.7 * 90.0
+    paths = synth.write_pose_dir(str(tmp_path), poses, w, fx)
+    K = np.diag([fx, fy, 1.0, 1.0])
+    K[:2, 2] = [w / 2.0, h / 2.0]
+    np.savetxt(str(tmp_path / "intrinsics.txt"), K)
+    th = ob.TreeHandle(tree)
+
+    def check(out_dir, cam_fx, cam_fy):
+        for i, pose in enumerate(poses):
+            img = np.asarray(Image.open(os.path.join(out_dir, f"{i:04d}.png")))
+            cam = ob.make_camera(synth.c2w_to_transform(pose), w, h, cam_fx, cam_fy)
+            want, _, _ = ob.render(th, cam, ob.default_options(), want_accum=False)
+            assert img.shape == (h, w, 4)
+            assert np.array_equal(img, want), (out_dir, i)
+            assert (want[..., :3] != 255).any(-1).mean() >= 0.2, "the camera must see the volume"
+
+    out_dir = str(tmp_path / "o1")
+    r = subprocess.run([cli, npz, *paths, "-w", str(w), "-h", str(h), "-i", str(tmp_path / "intrinsics.txt"),
+                        "-o", out_dir], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    check(out_dir, fx, fy)
+    # --scale: (int)(129 * 0.5) = 64, (int)(97 * 0.5) = 48; fx *= 64.f / 129, fy *= 48.f / 97 in float
+    out_dir = str(tmp_path / "o2")
+    r = subprocess.run([cli, npz, *paths, "--width", "129", "--height", "97", "--fx", "217.5", "--fy", "127.25",
+                        "--scale", "0.5", "-o", out_dir], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    f32 = np.float32
+    check(out_dir, f32(217.5) * (f32(64) / f32(129)), f32(127.25) * (f32(48) / f32(97)))

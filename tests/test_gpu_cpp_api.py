@@ -59,10 +59,11 @@ def test_cpp_launch_renderer_matches_oracle(exe, tmp_path, case, mode):
     assert (got[..., :3] != 255).any()
 
 
-def _run(exe, tmp_path, tree, poses, w, h, f, mode, spec_opts, oracle_opts):
+def _run(exe, tmp_path, tree, poses, w, h, f, mode, spec_opts, oracle_opts, fy=None):
     npz = str(tmp_path / "t.npz")
     synth.save_npz(tree, npz, compressed=False)
-    spec = [f"size {w} {h} {f!r} {f!r}", f"mode {mode}"]
+    fy = f if fy is None else fy
+    spec = [f"size {w} {h} {f!r} {fy!r}", f"mode {mode}"]
     for k, v in spec_opts.items():
         vals = v if isinstance(v, (tuple, list)) else (v,)
         spec.append(k + " " + " ".join(repr(float(x)) if isinstance(x, float) else str(int(x))
@@ -76,6 +77,18 @@ def _run(exe, tmp_path, tree, poses, w, h, f, mode, spec_opts, oracle_opts):
     assert r.returncode == 0, r.stdout + r.stderr
     got = np.fromfile(raw, dtype=np.uint8).reshape(len(poses), h, w, 4)
     for i, p in enumerate(poses):
-        want, _, _ = common.oracle_frame(tree, p, w, h, f, **oracle_opts)
+        want, _, _ = common.oracle_frame(tree, p, w, h, f, fy=fy, **oracle_opts)
         assert np.array_equal(got[i], want), f"{mode} frame {i}: differs from the oracle"
     return got
+
+
+@pytest.mark.parametrize("mode", ["single", "batch"])
+def test_cpp_launch_renderer_asymmetric_geometry(exe, tmp_path, mode):
+    """A tree.npz whose invradius3 and offset differ on every axis, fx != fy on a 64 x 48 frame, the orbit
+    pose and its mirrored, stretched form: N3Tree::open and launch_renderer carry each number to its own
+    axis (tests/common.py asymmetric)."""
+    tree = common.asymmetric_scene()
+    tr, w, h, fx, fy = common.asymmetric_camera()
+    opts = dict(rot_dirs=(0.3, -0.2, 0.9), render_bbox=(0.1, 0.2, 0.0, 0.8, 0.9, 0.7))
+    got = _run(exe, tmp_path, tree, [tr, common.non_orthonormal(tr)], w, h, fx, mode, opts, opts, fy=fy)
+    assert ((got[..., :3] != 255).any(-1).mean((1, 2)) >= 0.2).all()

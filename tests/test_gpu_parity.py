@@ -23,10 +23,10 @@ def torch_cuda():
 
 
 def gpu_frame(torch, tree, transform, w, h, focal, fp_mode=0, ndc=None, offscreen=True,
-              rgba_init=None, depth_init=None, shard=None, **opt_kw):
+              rgba_init=None, depth_init=None, shard=None, fy=None, **opt_kw):
     from volrend_amd import api
     t = api.N3Tree.from_synth(tree, ndc=ndc)
-    cam = api.Camera(w, h, focal, focal)
+    cam = api.Camera(w, h, focal, focal if fy is None else fy)
     cam.transform = np.asarray(transform, dtype=np.float32)
     opts = api.RenderOptions(**opt_kw)
     if rgba_init is not None:

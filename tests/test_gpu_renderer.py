@@ -98,3 +98,34 @@ def test_volume_renderer_matches_oracle_compositing(exe, tmp_path, underlay, bri
     assert hit == len(CAMS), "every camera must see the volume"
     # clear(): render() without a tree leaves the cleared frame / the underlay
     assert np.array_equal(got[-1], rgba0)
+
+
+def test_volume_renderer_asymmetric_geometry(exe, tmp_path):
+    """A tree whose scale and offset differ on every axis under fx != fy on a 64 x 48 frame, composited over a
+    mesh underlay whose depth ends part of the rays (tmax / delta_scale, with a delta_scale per ray)."""
+    tree = common.asymmetric_scene()
+    w, h = 64, 48
+    fx, fy = 1.2 * 90.0, 0.7 * 90.0
+    npz = str(tmp_path / "t.npz")
+    synth.save_npz(tree, npz, compressed=False)
+    rgba0, depth0 = common.mesh_underlay(w, h)
+    rgba0[..., 3] = 255
+    rgba0.tofile(str(tmp_path / "u_rgba.raw"))
+    depth0.tofile(str(tmp_path / "u_depth.raw"))
+    spec = [f"size {w} {h} {fx!r} {fy!r}", f"underlay {tmp_path / 'u_rgba.raw'} {tmp_path / 'u_depth.raw'}"]
+    spec += ["cam " + " ".join(repr(float(x)) for x in c) for c in CAMS]
+    sp = str(tmp_path / "spec.txt")
+    open(sp, "w").write("\n".join(spec) + "\n")
+    raw = str(tmp_path / "out.raw")
+    r = subprocess.run([exe, npz, sp, raw], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout + r.stderr
+    transforms = [np.array([float(x) for x in l.split()[1:]], dtype=np.float32)
+                  for l in r.stdout.splitlines() if l.startswith("transform")]
+    assert len(transforms) == len(CAMS)
+    got = np.fromfile(raw, dtype=np.uint8).reshape(len(CAMS) + 1, h, w, 4)
+    for i, tr in enumerate(transforms):
+        kw = dict(offscreen=False, rgba_init=rgba0, fy=fy, basis_minmax=(0, tree.basis_dim - 1))
+        want, _, _ = common.oracle_frame(tree, tr, w, h, fx, depth_init=depth0, **kw)
+        assert np.array_equal(got[i], want), f"frame {i}: differs from the oracle's compositing path"
+        assert (want != rgba0).any(-1).mean() >= 0.2, "the camera must see the volume"
+        assert not np.array_equal(want, common.oracle_frame(tree, tr, w, h, fx, **kw)[0]), "the depth cuts no ray"

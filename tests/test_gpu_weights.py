@@ -43,11 +43,12 @@ def host(t):
 
 
 def accumulate(torch, t, w, h, f, trs, fp_mode=0, want=("max_weight", "hits"), stream=None, mw=None, hc=None,
-               tree=None, **opt_kw):
+               tree=None, fy=None, **opt_kw):
     from volrend_amd import api
     if mw is None and hc is None:
         mw, hc = buffers(torch, tree, want)
-    t.accumulate_weights(api.Camera(w, h, f, f), trs, api.RenderOptions(**opt_kw), max_weight=mw, hits=hc,
+    cam = api.Camera(w, h, f, f if fy is None else fy)
+    t.accumulate_weights(cam, trs, api.RenderOptions(**opt_kw), max_weight=mw, hits=hc,
                          want=(), fp_mode=fp_mode, stream=stream)
     return mw, hc
 

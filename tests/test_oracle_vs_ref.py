@@ -16,9 +16,9 @@ from tests import common
 from tests.common import assert_ref_equal, ob, ref_array
 
 
-def both(key, tree, tr, w, h, f, ndc=None, msg="", **opt_kw):
+def both(key, tree, tr, w, h, f, ndc=None, msg="", fy=None, **opt_kw):
     th = ob.TreeHandle(tree, ndc=ndc)
-    cam = ob.make_camera(tr, w, h, f)
+    cam = ob.make_camera(tr, w, h, f, fy)
     opt = ob.default_options(**opt_kw)
     rgba_o, acc_o, _ = ob.render(th, cam, opt, ob.FP_STRICT)
     assert_ref_equal(key + "/rgba", rgba_o, lambda: ob.ref_render(th, cam, opt), msg=msg)
@@ -277,3 +277,96 @@ def test_fog_bit_exact(request, case):
     tree, tr, w, h, f, kw = common.fog_case(case)
     rgba_o, acc_o, (th, cam, opt) = both(request.node.name, tree, tr, w, h, f, **kw)
     assert_accum_equal(request.node.name, acc_o, th, cam, opt)
+
+
+# ---- asymmetric geometry (tests/common.py): scale, offset, fx / fy and the NDC numbers all differ per axis ----
+ASYM_CASES = [f"{fmt}{bd}-{o}" for fmt, bd in common.ASYM_FORMATS for o in common.ASYM_OPTIONS] + \
+    ["ndc", "non_orthonormal", "compositing", "probe"]
+
+
+@pytest.mark.parametrize("case", ASYM_CASES)
+def test_asymmetric_geometry_bit_exact(request, case):
+    """A tree whose scale and offset differ on every axis under a camera with fx != fy (and, for the NDC
+    tree, ndc width / height / focal that are neither each other's nor the camera's): an index mix-up in
+    the ray set-up, or a per-ray delta_scale taken for a constant, shows here and nowhere else."""
+    key = request.node.name
+    tr, w, h, fx, fy = common.asymmetric_camera()
+    if case == "ndc":
+        tree, tr, w, h, fx, fy, ndc = common.asymmetric_ndc_case()
+        rgba_o, acc_o, (th, cam, opt) = both(key, tree, tr, w, h, fx, ndc=ndc, fy=fy)
+    elif case == "non_orthonormal":
+        rgba_o, acc_o, (th, cam, opt) = both(key, common.asymmetric_scene(), common.non_orthonormal(tr), w, h, fx, fy=fy)
+    elif case == "compositing":
+        th = ob.TreeHandle(common.asymmetric_scene())
+        cam, opt = ob.make_camera(tr, w, h, fx, fy), ob.default_options()
+        init, depth = common.mesh_underlay(w, h)
+        rgba_o, _, _ = ob.render(th, cam, opt, offscreen=False, rgba_init=init, depth_init=depth)
+        assert_ref_equal(key + "/rgba", rgba_o,
+                         lambda: ob.ref_render(th, cam, opt, offscreen=False, rgba_init=init, depth_init=depth))
+        free, _, _ = ob.render(th, cam, opt, offscreen=False, rgba_init=init)
+        assert not np.array_equal(rgba_o, free), "the mesh depth must cut some rays short"
+        return
+    elif case == "probe":
+        tree = common.asymmetric_scene()
+        rgba_o, acc_o, (th, cam, opt) = both(key, tree, tr, w, h, fx, fy=fy, enable_probe=1, probe=common.ASYM_PROBE,
+                                             probe_disp_size=30, basis_minmax=(0, tree.basis_dim - 1))
+        a = np.zeros(tree.data_dim - 1, np.float32)
+        ob.lib().or_probe_coeffs(C.byref(th.struct), C.byref(opt), a.ctypes.data)
+
+        def ref_coeffs():
+            b = np.zeros(tree.data_dim - 1, np.float32)
+            ob.ref_lib().ref_probe_coeffs(C.byref(th.struct), C.byref(opt), b.ctypes.data)
+            return b.view(np.uint32)
+        assert_ref_equal(key + "/probe_coeffs", a.view(np.uint32), ref_coeffs)
+        return                         # (ref_trace has no overlay: RGBA8 and the coefficients are the pin)
+    else:
+        name, o = case.split("-")
+        fmt, bd = next(f for f in common.ASYM_FORMATS if f"{f[0]}{f[1]}" == name)
+        rgba_o, acc_o, (th, cam, opt) = both(key, common.asymmetric_scene(fmt, bd), tr, w, h, fx, fy=fy,
+                                             **common.ASYM_OPTIONS[o])
+    assert_accum_equal(key, acc_o, th, cam, opt)
+    assert (acc_o[..., 3] != 0).mean() >= 0.2, "the case shows too little"
+
+
+def _swapped(v, i, j):
+    v = np.array(v, np.float32).copy()
+    v[[i, j]] = v[[j, i]]
+    return v
+
+
+def test_asymmetric_cases_have_teeth():
+    """Every mix-up the asymmetric cases are there to catch changes the oracle's accumulators on at least
+    half of the pixels either frame hits, with at least a fifth of the frame hit -- conditions on the
+    cases, checked on the oracle alone."""
+    import dataclasses
+    from tests import aov_util as au
+    tree = common.asymmetric_scene()
+    tr, w, h, fx, fy = common.asymmetric_camera()
+    s, o = tree.invradius3, tree.offset
+    base = common.oracle_frame(tree, tr, w, h, fx, fy=fy)[1]
+    rep = dataclasses.replace
+    changes = {
+        "fy := fx": (tree, fx, fx),
+        "fx <-> fy": (tree, fy, fx),
+        "scale x <-> y": (rep(tree, invradius3=_swapped(s, 0, 1)), fx, fy),
+        "scale y <-> z": (rep(tree, invradius3=_swapped(s, 1, 2)), fx, fy),
+        "scale := scale[0]": (rep(tree, invradius3=np.full(3, s[0], np.float32)), fx, fy),
+        "offset x <-> y": (rep(tree, offset=_swapped(o, 0, 1)), fx, fy),
+        "offset y <-> z": (rep(tree, offset=_swapped(o, 1, 2)), fx, fy),
+    }
+    frames = {k: (base, common.oracle_frame(t, tr, w, h, a, fy=b)[1]) for k, (t, a, b) in changes.items()}
+    ntree, ntr, nw, nh, nfx, nfy, (ndw, ndh, ndf) = common.asymmetric_ndc_case()
+    nbase = common.oracle_frame(ntree, ntr, nw, nh, nfx, fy=nfy, ndc=(ndw, ndh, ndf))[1]
+    for k, ndc in (("ndc_width <-> ndc_height", (ndh, ndw, ndf)), ("ndc_focal := fx", (ndw, ndh, nfx))):
+        frames[k] = (nbase, common.oracle_frame(ntree, ntr, nw, nh, nfx, fy=nfy, ndc=ndc)[1])
+    for k, (a, b) in frames.items():
+        hit = (a[..., 3] != 0) | (b[..., 3] != 0)
+        differ = (a.view(np.uint32) != b.view(np.uint32)).any(-1)
+        print(f"{k}: hit share {hit.mean():.2f}, differing share of the hit pixels {differ[hit].mean():.2f}")
+        assert hit.mean() >= 0.2, f"{k}: only {hit.mean():.2f} of the frame is hit"
+        assert differ[hit].mean() >= 0.5, f"{k}: only {differ[hit].mean():.2f} of the hit pixels differ"
+    # delta_scale is per-ray state under this tree: it spans more than 10 % and takes > 500 values
+    ds = au.restate(tree, tr, w, h, fx, fy=fy)[2]
+    print(f"delta_scale: {np.unique(ds.view(np.uint32)).size} values, spread {(ds.max() - ds.min()) / ds.min():.3f}")
+    assert (ds.max() - ds.min()) / ds.min() > 0.10
+    assert np.unique(ds.view(np.uint32)).size > 500

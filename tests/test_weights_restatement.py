@@ -18,13 +18,13 @@ from tests.common import ob
 FP = pytest.mark.parametrize("fp_mode", [ob.FP_STRICT, ob.FP_FMA], ids=["strict", "fma"])
 
 
-def tie(tree, tr, w, h, f, fp_mode, ndc=None, **kw):
-    r = wu.restate_frame(tree, tr, w, h, f, fp_mode, ndc=ndc, **kw)
-    D, T, _, stop = au.restate(tree, tr, w, h, f, fp_mode, ndc=ndc, **kw)
+def tie(tree, tr, w, h, f, fp_mode, ndc=None, fy=None, **kw):
+    r = wu.restate_frame(tree, tr, w, h, f, fp_mode, ndc=ndc, fy=fy, **kw)
+    D, T, _, stop = au.restate(tree, tr, w, h, f, fp_mode, ndc=ndc, fy=fy, **kw)
     au.assert_same_bits(r["D"], D, "D")
     au.assert_same_bits(r["T"], T, "T")
     assert np.array_equal(r["stop"], stop)
-    counters = common.oracle_frame(tree, tr, w, h, f, fp_mode, ndc=ndc, **kw)[2]
+    counters = common.oracle_frame(tree, tr, w, h, f, fp_mode, ndc=ndc, fy=fy, **kw)[2]
     assert int(r["hits"].sum(dtype=np.uint64)) == counters["hit_samples"]
     # the rule itself, on what the restatement returned
     assert not np.isnan(r["max_weight"]).any() and (r["max_weight"] >= 0).all()
@@ -72,3 +72,18 @@ def test_restatement_on_an_ndc_tree(fp_mode):
     tree = common.small_scene(depth=5, basis_dim=4, seed=51)
     r = tie(tree, au.NDC_TRANSFORM, 96, 72, 80.0, fp_mode, ndc=au.NDC)
     assert (r["max_weight"] > 0).any()
+
+
+@FP
+def test_restatement_under_asymmetric_geometry(fp_mode):
+    """Scale and offset that differ per axis, fx != fy: delta_scale is a different number for every ray."""
+    tr, w, h, fx, fy = common.asymmetric_camera()
+    r = tie(common.asymmetric_scene(), tr, w, h, fx, fp_mode, fy=fy)
+    assert (r["max_weight"] > 0).sum() > 500 and r["stop"].any()
+
+
+@FP
+def test_restatement_on_the_asymmetric_ndc_tree(fp_mode):
+    tree, tr, w, h, fx, fy, ndc = common.asymmetric_ndc_case()
+    r = tie(tree, tr, w, h, fx, fp_mode, fy=fy, ndc=ndc)
+    assert (r["max_weight"] > 0).sum() > 500

@@ -43,12 +43,12 @@ def slots_shape(tree):
     return (tree.capacity, tree.N, tree.N, tree.N)
 
 
-def restate_frame(tree, transform, w, h, focal, fp_mode=0, ndc=None, max_weight=None, hits=None, **opt_kw):
+def restate_frame(tree, transform, w, h, focal, fp_mode=0, ndc=None, max_weight=None, hits=None, fy=None, **opt_kw):
     """One frame, accumulated INTO max_weight (float32) / hits (uint32), both [capacity, N, N, N] in the
     file's numbering (allocated zeroed when None).
     -> dict(max_weight, hits, D, T, stop [h, w], nonpositive)."""
     th = ob.TreeHandle(tree, ndc=ndc)
-    cam = ob.make_camera(transform, w, h, focal)
+    cam = ob.make_camera(transform, w, h, focal, fy)
     opt = ob.default_options(**opt_kw)
     mw = np.zeros(slots_shape(tree), np.float32) if max_weight is None else max_weight
     hc = np.zeros(slots_shape(tree), np.uint32) if hits is None else hits
@@ -63,13 +63,13 @@ def restate_frame(tree, transform, w, h, focal, fp_mode=0, ndc=None, max_weight=
     return dict(max_weight=mw, hits=hc, D=D, T=T, stop=stop.astype(bool), nonpositive=int(bad.value))
 
 
-def restate(tree, transforms, w, h, focal, fp_mode=0, ndc=None, max_weight=None, hits=None, **opt_kw):
+def restate(tree, transforms, w, h, focal, fp_mode=0, ndc=None, max_weight=None, hits=None, fy=None, **opt_kw):
     """All frames into one pair of arrays -> (max_weight, hits, nonpositive over all frames)."""
     mw = np.zeros(slots_shape(tree), np.float32) if max_weight is None else max_weight.copy()
     hc = np.zeros(slots_shape(tree), np.uint32) if hits is None else hits.copy()
     bad = 0
     for tr in transforms:
-        bad += restate_frame(tree, tr, w, h, focal, fp_mode, ndc, mw, hc, **opt_kw)["nonpositive"]
+        bad += restate_frame(tree, tr, w, h, focal, fp_mode, ndc, mw, hc, fy=fy, **opt_kw)["nonpositive"]
     return mw, hc, bad
 
 
