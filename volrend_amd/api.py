@@ -608,6 +608,32 @@ def _depth_units(depth_units) -> int:
     return int(depth_units)
 
 
+def _fill_frame(f: "_abi.VrFrame", image, depth, accum, counters, offscreen: bool, pitch: int,
+                shard: TileShard | None, fp_mode: int) -> None:
+    """The ``VrFrame`` of one pose, into ``f``."""
+    _abi.lib().vr_default_frame(C.byref(f))
+    f.rgba = _ptr(image)
+    f.pitch = pitch
+    f.depth = _ptr(depth)
+    f.accum = _ptr(accum)
+    f.offscreen = 1 if offscreen else 0
+    f.fp_mode = fp_mode
+    f.counters = _ptr(counters)  # device int64[7], zeroed by the caller (instrumentation)
+    if shard is not None:
+        f.tile_w, f.tile_h, f.rank, f.world = shard.tile_w, shard.tile_h, shard.rank, shard.world
+        f.layout = _abi.LAYOUT_COMPACT if shard.compact else _abi.LAYOUT_FRAME
+
+
+def _cameras_c(cam: Camera, transforms):
+    """``cam`` at every pose of ``transforms`` (12 floats each) as a ``VrCamera`` array.  ``cam.transform``
+    is left at the last pose."""
+    cams = (_abi.VrCamera * len(transforms))()
+    for i, tr in enumerate(transforms):
+        cam.transform = np.asarray(tr, dtype=np.float32)
+        cams[i] = cam.to_c()
+    return cams
+
+
 def launch_renderer(tree: N3Tree, cam: Camera, options: RenderOptions, image, depth=None,
                     stream=None, offscreen: bool = False, *, accum=None, pitch: int = 0,
                     shard: TileShard | None = None, fp_mode: int = _abi.FP_STRICT,
@@ -622,17 +648,7 @@ def launch_renderer(tree: N3Tree, cam: Camera, options: RenderOptions, image, de
     """
     f = _abi.VrFrame()
     L = _abi.lib()
-    L.vr_default_frame(C.byref(f))
-    f.rgba = _ptr(image)
-    f.pitch = pitch
-    f.depth = _ptr(depth)
-    f.accum = _ptr(accum)
-    f.offscreen = 1 if offscreen else 0
-    f.fp_mode = fp_mode
-    f.counters = _ptr(counters)  # device int64[7], zeroed by the caller (instrumentation)
-    if shard is not None:
-        f.tile_w, f.tile_h, f.rank, f.world = shard.tile_w, shard.tile_h, shard.rank, shard.world
-        f.layout = _abi.LAYOUT_COMPACT if shard.compact else _abi.LAYOUT_FRAME
+    _fill_frame(f, image, depth, accum, counters, offscreen, pitch, shard, fp_mode)
     c = cam.to_c()
     o = options.to_c()
     if aov is not None:
@@ -658,9 +674,8 @@ class PreparedBatch:
             raise ValueError("one image per pose")
         if aov is not None and len(aov) != n:
             raise ValueError("one AovPlanes per pose")
-        L = _abi.lib()
         self.tree, self.n = tree, n
-        self.cams = (_abi.VrCamera * n)()
+        self.cams = _cameras_c(cam, transforms)
         self.frames = (_abi.VrFrame * n)()
         self._keep = (images, accums, depths, counters, aov)  # the buffers must outlive the launch
         # aov: one AovPlanes per pose -> launch() is vr_render_aov instead of vr_render_batch
@@ -670,21 +685,8 @@ class PreparedBatch:
             for i in range(n):
                 self.aovs[i] = _aov_c(aov[i])
         for i in range(n):
-            cam.transform = np.asarray(transforms[i], dtype=np.float32)
-            self.cams[i] = cam.to_c()
-            f = self.frames[i]
-            L.vr_default_frame(C.byref(f))
-            f.rgba = _ptr(images[i])
-            f.pitch = pitch
-            f.depth = _ptr(depths[i]) if depths else None
-            f.accum = _ptr(accums[i]) if accums else None
-            f.offscreen = 1 if offscreen else 0
-            f.fp_mode = fp_mode
-            f.counters = _ptr(counters[i]) if counters else None
-            if shard is not None:
-                f.tile_w, f.tile_h, f.rank, f.world = (shard.tile_w, shard.tile_h, shard.rank,
-                                                       shard.world)
-                f.layout = _abi.LAYOUT_COMPACT if shard.compact else _abi.LAYOUT_FRAME
+            _fill_frame(self.frames[i], images[i], depths[i] if depths else None, accums[i] if accums else None,
+                        counters[i] if counters else None, offscreen, pitch, shard, fp_mode)
         self.opts = options.to_c()
 
     def launch(self, stream=None) -> None:
@@ -742,10 +744,7 @@ def accumulate_weights(tree, cam: Camera, transforms, options: RenderOptions, *,
     n = len(transforms)
     for first in range(0, max(n, 1), _abi.MAX_BATCH):
         m = min(_abi.MAX_BATCH, n - first)
-        cams = (_abi.VrCamera * m)() if m else None
-        for i in range(m):
-            cam.transform = np.asarray(transforms[first + i], dtype=np.float32)
-            cams[i] = cam.to_c()
+        cams = _cameras_c(cam, [transforms[first + i] for i in range(m)]) if m else None
         _abi.check(L.vr_accumulate_weights(tree.handle, m, cams, C.byref(o), int(fp_mode), C.byref(out),
                                            _stream_ptr(stream)))
     return res

@@ -43,17 +43,61 @@ VrCamera to_c(const Camera& cam, const float* transform12) {
     return c;
 }
 
+VrAov to_c(const AovPlanes& a) {
+    VrAov c;
+    c.depth = a.depth;
+    c.transmittance = a.transmittance;
+    c.pitch = a.pitch;
+    return c;
+}
+
+VrFrame frame_to_c(void* image_rgba8_dev, const float* depth_dev, bool offscreen) {
+    VrFrame f;
+    vr_default_frame(&f);
+    f.rgba = image_rgba8_dev;
+    f.depth = depth_dev;
+    f.offscreen = offscreen ? 1 : 0;
+    return f;
+}
+
+// The poses in chunks of VR_MAX_BATCH, as cameras: launch(first, n, cams) once per chunk.
+template <class Launch>
+void for_camera_chunks(const Camera& cam, const std::vector<const float*>& transforms, Launch&& launch) {
+    for (size_t first = 0; first < transforms.size(); first += VR_MAX_BATCH) {
+        const int n = (int)std::min<size_t>(VR_MAX_BATCH, transforms.size() - first);
+        VrCamera cams[VR_MAX_BATCH];
+        for (int i = 0; i < n; ++i) cams[i] = to_c(cam, transforms[first + i]);
+        launch(first, n, cams);
+    }
+}
+
+// One launch per VR_MAX_BATCH poses: vr_render_batch, or with planes (one per pose) vr_render_aov.
+void render_batch(const N3Tree& tree, const Camera& cam, const std::vector<const float*>& transforms,
+                  const RenderOptions& options, const std::vector<void*>& images,
+                  const std::vector<AovPlanes>* aovs, DepthUnits depth_units, void* stream, bool offscreen) {
+    const VrRenderOptions o = to_c(options);
+    for_camera_chunks(cam, transforms, [&](size_t first, int n, const VrCamera* cams) {
+        VrFrame frames[VR_MAX_BATCH];
+        std::vector<VrAov> planes(aovs ? (size_t)n : 0);
+        for (int i = 0; i < n; ++i) {
+            frames[i] = frame_to_c(images[first + i], nullptr, offscreen);
+            if (aovs) planes[(size_t)i] = to_c((*aovs)[first + i]);
+        }
+        if (aovs)
+            internal::vr_check(vr_render_aov(tree.device, n, cams, &o, frames, planes.data(), (int)depth_units, stream),
+                               "vr_render_aov");
+        else
+            internal::vr_check(vr_render_batch(tree.device, n, cams, &o, frames, stream), "vr_render_batch");
+    });
+}
+
 }  // namespace
 
 void launch_renderer(const N3Tree& tree, const Camera& cam, const RenderOptions& options,
                      void* image_rgba8_dev, const float* depth_dev, void* stream, bool offscreen) {
     const VrCamera c = to_c(cam, glm::value_ptr(cam.transform));
     const VrRenderOptions o = to_c(options);
-    VrFrame f;
-    vr_default_frame(&f);
-    f.rgba = image_rgba8_dev;
-    f.depth = depth_dev;
-    f.offscreen = offscreen ? 1 : 0;
+    const VrFrame f = frame_to_c(image_rgba8_dev, depth_dev, offscreen);
     internal::vr_check(vr_render(tree.device, &c, &o, &f, stream), "vr_render");
 }
 
@@ -63,44 +107,19 @@ void launch_renderer_batch(const N3Tree& tree, const Camera& cam,
                            void* stream, bool offscreen) {
     if (transforms.size() != images.size())
         throw std::invalid_argument("launch_renderer_batch: one image per pose");
-    const VrRenderOptions o = to_c(options);
-    for (size_t first = 0; first < transforms.size(); first += VR_MAX_BATCH) {
-        const int n = (int)std::min<size_t>(VR_MAX_BATCH, transforms.size() - first);
-        VrCamera cams[VR_MAX_BATCH];
-        VrFrame frames[VR_MAX_BATCH];
-        for (int i = 0; i < n; ++i) {
-            cams[i] = to_c(cam, transforms[first + i]);
-            vr_default_frame(&frames[i]);
-            frames[i].rgba = images[first + i];
-            frames[i].offscreen = offscreen ? 1 : 0;
-        }
-        internal::vr_check(vr_render_batch(tree.device, n, cams, &o, frames, stream), "vr_render_batch");
-    }
+    render_batch(tree, cam, transforms, options, images, nullptr, DepthUnits{}, stream, offscreen);
 }
 
 void accumulate_weights(const N3Tree& tree, const Camera& cam, const std::vector<const float*>& transforms,
                         const RenderOptions& options, const LeafWeights& out, void* stream, int fp_mode) {
     const VrRenderOptions o = to_c(options);
-    size_t first = 0;
-    do {  // (no pose at all: one call with n = 0, the warm-up)
-        const int n = (int)std::min<size_t>(VR_MAX_BATCH, transforms.size() - first);
-        std::vector<VrCamera> cams((size_t)n);
-        for (int i = 0; i < n; ++i) cams[(size_t)i] = to_c(cam, transforms[first + i]);
-        internal::vr_check(vr_accumulate_weights(tree.device, n, n ? cams.data() : nullptr, &o, fp_mode, &out, stream),
+    const auto launch = [&](size_t, int n, const VrCamera* cams) {
+        internal::vr_check(vr_accumulate_weights(tree.device, n, cams, &o, fp_mode, &out, stream),
                            "vr_accumulate_weights");
-        first += VR_MAX_BATCH;
-    } while (first < transforms.size());
+    };
+    if (transforms.empty()) launch(0, 0, nullptr);  // (no pose at all: one call with n = 0, the warm-up)
+    else for_camera_chunks(cam, transforms, launch);
 }
-
-namespace {
-VrAov to_c(const AovPlanes& a) {
-    VrAov c;
-    c.depth = a.depth;
-    c.transmittance = a.transmittance;
-    c.pitch = a.pitch;
-    return c;
-}
-}  // namespace
 
 void launch_renderer_aov(const N3Tree& tree, const Camera& cam, const RenderOptions& options,
                          void* image_rgba8_dev, const float* depth_dev, const AovPlanes& aov,
@@ -108,11 +127,7 @@ void launch_renderer_aov(const N3Tree& tree, const Camera& cam, const RenderOpti
     const VrCamera c = to_c(cam, glm::value_ptr(cam.transform));
     const VrRenderOptions o = to_c(options);
     const VrAov a = to_c(aov);
-    VrFrame f;
-    vr_default_frame(&f);
-    f.rgba = image_rgba8_dev;
-    f.depth = depth_dev;
-    f.offscreen = offscreen ? 1 : 0;
+    const VrFrame f = frame_to_c(image_rgba8_dev, depth_dev, offscreen);
     internal::vr_check(vr_render_aov(tree.device, 1, &c, &o, &f, &a, (int)depth_units, stream), "vr_render_aov");
 }
 
@@ -122,22 +137,7 @@ void launch_renderer_aov_batch(const N3Tree& tree, const Camera& cam,
                                DepthUnits depth_units, void* stream, bool offscreen) {
     if (transforms.size() != images.size() || transforms.size() != aovs.size())
         throw std::invalid_argument("launch_renderer_aov_batch: one image and one AovPlanes per pose");
-    const VrRenderOptions o = to_c(options);
-    for (size_t first = 0; first < transforms.size(); first += VR_MAX_BATCH) {
-        const int n = (int)std::min<size_t>(VR_MAX_BATCH, transforms.size() - first);
-        VrCamera cams[VR_MAX_BATCH];
-        VrFrame frames[VR_MAX_BATCH];
-        std::vector<VrAov> planes((size_t)n);
-        for (int i = 0; i < n; ++i) {
-            cams[i] = to_c(cam, transforms[first + i]);
-            vr_default_frame(&frames[i]);
-            frames[i].rgba = images[first + i];
-            frames[i].offscreen = offscreen ? 1 : 0;
-            planes[(size_t)i] = to_c(aovs[first + i]);
-        }
-        internal::vr_check(vr_render_aov(tree.device, n, cams, &o, frames, planes.data(), (int)depth_units, stream),
-                           "vr_render_aov");
-    }
+    render_batch(tree, cam, transforms, options, images, &aovs, depth_units, stream, offscreen);
 }
 
 namespace {

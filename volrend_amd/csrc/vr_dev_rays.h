@@ -1,6 +1,7 @@
 // vr_dev_rays.h -- a ray from pixel to pixel: ray-id order, ray generation up to the ray/box test,
 // the compositing tail, the ray buffer raygen_kernel writes and render_kernel reads, and the ray
-// queues the persistent waves draw their chunks from.  Device code only.
+// queues ray generation compacts its rays into and the persistent waves draw their chunks from.
+// Device code only.
 #pragma once
 #include "vr_device_math.h"
 #include "vr_dev_layout.h"
@@ -362,6 +363,51 @@ __device__ __forceinline__ void grab_chunk(const KParams& p, int lane, uint32_t&
                 break;
             }
         }
+    }
+}
+
+// Ray generation's compaction (raygen_kernel, weights_raygen_kernel; GW = waves per workgroup, every
+// lane of the workgroup calls): m_valid = the wave's lanes whose ray enters the volume.  Returns the ray
+// slot of the wave's first such lane; the others follow by lane_rank(m_valid).
+// Wave ballot + mbcnt prefix inside the wave, a scan over the workgroup's waves, and
+// ONE atomic per workgroup on the count word of the queue that owns the workgroup's blocks (a
+// single word only sustains ~90 returning atomics per microsecond chip-wide; workgroups never
+// straddle a queue boundary: those lie at multiples of 16 blocks).
+template <int GW>
+__device__ __forceinline__ uint32_t reserve_ray_slots(const KParams& p, unsigned long long m_valid, int lane,
+                                                      int wave) {
+    __shared__ uint32_t wave_count[GW];
+    __shared__ uint32_t wave_base[GW];
+    const uint32_t nq = (uint32_t)p.n_queues;
+    uint32_t sh, n16;
+    queue_split(p, sh, n16);
+    const uint32_t g16 = (uint32_t)(((int64_t)blockIdx.x * GW) >> 4);  // this workgroup's group of 16 blocks
+    uint32_t qx = (uint32_t)(((uint64_t)g16 << sh) / n16);               // its queue: first guess, then exact
+    while (qx + 1u < nq && (queue_first_block(n16, qx + 1u, sh) >> 4) <= g16) ++qx;
+    while (qx > 0u && (queue_first_block(n16, qx, sh) >> 4) > g16) --qx;
+    uint32_t* const q_count = p.queue_head + qx * kQueueStride + kQueueCount;
+    const uint32_t q_base = queue_first_block(n16, qx, sh) << 6;
+    if constexpr (GW == 1) {
+        const uint32_t n = (uint32_t)__builtin_popcountll(m_valid);
+        uint32_t b = 0;
+        if (lane == 0 && n) b = atomicAdd(q_count, n);
+        return q_base + (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+    } else {
+        if (lane == 0) wave_count[wave] = (uint32_t)__builtin_popcountll(m_valid);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            uint32_t sum = 0;
+#pragma unroll
+            for (int w = 0; w < GW; ++w) {
+                wave_base[w] = sum;
+                sum += wave_count[w];
+            }
+            const uint32_t base = q_base + (sum ? atomicAdd(q_count, sum) : 0u);
+#pragma unroll
+            for (int w = 0; w < GW; ++w) wave_base[w] += base;
+        }
+        __syncthreads();
+        return wave_base[wave];
     }
 }
 

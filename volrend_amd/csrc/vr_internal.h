@@ -188,6 +188,22 @@ struct KParams {
     uint32_t* touch[4];
 };
 
+// The tree takes the N == 2 lookup (top grid + bricks, built at upload when the tree qualifies) and not
+// the literal descent: the launchers of vr_render.hip, vr_weights.hip and vr_query.hip pick their flavour by it.
+inline bool uses_lookup(const KParams& p) { return p.N == 2 && p.top_levels > 0; }
+
+// The grid of a persistent march kernel (render_kernel, weights_kernel; one wave per workgroup) over
+// total_blocks blocks of 64 rays: enough waves to fill the chip -- waves_per_cu of the flavour on each of
+// n_cus -- but no more than about one per 128 pixels (one per 64 rays that enter the volume), so that
+// small launches still rebalance through the ray queue.
+inline unsigned persistent_grid(int64_t total_blocks, int n_cus, int waves_per_cu) {
+    int64_t want = total_blocks / 2;
+    if (want < 256) want = 256;
+    if (want > total_blocks) want = total_blocks;
+    const int64_t cap = (int64_t)n_cus * waves_per_cu;
+    return (unsigned)(want < cap ? want : cap);
+}
+
 // ---------------------------------------------------------------------------
 // AOV launches (vr_render_aov): extra per-pixel float planes next to the colour.  The AOV kernel
 // flavours take KParams unchanged plus this second argument; the per-frame plane pointers sit in a

@@ -30,8 +30,8 @@ int ray_tail_words_of(const VrTreeOpaque* t) {
     return vr::ray_tail_words(t->desc.format, vr::basis_flavour(t->desc.format, t->desc.basis_dim));
 }
 
-size_t ray_buffer_bytes(uint32_t total_rays, int tail_words) {
-    return vr::ray_slots(total_rays) * (vr::kRayWords + (size_t)tail_words) * sizeof(uint32_t);
+size_t ray_buffer_bytes(uint32_t total_rays, int words_per_ray) {
+    return vr::ray_slots(total_rays) * (size_t)words_per_ray * sizeof(uint32_t);
 }
 
 // Replaces the ray buffer of a slot the caller owns (it holds the launch mutex, or has marked the
@@ -114,7 +114,27 @@ int launch_geometry(int width, int height, int tile_w, int tile_h, int rank, int
     return VR_OK;
 }
 
-namespace {  // the steps of vr_render_batch
+namespace {  // the steps of a launch: vr_render_batch, vr_render_aov, vr_accumulate_weights
+
+// The view checks: the launch has a focal length, and frame i the intrinsics of frame 0.
+int check_focal(const VrCamera& cam) {
+    if (!(cam.fx != 0.f) || !(cam.fy != 0.f)) return fail(VR_ERR_INVALID_ARGUMENT, "focal length must be non-zero");
+    return VR_OK;
+}
+int check_intrinsics(const VrCamera* cams, int i) {
+    if (cams[i].width != cams[0].width || cams[i].height != cams[0].height || cams[i].fx != cams[0].fx ||
+        cams[i].fy != cams[0].fy)
+        return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: intrinsics differ within the batch", i);
+    return VR_OK;
+}
+
+// the reference spins forever on step_size <= 0 (rt_core.cuh:108-175: t never advances past
+// a leaf face); the kernel's iteration cap would cut such rays short silently -- refuse.
+int check_step_size(const VrRenderOptions* opt) {
+    if (!(opt->step_size > 0.f))
+        return fail(VR_ERR_INVALID_ARGUMENT, "step_size must be positive (got %g)", (double)opt->step_size);
+    return VR_OK;
+}
 
 // One launch shares everything but the pose and the buffers: checks the batch against its first
 // frame and leaves in `k` what the checks compute -- the launch geometry, pitch, instrumented, any_accum.
@@ -138,18 +158,14 @@ int validate_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRend
     if (k.pitch < (int64_t)cam->width * 4 || k.pitch * cam->height >= (1ll << 32))
         return fail(VR_ERR_INVALID_ARGUMENT, "pitch %lld unusable for a %dx%d frame",
                     (long long)k.pitch, cam->width, cam->height);
-    if (!(cam->fx != 0.f) || !(cam->fy != 0.f))
-        return fail(VR_ERR_INVALID_ARGUMENT, "focal length must be non-zero");
+    if (int rc = check_focal(*cam)) return rc;
 
     bool instrumented = false, any_accum = false;
     for (int i = 0; i < n_frames; ++i) {
         const VrFrame& fi = frames[i];
-        const VrCamera& ci = cams[i];
         if (!fi.rgba) return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: rgba is NULL", i);
         // one launch shares everything but the pose and the buffers
-        if (ci.width != cam->width || ci.height != cam->height || ci.fx != cam->fx ||
-            ci.fy != cam->fy)
-            return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: intrinsics differ within the batch", i);
+        if (int rc = check_intrinsics(cams, i)) return rc;
         if (fi.pitch != f->pitch || fi.offscreen != f->offscreen || fi.layout != f->layout ||
             fi.tile_w != f->tile_w || fi.tile_h != f->tile_h || fi.rank != f->rank ||
             fi.world != f->world || fi.fp_mode != f->fp_mode)
@@ -158,20 +174,15 @@ int validate_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRend
         any_accum = any_accum || fi.accum != nullptr;
     }
 
-    // the reference spins forever on step_size <= 0 (rt_core.cuh:108-175: t never advances past
-    // a leaf face); the kernel's iteration cap would cut such rays short silently -- refuse.
-    if (!(opt->step_size > 0.f))
-        return fail(VR_ERR_INVALID_ARGUMENT, "step_size must be positive (got %g)",
-                    (double)opt->step_size);
+    if (int rc = check_step_size(opt)) return rc;
     k.n_frames = n_frames;
     k.instrumented = instrumented ? 1 : 0;
     k.any_accum = any_accum ? 1 : 0;
     return VR_OK;
 }
 
-// The part of KParams that comes from the caller: intrinsics, options, the launch-uniform half of
-// the view-direction rotation, and how the frames are written (`f` = the first frame).
-void fill_caller_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptions* opt, const VrFrame* f) {
+// What the march reads of the caller's arguments: the intrinsics and four options.
+void fill_march_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptions* opt) {
     k.width = cam->width;
     k.height = cam->height;
     k.fx = cam->fx;
@@ -179,8 +190,14 @@ void fill_caller_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptio
     k.step_size = opt->step_size;
     k.sigma_thresh = opt->sigma_thresh;
     k.stop_thresh = opt->stop_thresh;
-    k.background_brightness = opt->background_brightness;
     memcpy(k.bbox, opt->render_bbox, sizeof(k.bbox));
+}
+
+// The part of KParams that comes from the caller: intrinsics, options, the launch-uniform half of
+// the view-direction rotation, and how the frames are written (`f` = the first frame).
+void fill_caller_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptions* opt, const VrFrame* f) {
+    fill_march_params(k, cam, opt);
+    k.background_brightness = opt->background_brightness;
     k.basis_min = opt->basis_minmax[0];
     k.basis_max = opt->basis_minmax[1];
     k.render_depth = opt->render_depth != 0;
@@ -304,35 +321,36 @@ int validate_aov(int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
     return VR_OK;
 }
 
-// From its construction on kernels of a launch may be in the stream: whatever happens afterwards (a later
-// enqueue failing), the slot's event is recorded behind them and the slot is marked used, so
-// that the next user of the slot -- any stream -- waits for whatever did get enqueued.
-struct SlotSeal {
-    LaunchSlot& ls;
-    hipStream_t hs;
-    ~SlotSeal() {
-        if (hipEventRecord(ls.done.get(), hs) == hipSuccess) {
-            ls.used = true;
-            ls.last_stream = hs;
+// A launch's turn at its slot; begin() is the only way to take one.  Whoever used the slot last (any stream)
+// must have finished before its scratch is rewritten: begin() makes the stream wait for it (a failed wait
+// leaves the slot as it was).  From then on kernels of the launch may be in the stream: whatever happens
+// afterwards (a later enqueue failing), the slot's event is recorded behind them and the slot is marked used,
+// so that the next user of the slot -- any stream -- waits for whatever did get enqueued.
+class SlotTurn {
+    LaunchSlot* slot_ = nullptr;
+    hipStream_t stream_ = nullptr;
+public:
+    int begin(LaunchSlot& ls, hipStream_t hs) {
+        if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
+        slot_ = &ls;
+        stream_ = hs;
+        return VR_OK;
+    }
+    ~SlotTurn() {
+        if (!slot_) return;
+        if (hipEventRecord(slot_->done.get(), stream_) == hipSuccess) {
+            slot_->used = true;
+            slot_->last_stream = stream_;
         } else {
             (void)hipGetLastError();
         }
     }
 };
 
-// Puts the kernels of the launch into the stream, behind the slot's previous launch: the probe
-// pre-kernel, the frame table (for an AOV launch also the plane table), ray generation + render.
-// aovs = NULL: a colour launch, `a` is not read.
-int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, const Tuning& tn,
-                   const VrCamera* cams, const VrRenderOptions* opt, const VrFrame* frames, hipStream_t hs,
+// The frame table (poses, and the queue reset) -> device memory, kTableChunk poses per (tiny) kernel.
+// frames = NULL: poses alone (a leaf-weight launch); aovs: also the plane table of an AOV launch, through `a`.
+int enqueue_tables(const vr::KParams& k, const VrCamera* cams, hipStream_t hs, const VrFrame* frames = nullptr,
                    const VrAov* aovs = nullptr, const vr::AovParams& a = vr::AovParams{}) {
-    // whoever used this slot last (any stream) must have finished before its scratch is rewritten
-    if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
-    SlotSeal seal{ls, hs};
-    if (k.enable_probe)  // launch_renderer's pre-kernel, volrend.cu:202-209
-        HIP_TRY(vr::launch_probe(k, opt->probe, const_cast<float*>(k.probe_coeffs), hs));
-
-    // frame table -> device memory, kTableChunk poses per (tiny) kernel
     for (int first = 0; first < k.n_frames; first += vr::kTableChunk) {
         vr::FrameTable tbl;
         memset(&tbl, 0, sizeof(tbl));
@@ -340,6 +358,7 @@ int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, 
         tbl.n = k.n_frames - first < vr::kTableChunk ? k.n_frames - first : vr::kTableChunk;
         for (int i = 0; i < tbl.n; ++i) {
             memcpy(tbl.f[i].xf, cams[first + i].transform, sizeof(tbl.f[i].xf));
+            if (!frames) continue;
             tbl.f[i].rgba = static_cast<uint8_t*>(frames[first + i].rgba);
             tbl.f[i].accum = frames[first + i].accum;
             tbl.f[i].depth = frames[first + i].depth;
@@ -358,20 +377,21 @@ int enqueue_launch(const VrTreeOpaque* t, LaunchSlot& ls, const vr::KParams& k, 
             HIP_TRY(vr::launch_prepare_aov(a, at, hs));
         }
     }
-    // waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
-    // two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
-    // 4 waves find room there much earlier (vr_render.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
-    // two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
-    // 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
-    const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (k.n_frames <= 2 ? 4 : 16);
-    if (aovs)
-        HIP_TRY(vr::launch_render_aov(k, a, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
-    else
-        HIP_TRY(vr::launch_render(k, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
-    return VR_OK;  // (`seal` records the slot's event)
+    return VR_OK;
 }
 
-// vr_render_batch (aovs = NULL) and vr_render_aov: one launch, in steps.
+// waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
+// two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
+// 4 waves find room there much earlier (vr_render.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
+// two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
+// 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
+int raygen_waves(const Tuning& tn, int n_frames) {
+    return tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
+}
+
+// vr_render_batch (aovs = NULL) and vr_render_aov: one launch, in steps.  Into the stream go, behind the slot's
+// previous launch: the probe pre-kernel, the frame table (for an AOV launch also the plane table), ray
+// generation + render.
 int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
                   const VrFrame* frames, const VrAov* aovs, int depth_units, bool want_aov, void* stream) {
     vr::KParams k;
@@ -389,9 +409,19 @@ int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRende
     const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
     fill_tuning_params(k, t, tn);
     unsigned slot;
-    if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, k.ray_tail_words), slot)) return rc;
+    if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, vr::kRayWords + k.ray_tail_words), slot)) return rc;
     a.planes = t->slot_aovs.get<vr::AovDesc>() + (size_t)slot * vr::kMaxBatch;
-    return enqueue_launch(t, t->slots[slot], k, tn, cams, opt, frames, hs, want_aov ? aovs : nullptr, a);
+    SlotTurn turn;
+    if (int rc = turn.begin(t->slots[slot], hs)) return rc;
+    if (k.enable_probe)  // launch_renderer's pre-kernel, volrend.cu:202-209
+        HIP_TRY(vr::launch_probe(k, opt->probe, const_cast<float*>(k.probe_coeffs), hs));
+    if (int rc = enqueue_tables(k, cams, hs, frames, want_aov ? aovs : nullptr, a)) return rc;
+    const int gen_waves = raygen_waves(tn, n_frames);
+    if (want_aov)
+        HIP_TRY(vr::launch_render_aov(k, a, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
+    else
+        HIP_TRY(vr::launch_render(k, frames[0].fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, hs));
+    return VR_OK;  // (`turn` records the slot's event)
 }
 
 // ---- vr_accumulate_weights ----
@@ -405,18 +435,12 @@ int validate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRe
         return fail(VR_ERR_INVALID_ARGUMENT, "unknown fp_mode %d", fp_mode);
     if (n_frames < 0 || n_frames > VR_MAX_BATCH)
         return fail(VR_ERR_INVALID_ARGUMENT, "n_frames=%d outside [0,%d]", n_frames, VR_MAX_BATCH);
-    // (as vr_render_batch: the march would never advance past a leaf face)
-    if (!(opt->step_size > 0.f))
-        return fail(VR_ERR_INVALID_ARGUMENT, "step_size must be positive (got %g)", (double)opt->step_size);
+    if (int rc = check_step_size(opt)) return rc;
     if (n_frames == 0) return VR_OK;
-    const VrCamera* cam = &cams[0];
-    if (int rc = launch_geometry(cam->width, cam->height, 0, 0, 0, 1, n_frames, k)) return rc;
-    if (!(cam->fx != 0.f) || !(cam->fy != 0.f))
-        return fail(VR_ERR_INVALID_ARGUMENT, "focal length must be non-zero");
+    if (int rc = launch_geometry(cams[0].width, cams[0].height, 0, 0, 0, 1, n_frames, k)) return rc;
+    if (int rc = check_focal(cams[0])) return rc;
     for (int i = 1; i < n_frames; ++i)
-        if (cams[i].width != cam->width || cams[i].height != cam->height || cams[i].fx != cam->fx ||
-            cams[i].fy != cam->fy)
-            return fail(VR_ERR_INVALID_ARGUMENT, "frame %d: intrinsics differ within the batch", i);
+        if (int rc = check_intrinsics(cams, i)) return rc;
     k.n_frames = n_frames;
     return VR_OK;
 }
@@ -448,16 +472,8 @@ int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const Vr
     std::unique_lock<std::mutex> guard(t->launch_mutex);
     if (int rc = ensure_file_nodes(t)) return rc;
     if (n_frames == 0) return VR_OK;  // the warm-up call
-    // the caller's part: intrinsics and the four options the march reads; an offscreen frame without
-    // mesh depth, probe, depth mode or view-direction rotation
-    k.width = cams[0].width;
-    k.height = cams[0].height;
-    k.fx = cams[0].fx;
-    k.fy = cams[0].fy;
-    k.step_size = opt->step_size;
-    k.sigma_thresh = opt->sigma_thresh;
-    k.stop_thresh = opt->stop_thresh;
-    memcpy(k.bbox, opt->render_bbox, sizeof(k.bbox));
+    // the caller's part: an offscreen frame without mesh depth, probe, depth mode or view-direction rotation
+    fill_march_params(k, &cams[0], opt);
     k.offscreen = 1;
     k.layout = VR_LAYOUT_FRAME;
     k.pitch = (int64_t)k.width * 4;
@@ -465,26 +481,17 @@ int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const Vr
     const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
     fill_tuning_params(k, t, tn);
     unsigned slot;
-    const size_t need = vr::ray_slots(k.total_rays) * (size_t)vr::kWeightRayWords * sizeof(uint32_t);
-    if (int rc = acquire_slot(t, guard, hs, k, need, slot)) return rc;
-    LaunchSlot& ls = t->slots[slot];
-    if (ls.used) HIP_TRY(hipStreamWaitEvent(hs, ls.done.get(), 0));
-    SlotSeal seal{ls, hs};
-    for (int first = 0; first < n_frames; first += vr::kTableChunk) {  // the poses (and the queue reset)
-        vr::FrameTable tbl;
-        memset(&tbl, 0, sizeof(tbl));
-        tbl.first = first;
-        tbl.n = n_frames - first < vr::kTableChunk ? n_frames - first : vr::kTableChunk;
-        for (int i = 0; i < tbl.n; ++i) memcpy(tbl.f[i].xf, cams[first + i].transform, sizeof(tbl.f[i].xf));
-        HIP_TRY(vr::launch_prepare(k, tbl, hs));
-    }
+    if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, vr::kWeightRayWords), slot)) return rc;
+    SlotTurn turn;
+    if (int rc = turn.begin(t->slots[slot], hs)) return rc;
+    if (int rc = enqueue_tables(k, cams, hs)) return rc;
     vr::WeightParams w;
     w.max_weight = reinterpret_cast<uint32_t*>(out->max_weight);
     w.hits = out->hits;
     w.file_node = t->file_node_dev.get<int32_t>();
-    const int gen_waves = tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
-    HIP_TRY(vr::launch_weights(k, w, fp_mode, t->n_cus, tn.waves_per_cu, gen_waves, tn.weights_check != 0, hs));
-    return VR_OK;  // (`seal` records the slot's event)
+    HIP_TRY(vr::launch_weights(k, w, fp_mode, t->n_cus, tn.waves_per_cu, raygen_waves(tn, n_frames),
+                               tn.weights_check != 0, hs));
+    return VR_OK;  // (`turn` records the slot's event)
 }
 
 }  // namespace
@@ -517,7 +524,7 @@ int vr_reserve_tiles(vr_tree_t t, int width, int height, int n_frames, int tile_
     // exactly the ray count vr_render_batch computes, for rank 0 (which holds the most tiles)
     vr::KParams geo;
     if (int rc = launch_geometry(width, height, tile_w, tile_h, 0, world, n_frames, geo)) return rc;
-    const size_t need = ray_buffer_bytes(geo.total_rays, ray_tail_words_of(t));
+    const size_t need = ray_buffer_bytes(geo.total_rays, vr::kRayWords + ray_tail_words_of(t));
     DeviceGuard device_guard(t->device);
     std::lock_guard<std::mutex> guard(t->launch_mutex);
     for (int i = 0; i < n_slots; ++i) {

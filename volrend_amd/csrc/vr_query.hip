@@ -225,7 +225,7 @@ void enqueue_source(const KParams& p, const QueryArgs& q, unsigned blocks, hipSt
         }
         return;
     }
-    const bool n2 = p.N == 2 && p.top_levels > 0;  // built at upload when the tree qualifies
+    const bool n2 = uses_lookup(p);
     if (q.coeffs) {
         if (n2) enqueue<SRC, kLookupN2, true, kNoColour>(p, q, blocks, s);
         else enqueue<SRC, kLookupDescent, true, kNoColour>(p, q, blocks, s);

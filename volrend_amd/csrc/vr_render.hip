@@ -658,8 +658,6 @@ template <int FMA, bool FULL, int GW>
 __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
     constexpr bool AOV = VR_KERNEL_AOV;
     VR_KERNEL_AOV_LOCAL
-    __shared__ uint32_t wave_count[GW];
-    __shared__ uint32_t wave_base[GW];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const uint32_t id =
@@ -686,43 +684,9 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
             }
         }
     }
-    // Compaction: wave ballot + mbcnt prefix inside the wave, a scan over the workgroup's waves, and
-    // ONE atomic per workgroup on the count word of the queue that owns the workgroup's blocks (a
-    // single word only sustains ~90 returning atomics per microsecond chip-wide; workgroups never
-    // straddle a queue boundary: those lie at multiples of 16 blocks).
+    // compaction into the queue that owns the workgroup's blocks (vr_dev_rays.h)
     const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
-    const uint32_t nq = (uint32_t)p.n_queues;
-    uint32_t sh, n16;
-    queue_split(p, sh, n16);
-    const uint32_t g16 = (uint32_t)(((int64_t)blockIdx.x * GW) >> 4);  // this workgroup's group of 16 blocks
-    uint32_t qx = (uint32_t)(((uint64_t)g16 << sh) / n16);               // its queue: first guess, then exact
-    while (qx + 1u < nq && (queue_first_block(n16, qx + 1u, sh) >> 4) <= g16) ++qx;
-    while (qx > 0u && (queue_first_block(n16, qx, sh) >> 4) > g16) --qx;
-    uint32_t* const q_count = p.queue_head + qx * kQueueStride + kQueueCount;
-    const uint32_t q_base = queue_first_block(n16, qx, sh) << 6;
-    uint32_t my_base;
-    if constexpr (GW == 1) {
-        const uint32_t n = (uint32_t)__builtin_popcountll(m_valid);
-        uint32_t b = 0;
-        if (lane == 0 && n) b = atomicAdd(q_count, n);
-        my_base = q_base + (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
-    } else {
-        if (lane == 0) wave_count[wave] = (uint32_t)__builtin_popcountll(m_valid);
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t sum = 0;
-#pragma unroll
-            for (int w = 0; w < GW; ++w) {
-                wave_base[w] = sum;
-                sum += wave_count[w];
-            }
-            const uint32_t base = q_base + (sum ? atomicAdd(q_count, sum) : 0u);
-#pragma unroll
-            for (int w = 0; w < GW; ++w) wave_base[w] += base;
-        }
-        __syncthreads();
-        my_base = wave_base[wave];
-    }
+    const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
     if (!valid) return;
     const uint32_t slot = my_base + lane_rank(m_valid);
     uint32_t* rb = ray_slot(p.ray_buf_rw, kRayWords + p.ray_tail_words, slot);
@@ -871,17 +835,16 @@ bool needs_full(const KParams& p) {
     return p.format == VR_FORMAT_SG || p.format == VR_FORMAT_ASG || p.instrumented || p.render_depth;
 }
 
-// grid = the persistent waves: as many as the chip holds of this flavour (or the tuning
-// override), but no more than about one wave per 128 rays of a small launch
+// grid = the persistent waves (persistent_grid, vr_internal.h): as many as the chip holds of this flavour
+// (or the tuning override)
 template <int FMA, int MODE, bool AOV>
-hipError_t launch_basis(const KParams& p, const AovParams& a, int64_t want, int n_cus, int waves_override,
+hipError_t launch_basis(const KParams& p, const AovParams& a, int64_t total_blocks, int n_cus, int waves_override,
                         hipStream_t s) {
     const dim3 block(kWave);
 #define VR_LAUNCH(B)                                                                         \
     do {                                                                                     \
-        const int64_t cap_ = (int64_t)n_cus * (waves_override > 0 ? waves_override           \
-                                                                  : waves_per_cu<B, MODE, AOV>()); \
-        const dim3 grid((unsigned)(want < cap_ ? want : cap_));                              \
+        const dim3 grid(persistent_grid(total_blocks, n_cus,                                 \
+                                        waves_override > 0 ? waves_override : waves_per_cu<B, MODE, AOV>())); \
         constexpr bool kBlk = MODE == MODE_FAST;                                             \
         if constexpr (AOV) {                                                                 \
             if (kBlk && p.brick_blocked)                                                     \
@@ -906,12 +869,11 @@ hipError_t launch_basis(const KParams& p, const AovParams& a, int64_t want, int 
 }
 
 template <int FMA, bool AOV>
-hipError_t launch_fp(const KParams& p, const AovParams& a, int64_t want, int n_cus, int waves_override,
+hipError_t launch_fp(const KParams& p, const AovParams& a, int64_t total_blocks, int n_cus, int waves_override,
                      hipStream_t s) {
-    const bool n2 = (p.N == 2) && p.top_levels > 0;  // built at upload when the tree qualifies
-    if (!n2) return launch_basis<FMA, MODE_GENERIC, AOV>(p, a, want, n_cus, waves_override, s);
-    if (needs_full(p)) return launch_basis<FMA, MODE_FULL, AOV>(p, a, want, n_cus, waves_override, s);
-    return launch_basis<FMA, MODE_FAST, AOV>(p, a, want, n_cus, waves_override, s);
+    if (!uses_lookup(p)) return launch_basis<FMA, MODE_GENERIC, AOV>(p, a, total_blocks, n_cus, waves_override, s);
+    if (needs_full(p)) return launch_basis<FMA, MODE_FULL, AOV>(p, a, total_blocks, n_cus, waves_override, s);
+    return launch_basis<FMA, MODE_FAST, AOV>(p, a, total_blocks, n_cus, waves_override, s);
 }
 
 // Ray generation + the persistent march of one launch (the probe overlay is launch_render's own).
@@ -941,13 +903,9 @@ hipError_t launch_march(const KParams& p, const AovParams& a, int fp_mode, int n
 #undef VR_GEN_GW
 #undef VR_GEN
     }
-    // persistent march grid: enough waves to fill the chip, but no more than one per
-    // ~128 pixels so that small launches still rebalance through the ray queue
-    int64_t want = total_blocks / 2;  // about one wave per 64 rays that enter the volume
-    if (want < 256) want = 256;
-    if (want > total_blocks) want = total_blocks;
-    return fp_mode == VR_FP_FMA ? launch_fp<1, AOV>(p, a, want, n_cus, waves_override, stream)
-                                : launch_fp<0, AOV>(p, a, want, n_cus, waves_override, stream);
+    // the persistent march (its grid: persistent_grid, vr_internal.h)
+    return fp_mode == VR_FP_FMA ? launch_fp<1, AOV>(p, a, total_blocks, n_cus, waves_override, stream)
+                                : launch_fp<0, AOV>(p, a, total_blocks, n_cus, waves_override, stream);
 }
 
 }  // namespace

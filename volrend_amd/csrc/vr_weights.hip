@@ -32,14 +32,11 @@ typedef __attribute__((address_space(1))) const int32_t vr_gci32_t;
 // ---------------------------------------------------------------------------
 // weights_raygen_kernel: one lane per pixel of every frame.  setup_ray as raygen_kernel runs it (the frame
 // is offscreen: tmax comes from render_bbox alone); a ray that misses the box is dropped -- there is no
-// pixel to composite.  The others are compacted into their queue's region of the ray buffer exactly as
-// raygen_kernel compacts them (ballot + mbcnt in the wave, a scan over the workgroup's waves, one atomic
-// per workgroup on the queue's count word), as records of kWeightRayWords words.
+// pixel to composite.  The others are compacted into their queue's region of the ray buffer by the function
+// raygen_kernel compacts them with (reserve_ray_slots, vr_dev_rays.h), as records of kWeightRayWords words.
 // ---------------------------------------------------------------------------
 template <int FMA, int GW>
 __global__ __launch_bounds__(kWave* GW) void weights_raygen_kernel(const KParams p) {
-    __shared__ uint32_t wave_count[GW];
-    __shared__ uint32_t wave_base[GW];
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const uint32_t id = (uint32_t)(((int64_t)blockIdx.x * GW + wave) * kWave + lane);
@@ -55,31 +52,9 @@ __global__ __launch_bounds__(kWave* GW) void weights_raygen_kernel(const KParams
         }
     }
     const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
-    const uint32_t nq = (uint32_t)p.n_queues;
-    uint32_t sh, n16;
-    queue_split(p, sh, n16);
-    const uint32_t g16 = (uint32_t)(((int64_t)blockIdx.x * GW) >> 4);  // this workgroup's group of 16 blocks
-    uint32_t qx = (uint32_t)(((uint64_t)g16 << sh) / n16);               // its queue: first guess, then exact
-    while (qx + 1u < nq && (queue_first_block(n16, qx + 1u, sh) >> 4) <= g16) ++qx;
-    while (qx > 0u && (queue_first_block(n16, qx, sh) >> 4) > g16) --qx;
-    uint32_t* const q_count = p.queue_head + qx * kQueueStride + kQueueCount;
-    const uint32_t q_base = queue_first_block(n16, qx, sh) << 6;
-    if (lane == 0) wave_count[wave] = (uint32_t)__builtin_popcountll(m_valid);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t sum = 0;
-#pragma unroll
-        for (int w = 0; w < GW; ++w) {
-            wave_base[w] = sum;
-            sum += wave_count[w];
-        }
-        const uint32_t base = q_base + (sum ? atomicAdd(q_count, sum) : 0u);
-#pragma unroll
-        for (int w = 0; w < GW; ++w) wave_base[w] += base;
-    }
-    __syncthreads();
+    const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
     if (!valid) return;
-    const uint32_t slot = wave_base[wave] + lane_rank(m_valid);
+    const uint32_t slot = my_base + lane_rank(m_valid);
     uint32_t* rb = ray_slot(p.ray_buf_rw, kWeightRayWords, slot);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
@@ -283,14 +258,9 @@ hipError_t launch_fp(const KParams& p, const WeightParams& w, int n_cus, int wav
     else
         hipLaunchKernelGGL((weights_raygen_kernel<FMA, 4>), dim3((unsigned)((total_blocks + 3) / 4)),
                            dim3(kWave * 4), 0, s, p);
-    // the persistent grid, sized as render_kernel's: what the chip holds, at most one wave per ~128 pixels
-    int64_t want = total_blocks / 2;
-    if (want < 256) want = 256;
-    if (want > total_blocks) want = total_blocks;
-    const int64_t cap = (int64_t)n_cus * (waves_override > 0 ? waves_override : 4 * kWeightWaves);
-    const dim3 grid((unsigned)(want < cap ? want : cap));
+    const dim3 grid(persistent_grid(total_blocks, n_cus, waves_override > 0 ? waves_override : 4 * kWeightWaves));
     const bool hits = w.hits != nullptr;
-    const int query = !((p.N == 2) && p.top_levels > 0) ? kQueryGeneric : (p.brick_blocked ? kQueryN2Blocked : kQueryN2);
+    const int query = !uses_lookup(p) ? kQueryGeneric : (p.brick_blocked ? kQueryN2Blocked : kQueryN2);
 #define VR_WEIGHTS(Q)                                                              \
     do {                                                                           \
         if (hits) launch_march_check<FMA, Q, true>(p, w, check_first, grid, s);    \
