@@ -320,6 +320,43 @@ typedef struct VrLeafWeights {  /* device pointers; NULL = not wanted; at least 
 } VrLeafWeights;
 int vr_accumulate_weights(vr_tree_t tree, int n_frames, const VrCamera* cams,
                           const VrRenderOptions* opt, int fp_mode, const VrLeafWeights* out, void* stream);
+/* ---- Backward: gradients of a rendered batch with respect to the tree's values ---- */
+/* The step that follows pruning when a PlenOctree is optimised against its training images.
+ *   grad_accum  device, float32 [n_frames][height][width][4], tightly packed: dL / d out[0..3], out[] being
+ *               trace_ray's output (rt_core.cuh:66-196) for the pixel -- the four numbers VrFrame.accum
+ *               receives.  (The background composite is the caller's to differentiate.)
+ *   grad_data   device, float32 [capacity * N^3 * data_dim], indexed exactly as VrTreeDesc.data is (the file's
+ *               node numbering, record order [R.., G.., B.., sigma]).  The call ADDS into it; the caller
+ *               zeroes it once.  Elements that no hit sample of the call touches are not written at all.
+ * The frame is marched as vr_accumulate_weights marches it (offscreen, no mesh depth, tmax from render_bbox
+ * alone, FP model fp_mode).  The march geometry -- which samples exist, their leaves, delta_t, delta_scale,
+ * whether and where the ray stops -- has the colour kernels' bits and is a CONSTANT of the differentiation;
+ * only sigma and the record entries are variables.  Per ray, hit samples i = 1..K (sigma_i > sigma_thresh):
+ *   d_i = delta_t_i * delta_scale, a_i = exp(-d_i sigma_i), T_1 = 1, T_{i+1} = T_i a_i, w_i = T_i - T_{i+1}
+ *   c_{i,ch} = 1 / (1 + exp(-u)), u = sum_b B_b k_{i,ch,b} over the basis functions the renderer uses (all
+ *   of them for basis_dim 4 / 9 / 16 / 25, else b = 0 only); RGBA trees: c_{i,ch} = the record entry
+ *   s = 1 / (1 - T_{K+1}) when stop_thresh ended the ray at sample K, else 1
+ *   G_i = sum_ch g_ch c_{i,ch}, R_i = sum_{j>i} w_j G_j, C^ = sum_j w_j G_j, g = the pixel's grad_accum
+ *   SH coefficient (ch, b) of slot s_i += g_ch s w_i c_{i,ch} (1 - c_{i,ch}) B_b       (used b only)
+ *   RGBA entry ch of slot s_i          += g_ch s w_i
+ *   sigma of slot s_i                  += d_i (T_{i+1} G_i - R_i + g_3 T_{K+1})               (not stopped)
+ *                                      += d_i (s (T_{i+1} G_i - R_i) - s^2 T_{K+1} C^)        (stopped)
+ * summed over all rays of all frames, in binary32 (the running sum behind R_i in binary64) with float
+ * atomic adds: THE ORDER OF THE SUM IS NOT DEFINED, so two runs may differ in the last bits.  This is the
+ * library's one output that is not bit-reproducible; every other output stays bit-exact.
+ * A ray that meets non-finite records or gradients leaves unspecified values in the elements it touches;
+ * nothing faults, and elements no ray touches keep their bits.
+ * Contract: that of vr_accumulate_weights -- enqueue only, on a launch slot (vr_reserve of the same shape
+ * covers it), <= VR_MAX_BATCH frames of one size and one set of intrinsics, step_size <= 0 / NaN refused,
+ * the sample guard reports through vr_tree_status, n_frames == 0 uploads the file-order table and launches
+ * nothing; the tree is only read.
+ * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed or any device call: NULL tree / opt /
+ * grad_accum / grad_data / cams (when n_frames > 0), unknown fp_mode, n_frames outside 0..VR_MAX_BATCH,
+ * cameras that differ in size or intrinsics, a bad step_size.  VR_ERR_UNSUPPORTED: render_depth,
+ * enable_probe, non-zero rot_dirs (before the handle is followed); SG / ASG trees and a basis_minmax that
+ * leaves out a basis function of the tree (right after, before any device work). */
+int vr_render_backward(vr_tree_t tree, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                       int fp_mode, const float* grad_accum, float* grad_data, void* stream);
 /* Pre-allocates the ray buffers of two launch slots for batches of up to n_frames whole
  * width x height frames (128-228 bytes per ray): a render loop on one stream lives in one slot,
  * two alternating streams in two, so no later vr_render / vr_render_batch of that size (or

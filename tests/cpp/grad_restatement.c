@@ -1,0 +1,398 @@
+/*
+ * grad_restatement.c -- the yardstick of the vr_render_backward tests (TEST INFRASTRUCTURE).
+ *
+ * Two steps.
+ *   grad_trace_frame   marches every pixel of one offscreen frame with the oracle's own binary32 code
+ *                      (oracle/vr_oracle_core.inc, either FP model: ray generation, NDC warp, the ray/box test,
+ *                      the tree query, the step, the attenuation and the stop test of trace_ray,
+ *                      rt_core.cuh:66-196) and RECORDS what the differentiation treats as constants: per ray its
+ *                      pixel, its basis values, whether stop_thresh ended it, and per hit sample (sigma >
+ *                      sigma_thresh) the leaf slot in the file's numbering and delta = fl(delta_t * delta_scale).
+ *   grad_eval64 / grad_eval32   evaluate the formulas of include/volrend_hip.h (vr_render_backward) on such a
+ *                      record, with the VALUES (sigma and the record entries) taken from an array the caller
+ *                      hands in -- so a caller can perturb a value with every decision frozen.
+ *       grad_eval64    everything in binary64: out[4] per pixel, sum of the weights per pixel, the gradient
+ *                      per element of data (added into), and per element the magnitude M: the same sum with
+ *                      every factor and term replaced by its absolute value and every difference by a sum
+ *                      (w_i = T_i - T_{i+1} counts as T_i + T_{i+1}, 1 - c as 1 + c; s is a factor), and
+ *                      the underflow magnitude U: M with every transmittance factor (T_i, w_i, T_{K+1}) replaced
+ *                      by 1 -- binary32 carries a transmittance below 2^-126 with an ABSOLUTE error of up to
+ *                      that much (a light that decays to 1e-60 sticks at a subnormal), which no bound relative
+ *                      to M covers; 2^-126 U does.  U also carries eight smallest subnormals per contribution
+ *                      (SUBNORMAL_UNITS): a product that comes out below 2^-149 is zero in binary32.
+ *       grad_eval32    the same formulas in binary32, rays taken in a caller-given order and every
+ *                      contribution added into a binary32 array as it comes.
+ *
+ * Build: gcc -O2 -std=c11 -ffp-contract=off -mfma -fPIC -shared -I oracle (the oracle's flags).
+ */
+#define _GNU_SOURCE
+#include <math.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include "vr_oracle.h"
+#include "vr_detmath.h"
+
+#define VR_FMA 0
+#include "vr_oracle_core.inc"
+#undef VR_FMA
+#define VR_FMA 1
+#include "vr_oracle_core.inc"
+#undef VR_FMA
+
+/* A contribution is a chain of binary32 products; one whose result is subnormal carries an absolute error of half
+ * the smallest subnormal, 2^-150.  Per contribution U gets 2^-20: 2^-126 * 2^-20 = eight smallest subnormals. */
+#define SUBNORMAL_UNITS 0x1p-20
+
+static inline float madd_strict(float a, float b, float c) { return a * b + c; }
+static inline float madd_fma(float a, float b, float c) { return fmaf(a, b, c); }
+
+typedef struct {
+    int64_t slot;  /* node * N^3 + child slot, file numbering */
+    float delta;   /* fl(delta_t * delta_scale) */
+} GradHit;
+
+typedef struct {
+    int32_t pixel;    /* y * width + x */
+    int32_t stopped;  /* stop_thresh ended the ray at its last hit */
+    int64_t first, n; /* its hits: hits[first .. first + n) */
+    float basis[25];
+} GradRay;
+
+typedef struct {
+    GradRay* rays;
+    int64_t n_rays, cap_rays;
+    GradHit* hits;
+    int64_t n_hits, cap_hits;
+    int32_t width, height;
+    int32_t data_dim, basis_dim, n_basis; /* n_basis: basis functions the renderer uses; 0 = RGBA */
+} GradTrace;
+
+static int push_hit(GradTrace* tr, int64_t slot, float delta) {
+    if (tr->n_hits == tr->cap_hits) {
+        const int64_t cap = tr->cap_hits ? tr->cap_hits * 2 : 4096;
+        GradHit* h = (GradHit*)realloc(tr->hits, (size_t)cap * sizeof(GradHit));
+        if (!h) return 1;
+        tr->hits = h;
+        tr->cap_hits = cap;
+    }
+    tr->hits[tr->n_hits].slot = slot;
+    tr->hits[tr->n_hits].delta = delta;
+    tr->n_hits++;
+    return 0;
+}
+
+#define DEFINE_TRACE_PIXEL(M)                                                                         \
+    static int trace_pixel_##M(const OrTree* tree, const OrCamera* cam, const OrOptions* opt, int x,  \
+                               int y, GradTrace* tr, GradRay* ray) {                                  \
+        float light = 1.f, dir[3], cen[3];                                                            \
+        ray->pixel = y * cam->width + x;                                                              \
+        ray->stopped = 0;                                                                             \
+        ray->first = tr->n_hits;                                                                      \
+        ray->n = 0;                                                                                   \
+        for (int i = 0; i < 25; ++i) ray->basis[i] = 0.f;                                             \
+        if (!(tree->N > 0)) return 0;                                                                 \
+        screen2worlddir_##M(x, y, cam, dir, cen);                                                     \
+        const float vdir[3] = {dir[0], dir[1], dir[2]};                                               \
+        maybe_world2ndc_##M(tree, dir, cen);                                                          \
+        for (int i = 0; i < 3; ++i) cen[i] = madd_##M(tree->scale[i], cen[i], tree->offset[i]);       \
+        float tmax_bg = 1e9f;                                                                         \
+        dir[0] *= tree->scale[0];                                                                     \
+        dir[1] *= tree->scale[1];                                                                     \
+        dir[2] *= tree->scale[2];                                                                     \
+        const float delta_scale = 1.f / norm3_##M(dir);                                               \
+        dir[0] *= delta_scale;                                                                        \
+        dir[1] *= delta_scale;                                                                        \
+        dir[2] *= delta_scale;                                                                        \
+        tmax_bg /= delta_scale;                                                                       \
+        float tmin, tmax, invdir[3];                                                                  \
+        for (int i = 0; i < 3; ++i) invdir[i] = (float)(1.0 / ((double)dir[i] + 1e-9));               \
+        dda_world_##M(cen, invdir, &tmin, &tmax, opt->render_bbox);                                   \
+        tmax = vr_minf(tmax, tmax_bg);                                                                \
+        if (tmax < 0 || tmin > tmax) return 0;                                                        \
+        if (tr->n_basis > 0) precalc_basis_##M(tree, vdir, ray->basis);                               \
+        float t = tmin, cube_sz, pos[3];                                                              \
+        while (t < tmax) {                                                                            \
+            pos[0] = madd_##M(t, dir[0], cen[0]);                                                     \
+            pos[1] = madd_##M(t, dir[1], cen[1]);                                                     \
+            pos[2] = madd_##M(t, dir[2], cen[2]);                                                     \
+            int levels;                                                                               \
+            const int64_t leaf = query_##M(tree, pos, &cube_sz, &levels);                             \
+            const uint16_t* tree_val = tree->data + leaf * tree->data_dim;                            \
+            const float t_subcube = dda_unit_##M(pos, invdir) / cube_sz;                              \
+            const float delta_t = t_subcube + opt->step_size;                                         \
+            const float sigma = vr_half_bits_to_float(tree_val[tree->data_dim - 1]);                  \
+            if (sigma > opt->sigma_thresh) {                                                          \
+                const float att = vr_det_expf(-delta_t * delta_scale * sigma);                        \
+                if (push_hit(tr, leaf, delta_t * delta_scale)) return 1;                              \
+                ray->n++;                                                                             \
+                light *= att;                                                                         \
+                if (light < opt->stop_thresh) {                                                       \
+                    ray->stopped = 1;                                                                 \
+                    break;                                                                            \
+                }                                                                                     \
+            }                                                                                         \
+            t += delta_t;                                                                             \
+        }                                                                                             \
+        return 0;                                                                                     \
+    }
+
+DEFINE_TRACE_PIXEL(strict)
+DEFINE_TRACE_PIXEL(fma)
+
+void grad_trace_free(GradTrace* tr) {
+    if (!tr) return;
+    free(tr->rays);
+    free(tr->hits);
+    free(tr);
+}
+
+/* One frame, scanline order: ray r is pixel r. */
+GradTrace* grad_trace_frame(const OrTree* tree, const OrCamera* cam, const OrOptions* opt, int fp_mode) {
+    if (!tree || !cam || !opt) return NULL;
+    GradTrace* tr = (GradTrace*)calloc(1, sizeof(GradTrace));
+    if (!tr) return NULL;
+    tr->width = cam->width;
+    tr->height = cam->height;
+    tr->data_dim = tree->data_dim;
+    tr->basis_dim = tree->basis_dim;
+    if (tree->basis_dim < 0) tr->n_basis = 0;
+    else if (tree->basis_dim == 4 || tree->basis_dim == 9 || tree->basis_dim == 16 || tree->basis_dim == 25)
+        tr->n_basis = tree->basis_dim;
+    else tr->n_basis = 1;
+    tr->n_rays = tr->cap_rays = (int64_t)cam->width * cam->height;
+    tr->rays = (GradRay*)calloc((size_t)tr->n_rays, sizeof(GradRay));
+    if (!tr->rays) {
+        grad_trace_free(tr);
+        return NULL;
+    }
+    for (int y = 0; y < cam->height; ++y)
+        for (int x = 0; x < cam->width; ++x) {
+            GradRay* ray = tr->rays + ((int64_t)y * cam->width + x);
+            const int rc = fp_mode == OR_FP_FMA ? trace_pixel_fma(tree, cam, opt, x, y, tr, ray)
+                                                : trace_pixel_strict(tree, cam, opt, x, y, tr, ray);
+            if (rc) {
+                grad_trace_free(tr);
+                return NULL;
+            }
+        }
+    return tr;
+}
+
+/* Per pixel: hit samples, and whether the ray was stopped. */
+void grad_trace_rays(const GradTrace* tr, int64_t* n_hits, uint8_t* stopped) {
+    for (int64_t r = 0; r < tr->n_rays; ++r) {
+        n_hits[r] = tr->rays[r].n;
+        stopped[r] = (uint8_t)tr->rays[r].stopped;
+    }
+}
+
+/* The slots of ray r's hits, in march order (out: ray's n entries). */
+void grad_trace_slots(const GradTrace* tr, int64_t r, int64_t* out) {
+    const GradRay* ray = tr->rays + r;
+    for (int64_t i = 0; i < ray->n; ++i) out[i] = tr->hits[ray->first + i].slot;
+}
+
+/* Colour of one sample in binary64; dc = d colour / d (record entry of basis function b) without B_b. */
+static void colour64(const GradTrace* tr, const GradRay* ray, const double* v, double* c, double* dc) {
+    for (int ch = 0; ch < 3; ++ch) {
+        if (tr->n_basis == 0) {
+            c[ch] = v[ch];
+            dc[ch] = 1.0;
+        } else {
+            double u = 0.0;
+            for (int b = 0; b < tr->n_basis; ++b) u += (double)ray->basis[b] * v[ch * tr->basis_dim + b];
+            c[ch] = 1.0 / (1.0 + exp(-u));
+            dc[ch] = c[ch] * (1.0 - c[ch]);
+        }
+    }
+}
+
+/*
+ * data: [n_slots * data_dim] binary64 values (file order).  g: [height * width * 4] binary64.
+ * out: [height * width * 4] or NULL; wsum: [height * width] (sum of the w_i) or NULL;
+ * grad, mag, under: [n_slots * data_dim] ADDED INTO, or all NULL (forward only).
+ */
+int grad_eval64(const GradTrace* tr, const double* data, const double* g_all, double* out, double* wsum,
+                double* grad, double* mag, double* under) {
+    if (!tr || !data) return 1;
+    const int dd = tr->data_dim, nb = tr->n_basis, bd = tr->basis_dim;
+    double* suf = NULL;
+    int64_t suf_cap = 0;
+    for (int64_t r = 0; r < tr->n_rays; ++r) {
+        const GradRay* ray = tr->rays + r;
+        const GradHit* h = tr->hits + ray->first;
+        const int64_t K = ray->n;
+        /* forward: totals */
+        double T = 1.0, C[3] = {0, 0, 0}, Chat = 0.0, Chat_abs = 0.0, Gsum_abs = 0.0;
+        const double* g = g_all ? g_all + 4 * (int64_t)ray->pixel : NULL;
+        for (int64_t i = 0; i < K; ++i) {
+            const double* v = data + h[i].slot * dd;
+            const double a = exp(-(double)h[i].delta * v[dd - 1]);
+            const double w = T - T * a;
+            double c[3], dc[3];
+            colour64(tr, ray, v, c, dc);
+            for (int ch = 0; ch < 3; ++ch) C[ch] += w * c[ch];
+            if (g) {
+                Chat += w * (g[0] * c[0] + g[1] * c[1] + g[2] * c[2]);
+                Chat_abs += (T + T * a) * (fabs(g[0] * c[0]) + fabs(g[1] * c[1]) + fabs(g[2] * c[2]));
+                Gsum_abs += 2.0 * (fabs(g[0] * c[0]) + fabs(g[1] * c[1]) + fabs(g[2] * c[2]));
+            }
+            T *= a;
+        }
+        const double Tend = T;
+        const double s = ray->stopped ? 1.0 / (1.0 - Tend) : 1.0;
+        if (out) {
+            double* o = out + 4 * (int64_t)ray->pixel;
+            o[0] = s * C[0];
+            o[1] = s * C[1];
+            o[2] = s * C[2];
+            o[3] = ray->stopped ? 1.0 : (K > 0 ? 1.0 - Tend : 0.0);
+        }
+        if (wsum) wsum[ray->pixel] = 1.0 - Tend;
+        if (!grad || !mag || !under || !g) continue;
+        /* backward: R_i = what is still to come behind sample i, summed last sample first (three suffix sums per
+         * hit: of w G, of |w| |G| and of |G|) */
+        if (K > suf_cap) {
+            free(suf);
+            suf_cap = 2 * K;
+            suf = (double*)malloc((size_t)suf_cap * 3 * sizeof(double));
+            if (!suf) return 1;
+        }
+        T = 1.0;
+        for (int64_t i = 0; i < K; ++i) {
+            const double* v = data + h[i].slot * dd;
+            const double a = exp(-(double)h[i].delta * v[dd - 1]);
+            const double w = T - T * a;
+            double c[3], dc[3];
+            colour64(tr, ray, v, c, dc);
+            const double G_abs = fabs(g[0] * c[0]) + fabs(g[1] * c[1]) + fabs(g[2] * c[2]);
+            suf[3 * i + 0] = w * (g[0] * c[0] + g[1] * c[1] + g[2] * c[2]);
+            suf[3 * i + 1] = (T + T * a) * G_abs;
+            suf[3 * i + 2] = 2.0 * G_abs;
+            T *= a;
+        }
+        {
+            double acc[3] = {0, 0, 0};
+            for (int64_t i = K - 1; i >= 0; --i)
+                for (int q = 0; q < 3; ++q) {
+                    const double term = suf[3 * i + q];
+                    suf[3 * i + q] = acc[q];
+                    acc[q] += term;
+                }
+        }
+        T = 1.0;
+        for (int64_t i = 0; i < K; ++i) {
+            const int64_t base = h[i].slot * dd;
+            const double* v = data + base;
+            const double delta = (double)h[i].delta;
+            const double a = exp(-delta * v[dd - 1]);
+            const double w = T - T * a, Tn = T * a;
+            double c[3], dc[3];
+            colour64(tr, ray, v, c, dc);
+            const double G = g[0] * c[0] + g[1] * c[1] + g[2] * c[2];
+            const double G_abs = fabs(g[0] * c[0]) + fabs(g[1] * c[1]) + fabs(g[2] * c[2]);
+            const double R = suf[3 * i + 0], R_abs = suf[3 * i + 1], R_one = suf[3 * i + 2];
+            for (int ch = 0; ch < 3; ++ch) {
+                if (nb == 0) {
+                    grad[base + ch] += g[ch] * s * w;
+                    mag[base + ch] += fabs(g[ch] * s) * (T + Tn);
+                    under[base + ch] += 2.0 * fabs(g[ch] * s) + SUBNORMAL_UNITS;
+                } else {
+                    for (int b = 0; b < nb; ++b) {
+                        const double t = g[ch] * s * w * dc[ch] * (double)ray->basis[b];
+                        grad[base + ch * bd + b] += t;
+                        const double m1 = fabs(g[ch] * s * (double)ray->basis[b]) * c[ch] * (1.0 + c[ch]);
+                        mag[base + ch * bd + b] += m1 * (T + Tn);
+                        under[base + ch * bd + b] += 2.0 * m1 + SUBNORMAL_UNITS;
+                    }
+                }
+            }
+            if (!ray->stopped) {
+                grad[base + dd - 1] += delta * (Tn * G - R + g[3] * Tend);
+                mag[base + dd - 1] += fabs(delta) * (fabs(Tn) * G_abs + R_abs + fabs(g[3] * Tend));
+                under[base + dd - 1] += fabs(delta) * (G_abs + R_one + fabs(g[3])) + SUBNORMAL_UNITS;
+            } else {
+                grad[base + dd - 1] += delta * (s * (Tn * G - R) - s * s * Tend * Chat);
+                mag[base + dd - 1] += fabs(delta) * (fabs(s) * (fabs(Tn) * G_abs + R_abs) + s * s * fabs(Tend) * Chat_abs);
+                under[base + dd - 1] += fabs(delta) * (fabs(s) * (G_abs + R_one) + s * s * Gsum_abs) + SUBNORMAL_UNITS;
+            }
+            T = Tn;
+        }
+    }
+    free(suf);
+    return 0;
+}
+
+/*
+ * The same formulas in binary32 (the suffix sum R_i formed directly, last sample first), rays in the order
+ * order[0 .. n_order), every contribution added into the binary32 array grad as it comes.
+ * data: [n_slots * data_dim] binary32 values; g: [height * width * 4] binary32.
+ */
+int grad_eval32(const GradTrace* tr, const float* data, const float* g_all, const int64_t* order, int64_t n_order,
+                float* grad) {
+    if (!tr || !data || !g_all || !order || !grad) return 1;
+    const int dd = tr->data_dim, nb = tr->n_basis, bd = tr->basis_dim;
+    int64_t cap = 0;
+    float* buf = NULL; /* per hit: w, Tn, G, R, c(1-c) x 3 */
+    for (int64_t q = 0; q < n_order; ++q) {
+        const GradRay* ray = tr->rays + order[q];
+        const GradHit* h = tr->hits + ray->first;
+        const int64_t K = ray->n;
+        if (K == 0) continue;
+        if (K > cap) {
+            free(buf);
+            cap = K * 2;
+            buf = (float*)malloc((size_t)cap * 7 * sizeof(float));
+            if (!buf) return 1;
+        }
+        const float* g = g_all + 4 * (int64_t)ray->pixel;
+        float T = 1.f;
+        for (int64_t i = 0; i < K; ++i) {
+            const float* v = data + h[i].slot * dd;
+            const float a = expf(-h[i].delta * v[dd - 1]);
+            float* e = buf + 7 * i;
+            float c[3];
+            for (int ch = 0; ch < 3; ++ch) {
+                if (nb == 0) {
+                    c[ch] = v[ch];
+                    e[4 + ch] = 1.f;
+                } else {
+                    float u = 0.f;
+                    for (int b = 0; b < nb; ++b) u += ray->basis[b] * v[ch * bd + b];
+                    c[ch] = 1.f / (1.f + expf(-u));
+                    e[4 + ch] = c[ch] * (1.f - c[ch]);
+                }
+            }
+            e[0] = T * (1.f - a);
+            e[1] = T * a;
+            e[2] = g[0] * c[0] + g[1] * c[1] + g[2] * c[2];
+            T = e[1];
+        }
+        const float Tend = T;
+        float R = 0.f;
+        for (int64_t i = K - 1; i >= 0; --i) {
+            buf[7 * i + 3] = R;
+            R += buf[7 * i + 0] * buf[7 * i + 2];
+        }
+        const float Chat = R;
+        const float s = ray->stopped ? 1.f / (1.f - Tend) : 1.f;
+        for (int64_t i = 0; i < K; ++i) {
+            const int64_t base = h[i].slot * dd;
+            const float* e = buf + 7 * i;
+            for (int ch = 0; ch < 3; ++ch) {
+                if (nb == 0) {
+                    grad[base + ch] += g[ch] * s * e[0];
+                } else {
+                    const float f = g[ch] * s * e[0] * e[4 + ch];
+                    for (int b = 0; b < nb; ++b) grad[base + ch * bd + b] += f * ray->basis[b];
+                }
+            }
+            if (!ray->stopped) grad[base + dd - 1] += h[i].delta * (e[1] * e[2] - e[3] + g[3] * Tend);
+            else grad[base + dd - 1] += h[i].delta * (s * (e[1] * e[2] - e[3]) - s * s * Tend * Chat);
+        }
+    }
+    free(buf);
+    return 0;
+}

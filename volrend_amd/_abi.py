@@ -117,6 +117,8 @@ PROTOTYPES = {
                                 C.POINTER(VrFrame), C.POINTER(VrAov), C.c_int, C.c_void_p]),
     "vr_accumulate_weights": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
                                         C.c_int, C.POINTER(VrLeafWeights), C.c_void_p]),
+    "vr_render_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
+                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vr_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "vr_reserve_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int]),

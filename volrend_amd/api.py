@@ -479,6 +479,22 @@ class N3Tree:
         return accumulate_weights(self, cam, transforms, options, max_weight=max_weight, hits=hits, want=want,
                                   fp_mode=fp_mode, stream=stream)
 
+    # ---- gradients of a rendered batch (vr_render_backward) ----------------
+    def render_backward(self, cam: "Camera", transforms, options: "RenderOptions", grad_accum, *, grad_data=None,
+                        fp_mode: int = _abi.FP_STRICT, stream=None):
+        """The derivative of a rendered batch with respect to the tree's values -- vr_render_backward,
+        enqueued on ``stream``, one launch per 512 poses.
+
+        ``grad_accum``: float32 [len(transforms), height, width, 4], contiguous, on the tree's device:
+        dL/d of the four numbers ``accums`` of ``launch_renderer_batch`` receive per pixel.  Returns the
+        float32 tensor [capacity, N, N, N, data_dim], indexed like the file's ``data`` array, that the
+        contributions were ADDED into: ``grad_data`` when given (contiguous, float32), else one allocated
+        zeroed.  The sum uses float atomics: two runs may differ in the last bits.  The march is that of
+        ``accumulate_weights`` (offscreen, no mesh depth); render_depth, enable_probe, rot_dirs, a narrowed
+        basis_minmax and SG / ASG trees are refused."""
+        return render_backward(self, cam, transforms, options, grad_accum, grad_data=grad_data, fp_mode=fp_mode,
+                               stream=stream)
+
     def info(self) -> dict:
         i = _abi.VrTreeInfo()
         _abi.check(_abi.lib().vr_tree_info(self._handle, C.byref(i)))
@@ -748,6 +764,36 @@ def accumulate_weights(tree, cam: Camera, transforms, options: RenderOptions, *,
         _abi.check(L.vr_accumulate_weights(tree.handle, m, cams, C.byref(o), int(fp_mode), C.byref(out),
                                            _stream_ptr(stream)))
     return res
+
+
+def render_backward(tree, cam: Camera, transforms, options: RenderOptions, grad_accum, *, grad_data=None,
+                    fp_mode: int = _abi.FP_STRICT, stream=None):
+    """``N3Tree.render_backward`` (documented there)."""
+    n = len(transforms)
+    shape_g = (n, cam.height, cam.width, 4)
+    shape_d = (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim)
+    for name, buf, shape in (("grad_accum", grad_accum, shape_g), ("grad_data", grad_data, shape_d)):
+        if buf is None and name == "grad_data":
+            continue
+        if buf is None or not hasattr(buf, "is_contiguous"):
+            raise ValueError(f"{name} must be a torch tensor")
+        if tuple(buf.shape) != shape or not buf.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous tensor of shape {shape}, not {tuple(buf.shape)}")
+        if str(buf.dtype) != "torch.float32":
+            raise ValueError(f"{name} must be float32, not {buf.dtype}")
+    if grad_data is None:
+        import torch
+        grad_data = torch.zeros(shape_d, dtype=torch.float32, device=torch.device("cuda", tree.info()["device"]))
+    L, o = _abi.lib(), options.to_c()
+    frame_bytes = cam.height * cam.width * 16
+    for first in range(0, max(n, 1), _abi.MAX_BATCH):
+        m = min(_abi.MAX_BATCH, n - first)
+        cams = _cameras_c(cam, [transforms[first + i] for i in range(m)]) if m else None
+        # (no pose: an empty tensor has no address, and nothing is read -- any non-NULL pointer stands for it)
+        g_ptr = _ptr(grad_accum) + first * frame_bytes if m else (_ptr(grad_accum) or _ptr(grad_data))
+        _abi.check(L.vr_render_backward(tree.handle, m, cams, C.byref(o), int(fp_mode), g_ptr, _ptr(grad_data),
+                                        _stream_ptr(stream)))
+    return grad_data
 
 
 def set_tuning(**kw) -> None:

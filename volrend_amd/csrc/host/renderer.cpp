@@ -1,9 +1,11 @@
 // renderer.cpp -- volrend::launch_renderer[_aov] over vr_render / vr_render_batch / vr_render_aov, and
-// volrend::accumulate_weights over vr_accumulate_weights (the same poses, cameras and options).
+// volrend::accumulate_weights / render_backward over vr_accumulate_weights / vr_render_backward (the same
+// poses, cameras and options).
 #include <stdexcept>
 #include <string>
 
 #include "volrend/aov.hpp"
+#include "volrend/grad.hpp"
 #include "volrend/internal/check.hpp"
 #include "volrend/renderer_kernel.hpp"
 #include "volrend/weights.hpp"
@@ -116,6 +118,21 @@ void accumulate_weights(const N3Tree& tree, const Camera& cam, const std::vector
     const auto launch = [&](size_t, int n, const VrCamera* cams) {
         internal::vr_check(vr_accumulate_weights(tree.device, n, cams, &o, fp_mode, &out, stream),
                            "vr_accumulate_weights");
+    };
+    if (transforms.empty()) launch(0, 0, nullptr);  // (no pose at all: one call with n = 0, the warm-up)
+    else for_camera_chunks(cam, transforms, launch);
+}
+
+void render_backward(const N3Tree& tree, const Camera& cam, const std::vector<const float*>& transforms,
+                     const RenderOptions& options, const float* grad_accum, float* grad_data, void* stream,
+                     int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const size_t frame_floats = (size_t)cam.width * (size_t)cam.height * 4;
+    const auto launch = [&](size_t first, int n, const VrCamera* cams) {
+        internal::vr_check(vr_render_backward(tree.device, n, cams, &o, fp_mode,
+                                              grad_accum ? grad_accum + first * frame_floats : nullptr, grad_data,
+                                              stream),
+                           "vr_render_backward");
     };
     if (transforms.empty()) launch(0, 0, nullptr);  // (no pose at all: one call with n = 0, the warm-up)
     else for_camera_chunks(cam, transforms, launch);

@@ -1,5 +1,5 @@
 // vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp, vr_upload.cpp, vr_launch.cpp) and
-// the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_tree_kernels.hip).  Not part of the public ABI.
+// the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_grad.hip, vr_tree_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -192,7 +192,7 @@ struct KParams {
 // the literal descent: the launchers of vr_render.hip, vr_weights.hip and vr_query.hip pick their flavour by it.
 inline bool uses_lookup(const KParams& p) { return p.N == 2 && p.top_levels > 0; }
 
-// The grid of a persistent march kernel (render_kernel, weights_kernel; one wave per workgroup) over
+// The grid of a persistent march kernel (render_kernel, weights_kernel, grad_kernel; one wave per workgroup) over
 // total_blocks blocks of 64 rays: enough waves to fill the chip -- waves_per_cu of the flavour on each of
 // n_cus -- but no more than about one per 128 pixels (one per 64 rays that enter the volume), so that
 // small launches still rebalance through the ray queue.
@@ -241,6 +241,28 @@ struct WeightParams {
 // queue reset are launch_prepare's).  check_first: the max reads the word before it issues the atomic.
 hipError_t launch_weights(const KParams& p, const WeightParams& w, int fp_mode, int n_cus, int waves_override,
                           int gen_waves, bool check_first, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
+// Backward launches (vr_render_backward): the march of a leaf-weight launch that shades inline and scatters
+// float sums.  The kernels of vr_grad.hip take KParams unchanged plus this second argument.  Their ray
+// record is the weight record plus the view direction and the pixel's index into grad_accum: the length of
+// a colour ray's head, so a slot reserved for colour rays of the same shape holds them.
+// ---------------------------------------------------------------------------
+enum {
+    kGradRayVdir = kWeightRayWords,     // 3 words
+    kGradRayPixel = kGradRayVdir + 3,   // (frame * height + y) * width + x
+    kGradRayWords = kGradRayPixel + 1,
+};
+static_assert(kGradRayWords <= kRayWords, "a slot reserved for colour rays holds the backward rays of the same shape");
+struct GradParams {
+    const float* grad_accum;    // [n_frames][height][width][4]: dL / d out[0..3]
+    float* grad_data;           // [capacity * N3 * data_dim], file order; added into
+    const int32_t* file_node;   // device node -> the file's node (VrTreeOpaque.file_node)
+};
+
+// vr_grad.hip: ray generation + the persistent two-phase march of a backward launch
+hipError_t launch_grad(const KParams& p, const GradParams& g, int fp_mode, int n_cus, int waves_override,
+                       int gen_waves, hipStream_t stream);
 
 // vr_render.hip: the kernels of a launch
 hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream);

@@ -1,5 +1,5 @@
 // vr_launch.cpp -- launches (include/volrend_hip.h): vr_render_batch, vr_render_aov, vr_accumulate_weights,
-// vr_reserve*, vr_tree_status*,
+// vr_render_backward, vr_reserve*, vr_tree_status*,
 // the launch geometry and the launch-slot ring.  Built with -ffp-contract=off (the host-side
 // Rodrigues pre-computation below must round like the oracle).
 #include <hip/hip_runtime.h>
@@ -114,7 +114,7 @@ int launch_geometry(int width, int height, int tile_w, int tile_h, int rank, int
     return VR_OK;
 }
 
-namespace {  // the steps of a launch: vr_render_batch, vr_render_aov, vr_accumulate_weights
+namespace {  // the steps of a launch: vr_render_batch, vr_render_aov, vr_accumulate_weights, vr_render_backward
 
 // The view checks: the launch has a focal length, and frame i the intrinsics of frame 0.
 int check_focal(const VrCamera& cam) {
@@ -426,11 +426,10 @@ int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRende
 
 // ---- vr_accumulate_weights ----
 
-// Everything that can be refused without following the tree handle.  Leaves the launch geometry in `k`.
-int validate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
-                     const VrLeafWeights* out, vr::KParams& k) {
-    if (!t || !opt || !out || (n_frames > 0 && !cams)) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!out->max_weight && !out->hits) return fail(VR_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+// What a leaf-weight call and a backward call check of their views, without following the tree handle: FP
+// model, frame count (0 = the warm-up call), step, one size and one set of intrinsics.  Leaves the launch
+// geometry in `k`.
+int validate_march(int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode, vr::KParams& k) {
     if (fp_mode != VR_FP_STRICT && fp_mode != VR_FP_FMA)
         return fail(VR_ERR_INVALID_ARGUMENT, "unknown fp_mode %d", fp_mode);
     if (n_frames < 0 || n_frames > VR_MAX_BATCH)
@@ -443,6 +442,14 @@ int validate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRe
         if (int rc = check_intrinsics(cams, i)) return rc;
     k.n_frames = n_frames;
     return VR_OK;
+}
+
+// Everything that can be refused without following the tree handle.
+int validate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                     const VrLeafWeights* out, vr::KParams& k) {
+    if (!t || !opt || !out || (n_frames > 0 && !cams)) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (!out->max_weight && !out->hits) return fail(VR_ERR_INVALID_ARGUMENT, "both outputs are NULL");
+    return validate_march(n_frames, cams, opt, fp_mode, k);
 }
 
 // The device copy of the tree's device-node -> file-node table, made on the first call (under the launch
@@ -462,17 +469,17 @@ int ensure_file_nodes(VrTreeOpaque* t) {
     return VR_OK;
 }
 
-int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
-                       const VrLeafWeights* out, void* stream) {
-    vr::KParams k;
-    memset(&k, 0, sizeof(k));
-    if (int rc = validate_weights(t, n_frames, cams, opt, fp_mode, out, k)) return rc;
+// What a leaf-weight launch and a backward launch share once their arguments are checked: the file-order
+// table, an offscreen frame without mesh depth, probe, depth mode or view-direction rotation, a slot for rays
+// of `ray_words` words, the pose table, and then launch(k, tuning, stream).
+template <typename Launch>
+int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, vr::KParams& k,
+                 int ray_words, void* stream, Launch&& launch) {
     DeviceGuard device_guard(t->device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     std::unique_lock<std::mutex> guard(t->launch_mutex);
     if (int rc = ensure_file_nodes(t)) return rc;
     if (n_frames == 0) return VR_OK;  // the warm-up call
-    // the caller's part: an offscreen frame without mesh depth, probe, depth mode or view-direction rotation
     fill_march_params(k, &cams[0], opt);
     k.offscreen = 1;
     k.layout = VR_LAYOUT_FRAME;
@@ -481,22 +488,84 @@ int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const Vr
     const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
     fill_tuning_params(k, t, tn);
     unsigned slot;
-    if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, vr::kWeightRayWords), slot)) return rc;
+    if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, ray_words), slot)) return rc;
     SlotTurn turn;
     if (int rc = turn.begin(t->slots[slot], hs)) return rc;
     if (int rc = enqueue_tables(k, cams, hs)) return rc;
-    vr::WeightParams w;
-    w.max_weight = reinterpret_cast<uint32_t*>(out->max_weight);
-    w.hits = out->hits;
-    w.file_node = t->file_node_dev.get<int32_t>();
-    HIP_TRY(vr::launch_weights(k, w, fp_mode, t->n_cus, tn.waves_per_cu, raygen_waves(tn, n_frames),
-                               tn.weights_check != 0, hs));
+    HIP_TRY(launch(k, tn, hs));
     return VR_OK;  // (`turn` records the slot's event)
+}
+
+int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                       const VrLeafWeights* out, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = validate_weights(t, n_frames, cams, opt, fp_mode, out, k)) return rc;
+    return march_launch(t, n_frames, cams, opt, k, vr::kWeightRayWords, stream,
+                        [&](const vr::KParams& kp, const Tuning& tn, hipStream_t hs) {
+                            vr::WeightParams w;
+                            w.max_weight = reinterpret_cast<uint32_t*>(out->max_weight);
+                            w.hits = out->hits;
+                            w.file_node = t->file_node_dev.get<int32_t>();
+                            return vr::launch_weights(kp, w, fp_mode, t->n_cus, tn.waves_per_cu,
+                                                      raygen_waves(tn, n_frames), tn.weights_check != 0, hs);
+                        });
+}
+
+// ---- vr_render_backward ----
+
+// Everything that can be refused without following the tree handle.
+int validate_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                      const float* grad_accum, const float* grad_data, vr::KParams& k) {
+    if (!t || !opt || !grad_accum || !grad_data || (n_frames > 0 && !cams))
+        return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (int rc = validate_march(n_frames, cams, opt, fp_mode, k)) return rc;
+    if (opt->render_depth)
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward with render_depth: the depth visualisation has no derivative here");
+    if (opt->enable_probe)
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward with enable_probe: pixels under the probe disc are not traced");
+    if (!(opt->rot_dirs[0] == 0.f) || !(opt->rot_dirs[1] == 0.f) || !(opt->rot_dirs[2] == 0.f))
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward with rot_dirs: the view direction is not rotated");
+    return VR_OK;
+}
+
+// What needs the tree: the formats the backward kernels shade, and the whole basis.
+int check_backward_tree(const VrTreeOpaque* t, const VrRenderOptions* opt) {
+    const int format = t->desc.format, basis_dim = t->desc.basis_dim;
+    if (format == VR_FORMAT_SG || format == VR_FORMAT_ASG)
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward: SG / ASG trees are not supported");
+    if (vr::basis_flavour(format, basis_dim) != vr::BASIS_RGBA &&
+        (opt->basis_minmax[0] > 0 || opt->basis_minmax[1] < basis_dim - 1))
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward: basis_minmax [%d, %d] leaves out basis functions of the tree (%d)",
+                    opt->basis_minmax[0], opt->basis_minmax[1], basis_dim);
+    return VR_OK;
+}
+
+int render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                    const float* grad_accum, float* grad_data, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = validate_backward(t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, k)) return rc;
+    if (int rc = check_backward_tree(t, opt)) return rc;
+    return march_launch(t, n_frames, cams, opt, k, vr::kGradRayWords, stream,
+                        [&](const vr::KParams& kp, const Tuning& tn, hipStream_t hs) {
+                            vr::GradParams g;
+                            g.grad_accum = grad_accum;
+                            g.grad_data = grad_data;
+                            g.file_node = t->file_node_dev.get<int32_t>();
+                            return vr::launch_grad(kp, g, fp_mode, t->n_cus, tn.waves_per_cu,
+                                                   raygen_waves(tn, n_frames), hs);
+                        });
 }
 
 }  // namespace
 
 extern "C" {
+
+int vr_render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                       const float* grad_accum, float* grad_data, void* stream) {
+    return render_backward(t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, stream);
+}
 
 int vr_accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
                           int fp_mode, const VrLeafWeights* out, void* stream) {
