@@ -21,7 +21,7 @@ thread_local char g_err[512] = "";
 // One row per tuning knob (struct Tuning): its vr_set_tuning key, the environment variable the
 // process default is read from (once), how a value from either source is brought into range, and
 // whether the knob is fixed at upload (it shapes the lookup structure built then).
-enum KnobRange { kClamp, kClamp64, kFlag, kAutoFlag };  // [lo, hi]; then down to a multiple of 64;
+enum KnobRange { kClamp, kClamp64, kFlag, kAutoFlag };  // [lo, hi]; then down to a multiple of 64 (1..63: 64);
                                                         // 0 / 1; -1 (per tree) for v < 0, else 0 / 1
 struct Knob { const char *key, *env; int Tuning::*field; KnobRange range; int lo, hi; bool fixed_at_upload; };
 const Knob kKnobs[] = {
@@ -30,10 +30,10 @@ const Knob kKnobs[] = {
     {"drain_flush", "VR_DRAIN_FLUSH", &Tuning::drain_flush, kClamp, 0, 64, false},
     {"waves_per_cu", "VR_WAVES_PER_CU", &Tuning::waves_per_cu, kClamp, 0, 64, false},
     {"frame_group", "VR_FRAME_GROUP", &Tuning::frame_group, kClamp, 0, INT_MAX, false},
-    {"super_block", "VR_SUPER_BLOCK", &Tuning::super_block, kClamp, 1, 64, false},
+    {"super_block", "VR_SUPER_BLOCK", &Tuning::super_block, kClamp, 0, 64, false},
     {"records_nt", "VR_RECORDS_NT", &Tuning::records_nt, kAutoFlag, 0, 0, false},
     {"xcd_queues", "VR_XCD_QUEUES", &Tuning::xcd_queues, kFlag, 0, 0, false},
-    {"chunk_max", "VR_CHUNK_MAX", &Tuning::chunk_max, kClamp64, 64, INT_MAX, false},
+    {"chunk_max", "VR_CHUNK_MAX", &Tuning::chunk_max, kClamp64, 0, INT_MAX, false},
     {"raygen_waves", "VR_RAYGEN_WAVES", &Tuning::raygen_waves, kClamp, 0, INT_MAX, false},
     {"top_levels", "VR_TOP_LEVELS", &Tuning::top_levels, kClamp, INT_MIN, INT_MAX, true},
     {"brick_levels", "VR_BRICK_LEVELS", &Tuning::brick_levels, kClamp, INT_MIN, INT_MAX, true},
@@ -52,7 +52,7 @@ void set_knob(Tuning& tn, const Knob& k, int v) {
     const int clamped = v < k.lo ? k.lo : (v > k.hi ? k.hi : v);
     tn.*k.field = k.range == kFlag       ? v != 0
                   : k.range == kAutoFlag ? (v < 0 ? -1 : v != 0)
-                  : k.range == kClamp64  ? clamped & ~63
+                  : k.range == kClamp64  ? (clamped > 0 && clamped < 64 ? 64 : clamped & ~63)
                                          : clamped;
 }
 

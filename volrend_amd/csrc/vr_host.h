@@ -45,10 +45,12 @@ struct Tuning {
                            // measured 4..64, profiles/r05_experiments.jsonl: one frame per launch -13 %, two / four -5 %)
     int waves_per_cu = 0;   // 0: what the kernel flavour fits (vr_render.hip waves_per_cu<>)
     int frame_group = 0;   // poses per ray-order group (0 = all poses of the launch, 1 = frame-major)
-    int super_block = 1;   // 8x8 blocks per super-block edge in the ray order
+    int super_block = 0;   // 8x8 blocks per super-block edge in the ray order (1 = row-major); 0 = auto: by the kind and
+                           // size of the launch (auto_super_block, vr_launch.cpp)
     int records_nt = -1;   // record stream non-temporal: -1 = by lookup-structure size, 0 / 1 = forced
     int xcd_queues = 1;
-    int chunk_max = 4096;
+    int chunk_max = 0;     // cap of the guided chunk a wave takes from its queue at once (multiple of 64); 0 = auto:
+                           // by the kind of launch (auto_chunk_max, vr_launch.cpp)
     int raygen_waves = 0;  // waves per ray-generation workgroup: 16 / 4 / 1; 0 = by launch size (vr_render_batch)
     int top_levels = 0;    // lookup structure built at upload (vr_dev_layout.h); 0 = auto
     int brick_levels = 3;

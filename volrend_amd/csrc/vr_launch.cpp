@@ -219,9 +219,31 @@ void fill_caller_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptio
     k.layout = f->layout;
 }
 
+// The knobs that are "auto" (0) by default, resolved for one launch.  `colour`: a colour or AOV launch
+// (render_kernel / render_aov_kernel); the leaf-weight and backward launches keep the values they were
+// measured with (guided chunks of up to 4096 rays, row-major block order).
+//   * chunk_max: the cap of a wave's guided chunk (grab_chunk, vr_dev_rays.h).  256 for colour launches of
+//     any shape: four block-poses.  With 4096 one wave marched an 8x8 pixel block through all the poses of a
+//     64-frame launch, one after the other, and the lines it fetched for pose k were long evicted from its
+//     XCD's L2 at pose k + 1; with 256 the poses of a block go to 16 waves of the XCD at about the same time
+//     (fabric reads per C1 frame -7 %).  Below 256 the reads fall further (-24 % at 64) and the time RISES:
+//     a wave whose lanes hold unrelated blocks loses more in its own L1 than the L2 gains -- also with
+//     grabs that cost the wave no latency (EXPERIMENTS.md, round 7).  Small launches never reach the cap:
+//     the guided size of a one-frame launch is 64.
+//   * super_block: 4 (blocks visited in 4 x 4 super-blocks: consecutive chunks are screen neighbours in
+//     both directions) for launches of three frames and more, row-major for the small ones, which it
+//     costs 2 % (measured at one frame; four frames: no difference).
+constexpr int kColourChunkCap = 256, kGuidedChunkCap = 4096;
+int auto_chunk_max(const Tuning& tn, bool colour) {
+    return tn.chunk_max > 0 ? tn.chunk_max : colour ? kColourChunkCap : kGuidedChunkCap;
+}
+int auto_super_block(const Tuning& tn, bool colour, int n_frames) {
+    return tn.super_block > 0 ? tn.super_block : (colour && n_frames > 2) ? 4 : 1;
+}
+
 // The part of KParams that comes from the tree's knobs and from what its basis flavour makes a ray
 // carry.  Under the launch mutex, from the copy of the knobs the launch goes by.
-void fill_tuning_params(vr::KParams& k, const VrTreeOpaque* t, const Tuning& tn) {
+void fill_tuning_params(vr::KParams& k, const VrTreeOpaque* t, const Tuning& tn, bool colour) {
     // lookup structure (top + bricks) beyond 4x the aggregate L2 (8 x 4 MiB on MI355X): the record
     // stream would keep evicting it -- see the DMA loads in vr_render.hip
     k.records_nt = tn.records_nt >= 0 ? tn.records_nt
@@ -231,9 +253,9 @@ void fill_tuning_params(vr::KParams& k, const VrTreeOpaque* t, const Tuning& tn)
     k.drain_flush = tn.drain_flush;
     k.max_iter = tn.max_iter;
     k.frame_group = tn.frame_group < 1 || tn.frame_group > k.n_frames ? k.n_frames : tn.frame_group;
-    k.super_block = tn.super_block;
+    k.super_block = auto_super_block(tn, colour, k.n_frames);
     k.n_queues = tn.xcd_queues ? vr::kMaxQueues : 1;
-    k.chunk_max = tn.chunk_max;
+    k.chunk_max = auto_chunk_max(tn, colour);
     const int flavour = vr::basis_flavour(t->desc.format, t->desc.basis_dim);
     k.basis_words = vr::basis_words(flavour);
     k.ray_tail_words = vr::ray_tail_words(t->desc.format, flavour);
@@ -407,7 +429,7 @@ int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRende
     std::unique_lock<std::mutex> guard(t->launch_mutex);
     fill_tree_params(k, t);  // (under the mutex: vr_touch_enable / vr_touch_count (re)allocate the bitmaps)
     const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
-    fill_tuning_params(k, t, tn);
+    fill_tuning_params(k, t, tn, true);
     unsigned slot;
     if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, vr::kRayWords + k.ray_tail_words), slot)) return rc;
     a.planes = t->slot_aovs.get<vr::AovDesc>() + (size_t)slot * vr::kMaxBatch;
@@ -486,7 +508,7 @@ int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRender
     k.pitch = (int64_t)k.width * 4;
     fill_tree_params(k, t);
     const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
-    fill_tuning_params(k, t, tn);
+    fill_tuning_params(k, t, tn, false);
     unsigned slot;
     if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, ray_words), slot)) return rc;
     SlotTurn turn;
