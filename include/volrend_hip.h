@@ -10,6 +10,8 @@
  *   vr_tree_upload / vr_tree_free   N3Tree::load_cuda / free_cuda      src/cuda/n3tree.cu:9-49
  *   vr_tree_upload_quantized,       the codebook decode loop of
  *   vr_decode_quantized             N3Tree::load_npz                   src/n3tree.cpp:279-340
+ *   vr_tree_update_data,            no counterpart: the reference's device tree is written once,
+ *   vr_tree_read_data               by load_cuda                       src/cuda/n3tree.cu:9-41
  *   VrTreeDesc                      internal::TreeSpec                 include/volrend/internal/data_spec.hpp:23-50
  *   VrCamera                        internal::CameraSpec + the 48-byte
  *                                   Camera::_update upload             data_spec.hpp:11-22, src/camera.cpp:67-75
@@ -235,6 +237,39 @@ int vr_decode_quantized(const VrTreeDesc* desc, const VrQuantDesc* quant, uint16
 int vr_tree_clone(vr_tree_t src, int device, vr_tree_t* out);
 int vr_tree_free(vr_tree_t tree);
 int vr_tree_info(vr_tree_t tree, VrTreeInfo* info);
+/* ---- The values of an uploaded tree, in place ---- */
+/* The step that follows vr_render_backward in an optimiser loop, and its inverse.  The topology of the tree
+ * does not change, so neither call repeats any host work of an upload: each is a streaming pass on the device.
+ *   data_dev  device memory on the tree's device, capacity * N^3 * data_dim elements of `dtype`, indexed exactly
+ *             as VrTreeDesc.data and grad_data are: the file's node numbering, record [R.., G.., B.., sigma].
+ *   dtype     VR_DATA_F16: IEEE binary16 bits, as the file holds them.
+ *             VR_DATA_F32: binary32.  The update rounds to binary16 to nearest even (as numpy.astype(float16):
+ *             subnormal halves are produced, overflow goes to +-inf, the sign of zero is kept, a NaN becomes a
+ *             NaN with an unspecified payload); the read-back is the exact widening.
+ * vr_tree_update_data: once the call has passed on `stream`, every device array of the tree holds, bit for bit,
+ * what vr_tree_upload of the same child array with this data array would have built -- the coefficient records
+ * (padding zero; those of internal slots are stored, as upload stores them), the sigma of the leaf words and of
+ * the leaf entries of the top grid and the bricks.  So every output of the library (colour, accum, AOV planes,
+ * queries, probe, leaf weights, backward) is that of the fresh upload: in both query modes, both brick orders,
+ * every format, for trees uploaded from a quantised file and for clones.  The leaf bit of a node word decides
+ * what a slot is, as it did at upload: the sigma of an internal slot in data_dev is ignored.  `extra` (SG / ASG
+ * lobes) is not part of `data` and is not touched.
+ * vr_tree_read_data: writes the tree's current values to data_dev -- the bits of what was uploaded or last
+ * written, with the sigma of internal slots as +0.  update(read(tree)) changes nothing.
+ * Contract: both calls only enqueue on `stream`, run on the tree's device whatever the calling thread's current
+ * device is, and take no launch slot.  The first of them on a tree puts two tables on the device under the
+ * tree's mutex -- the 4-bytes-per-node file-order table of vr_accumulate_weights (whose n_frames == 0 call is
+ * the warm-up here too) and 4 bytes per brick of the lookup structure -- the call's one host-blocking step; from
+ * then on they count in VrTreeInfo.device_bytes.  A tree that is never updated or read holds neither.
+ * vr_tree_update_data WRITES the tree and is ordered like any write to a buffer that kernels read: launches,
+ * queries and clones enqueued LATER ON THE SAME STREAM see the new values; work on other streams must be
+ * ordered by the caller with events, both ways: nothing on the device may read the tree (no launch, query,
+ * read-back or clone) while the update runs.  vr_tree_read_data only reads the tree and may run beside launches.
+ * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed or any device call: NULL tree, NULL data_dev,
+ * unknown dtype.  Nothing is VR_ERR_UNSUPPORTED. */
+enum { VR_DATA_F16 = 0, VR_DATA_F32 = 1 };
+int vr_tree_update_data(vr_tree_t tree, const void* data_dev, int dtype, void* stream);
+int vr_tree_read_data(vr_tree_t tree, void* data_dev, int dtype, void* stream);
 
 /* ---- render ----------------------------------------------------------- */
 void vr_default_options(VrRenderOptions* opt);

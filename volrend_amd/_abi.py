@@ -24,6 +24,7 @@ SPACE_WORLD, SPACE_TREE = 0, 1  # vr_query_points / vr_query_grid
 SPACES = {"world": SPACE_WORLD, "tree": SPACE_TREE}
 DEPTH_TREE, DEPTH_WORLD = 0, 1  # vr_render_aov depth_units
 DEPTH_UNITS = {"tree": DEPTH_TREE, "world": DEPTH_WORLD}
+DATA_F16, DATA_F32 = 0, 1  # vr_tree_update_data / vr_tree_read_data dtype
 MAX_BASIS = 25
 
 
@@ -105,6 +106,8 @@ PROTOTYPES = {
     "vr_tree_clone": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p)]),
     "vr_tree_free": (C.c_int, [C.c_void_p]),
     "vr_tree_info": (C.c_int, [C.c_void_p, C.POINTER(VrTreeInfo)]),
+    "vr_tree_update_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "vr_tree_read_data": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "vr_query_mode_for": (C.c_int, [C.c_int, C.c_int, C.c_int64]),
     "vr_default_options": (None, [C.POINTER(VrRenderOptions)]),
     "vr_default_frame": (None, [C.POINTER(VrFrame)]),

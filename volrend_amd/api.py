@@ -495,6 +495,31 @@ class N3Tree:
         return render_backward(self, cam, transforms, options, grad_accum, grad_data=grad_data, fp_mode=fp_mode,
                                stream=stream)
 
+    # ---- the values of the device copy, in place (vr_tree_update_data / vr_tree_read_data) ----
+    def update_data(self, data, stream=None) -> None:
+        """Overwrites the values of the DEVICE copy with ``data`` -- vr_tree_update_data, enqueued on ``stream``:
+        the step after ``render_backward`` once the optimiser has moved its master parameters.
+
+        ``data``: a torch CUDA tensor (or any object with ``__cuda_array_interface__``) of dtype float16 or
+        float32 with capacity * N^3 * data_dim elements, contiguous, on the tree's device, indexed like the
+        file's ``data`` array ([capacity, N, N, N, data_dim], record [R.., G.., B.., sigma]).  float32 is rounded
+        to float16 to nearest even, as ``numpy.astype(float16)`` rounds.  Afterwards the device copy is bit for
+        bit what a fresh upload of this array would be; the sigma of internal slots is ignored.
+
+        The update WRITES the tree: launches and queries enqueued later on the same stream see the new values,
+        work on other streams has to be ordered with events, and nothing may read the tree while it runs.  The
+        host arrays of this object are NOT touched: ``data_`` goes stale, and ``load_device()`` from it would
+        undo the update (``read_data`` returns what the device holds)."""
+        update_data(self, data, stream=stream)
+
+    def read_data(self, dtype=None, out=None, stream=None):
+        """The current values of the DEVICE copy in file order -- vr_tree_read_data, enqueued on ``stream``: a
+        torch tensor [capacity, N, N, N, data_dim] of ``dtype`` (torch.float16, the default, or torch.float32:
+        the exact widening) on the tree's device; ``out`` when given (contiguous, that many elements; its dtype
+        decides).  The bits are those uploaded or last written, the sigma of internal slots +0.  Works where
+        the host arrays are gone (``clear_cpu_memory``, a quantised upload, a clone)."""
+        return read_data(self, dtype=dtype, out=out, stream=stream)
+
     def info(self) -> dict:
         i = _abi.VrTreeInfo()
         _abi.check(_abi.lib().vr_tree_info(self._handle, C.byref(i)))
@@ -794,6 +819,67 @@ def render_backward(tree, cam: Camera, transforms, options: RenderOptions, grad_
         _abi.check(L.vr_render_backward(tree.handle, m, cams, C.byref(o), int(fp_mode), g_ptr, _ptr(grad_data),
                                         _stream_ptr(stream)))
     return grad_data
+
+
+_DATA_DTYPES = {"float16": _abi.DATA_F16, "float32": _abi.DATA_F32}
+
+
+def _data_dtype(dtype) -> int:
+    """torch.float16 / torch.float32 (or their names, or a __cuda_array_interface__ typestr) -> VR_DATA_*."""
+    name = {"<f2": "float16", "<f4": "float32"}.get(dtype) if isinstance(dtype, str) and dtype.startswith("<") \
+        else str(dtype).replace("torch.", "")
+    if name not in _DATA_DTYPES:
+        raise ValueError(f"the tree's data must be float16 or float32, not {dtype}")
+    return _DATA_DTYPES[name]
+
+
+def _data_buffer(tree, x, what: str):
+    """Checks a buffer of the tree's values: dtype, element count, contiguity, device -> (pointer, VR_DATA_*).
+    Raises ValueError before any C call; a host tensor is refused before the tree is asked anything."""
+    n = tree.capacity * tree.N ** 3 * tree.data_dim
+    if hasattr(x, "is_contiguous") and hasattr(x, "data_ptr"):  # a torch tensor
+        code = _data_dtype(x.dtype)
+        if x.numel() != n:
+            raise ValueError(f"{what} must have capacity * N^3 * data_dim = {n} elements, not {x.numel()}")
+        if not x.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        if not x.is_cuda:
+            raise ValueError(f"{what} must be on the tree's device, not {x.device}")
+        dev = tree.info()["device"]
+        if x.device.index != dev:
+            raise ValueError(f"{what} must be on the tree's device cuda:{dev}, not {x.device}")
+        return int(x.data_ptr()), code
+    cai = getattr(x, "__cuda_array_interface__", None)
+    if cai is None:
+        raise ValueError(f"{what} must be a torch CUDA tensor or expose __cuda_array_interface__, got {type(x)}")
+    code = _data_dtype(cai["typestr"])
+    count = int(np.prod(cai["shape"], dtype=np.int64))
+    if count != n:
+        raise ValueError(f"{what} must have capacity * N^3 * data_dim = {n} elements, not {count}")
+    if cai.get("strides") is not None:
+        raise ValueError(f"{what} must be contiguous")
+    return int(cai["data"][0]), code
+
+
+def update_data(tree, data, stream=None) -> None:
+    """``N3Tree.update_data`` (documented there)."""
+    ptr, code = _data_buffer(tree, data, "data")
+    _abi.check(_abi.lib().vr_tree_update_data(tree.handle, ptr, code, _stream_ptr(stream)))
+
+
+def read_data(tree, dtype=None, out=None, stream=None):
+    """``N3Tree.read_data`` (documented there)."""
+    if out is None:
+        code = _data_dtype("float16" if dtype is None else dtype)
+        import torch
+        out = torch.empty((tree.capacity, tree.N, tree.N, tree.N, tree.data_dim),
+                          dtype=torch.float32 if code == _abi.DATA_F32 else torch.float16,
+                          device=torch.device("cuda", tree.info()["device"]))
+    elif dtype is not None and _data_dtype(dtype) != _data_buffer(tree, out, "out")[1]:
+        raise ValueError(f"out is not of dtype {dtype}")
+    ptr, code = _data_buffer(tree, out, "out")
+    _abi.check(_abi.lib().vr_tree_read_data(tree.handle, ptr, code, _stream_ptr(stream)))
+    return out
 
 
 def set_tuning(**kw) -> None:

@@ -105,6 +105,8 @@ struct VrTreeOpaque : TreeShape {
     DeviceBuffer slot_aovs;      // kLaunchSlots x kMaxBatch vr::AovDesc: the plane pointers of an AOV launch
     std::vector<int32_t> file_node;  // device node -> the file's node: the inverse of the upload's renumbering (host)
     DeviceBuffer file_node_dev;  // its device copy, made by the first vr_accumulate_weights (then in device_bytes)
+    std::vector<int32_t> brick_root;  // n_bricks: the node of each brick, ascending (host; empty without bricks)
+    DeviceBuffer brick_root_dev;  // its device copy, made by the first vr_tree_update_data / vr_tree_read_data (then in device_bytes)
     LaunchSlot slots[kLaunchSlots];
     unsigned launch_seq = 0;
     std::mutex launch_mutex;  // slot bookkeeping + enqueue order of one launch; guards `tn`

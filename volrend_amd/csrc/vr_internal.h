@@ -1,5 +1,5 @@
 // vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp, vr_upload.cpp, vr_launch.cpp) and
-// the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_grad.hip, vr_tree_kernels.hip).  Not part of the public ABI.
+// the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_grad.hip, vr_update.hip, vr_tree_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -263,6 +263,26 @@ struct GradParams {
 // vr_grad.hip: ray generation + the persistent two-phase march of a backward launch
 hipError_t launch_grad(const KParams& p, const GradParams& g, int fp_mode, int n_cus, int waves_override,
                        int gen_waves, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
+// Value passes (vr_tree_update_data / vr_tree_read_data, vr_update.hip): the tree's values between the file's
+// array and the device layout.  No launch slot, no KParams: the passes do not march.
+// ---------------------------------------------------------------------------
+struct UpdateArgs {
+    uint32_t* nodes;            // device layout (vr_dev_layout.h); the read-back only reads both
+    uint16_t* leaves;
+    const int32_t* file_node;   // device node -> the file's node (VrTreeOpaque.file_node)
+    void* data;                 // [capacity * N3 * data_dim], file order: read by the update, written by the read-back
+    int64_t capacity;
+    int32_t N3, data_dim;
+    int32_t stride_h;           // fp16 elements between padded records
+    int32_t f32;                // `data` is binary32 (VR_DATA_F32), else binary16
+};
+hipError_t launch_update_values(const UpdateArgs& a, int n_cus, hipStream_t stream);
+hipError_t launch_read_values(const UpdateArgs& a, int n_cus, hipStream_t stream);
+// the sigma fields of the leaf entries of top grid and bricks, from the node words (after an update)
+hipError_t launch_refresh_lookup(const uint32_t* nodes, const int32_t* brick_root, int n_bricks, uint2* top,
+                                 uint32_t* bricks, int top_levels, int brick_levels, hipStream_t stream);
 
 // vr_render.hip: the kernels of a launch
 hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream);

@@ -1,6 +1,6 @@
 // vr_launch.cpp -- launches (include/volrend_hip.h): vr_render_batch, vr_render_aov, vr_accumulate_weights,
-// vr_render_backward, vr_reserve*, vr_tree_status*,
-// the launch geometry and the launch-slot ring.  Built with -ffp-contract=off (the host-side
+// vr_render_backward, vr_reserve*, vr_tree_status*, the value passes vr_tree_update_data / vr_tree_read_data
+// (which share the file-order table of the march launches), the launch geometry and the launch-slot ring.  Built with -ffp-contract=off (the host-side
 // Rodrigues pre-computation below must round like the oracle).
 #include <hip/hip_runtime.h>
 
@@ -580,9 +580,68 @@ int render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRen
                         });
 }
 
+// ---- vr_tree_update_data / vr_tree_read_data ----
+
+// The device copy of the brick-root table (brick -> its node), which the refresh of the bricks reads: made
+// like the file-order table, on the first call, under the launch mutex.  Trees without bricks have none.
+int ensure_brick_roots(VrTreeOpaque* t) {
+    if (t->brick_root_dev || t->top_levels <= 0 || t->n_bricks <= 0) return VR_OK;
+    const size_t bytes = t->brick_root.size() * sizeof(int32_t);
+    if (bytes != (size_t)t->n_bricks * sizeof(int32_t)) return fail(VR_ERR_HIP, "the tree carries no brick-root table");
+    hipError_t e = t->brick_root_dev.alloc(bytes);
+    if (e == hipSuccess) e = hipMemcpy(t->brick_root_dev.get(), t->brick_root.data(), bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        (void)t->brick_root_dev.reset();
+        return fail(hip_code(e), "brick-root table of %zu bytes: %s", bytes, hipGetErrorString(e));
+    }
+    t->device_bytes += bytes;
+    return VR_OK;
+}
+
+// Both value passes: the refusals that need no tree, the two tables (the call's one host-blocking step), the
+// values pass and -- after an update of a tree with a lookup structure -- the refresh of its sigma fields
+// behind it on the same stream.  No launch slot: the passes hold no per-call scratch.
+int tree_data_pass(vr_tree_t t, void* data_dev, int dtype, void* stream, bool update) {
+    if (!t || !data_dev) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (dtype != VR_DATA_F16 && dtype != VR_DATA_F32) return fail(VR_ERR_INVALID_ARGUMENT, "unknown dtype %d", dtype);
+    DeviceGuard device_guard(t->device);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> guard(t->launch_mutex);  // (also orders an update among the launches of other host threads)
+    if (int rc = ensure_file_nodes(t)) return rc;
+    if (int rc = ensure_brick_roots(t)) return rc;
+    vr::UpdateArgs a;
+    a.nodes = t->arrays[kNodes].get<uint32_t>();
+    a.leaves = t->arrays[kLeaves].get<uint16_t>();
+    a.file_node = t->file_node_dev.get<int32_t>();
+    a.data = data_dev;
+    a.capacity = t->desc.capacity;
+    a.N3 = t->desc.N * t->desc.N * t->desc.N;
+    a.data_dim = t->desc.data_dim;
+    a.stride_h = t->leaf_stride_h;
+    a.f32 = dtype == VR_DATA_F32;
+    if (!update) {
+        HIP_TRY(vr::launch_read_values(a, t->n_cus, hs));
+        return VR_OK;
+    }
+    HIP_TRY(vr::launch_update_values(a, t->n_cus, hs));
+    if (t->top_levels > 0)
+        HIP_TRY(vr::launch_refresh_lookup(a.nodes, t->brick_root_dev.get<int32_t>(), t->n_bricks,
+                                          t->arrays[kTop].get<uint2>(), t->arrays[kBricks].get<uint32_t>(),
+                                          t->top_levels, t->brick_levels, hs));
+    return VR_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+int vr_tree_update_data(vr_tree_t t, const void* data_dev, int dtype, void* stream) {
+    return tree_data_pass(t, const_cast<void*>(data_dev), dtype, stream, true);
+}
+
+int vr_tree_read_data(vr_tree_t t, void* data_dev, int dtype, void* stream) {
+    return tree_data_pass(t, data_dev, dtype, stream, false);
+}
 
 int vr_render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
                        const float* grad_accum, float* grad_data, void* stream) {

@@ -267,6 +267,7 @@ hipError_t build_lookup(const LookupPlan& plan, const std::vector<int32_t>& bric
         t->brick_levels = n_bricks ? BL : 0;
         t->brick_blocked = blocked;
         t->n_bricks = n_bricks;
+        t->brick_root.assign(brick_roots.begin(), brick_roots.begin() + n_bricks);  // what vr_tree_update_data refreshes the bricks by
         t->device_bytes += top_sz + brick_sz;
     }
     return e;
@@ -416,7 +417,8 @@ int vr_tree_clone(vr_tree_t src, int device, vr_tree_t* out) {
     t->device = device;
     t->tn = src->tn;
     t->file_node = src->file_node;  // (its device copy is made on the clone's first vr_accumulate_weights)
-    t->device_bytes -= src->file_node_dev.bytes();
+    t->brick_root = src->brick_root;  // (likewise: on the clone's first vr_tree_update_data / vr_tree_read_data)
+    t->device_bytes -= src->file_node_dev.bytes() + src->brick_root_dev.bytes();
     // the re-laid-out arrays travel device to device (over xGMI between two GPUs of a node):
     // no second pass over PCIe, no second re-layout
     // direct peer access (xGMI / PCIe P2P) when the two devices have it: hipMemcpyPeer then moves
