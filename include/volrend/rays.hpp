@@ -1,0 +1,42 @@
+// volrend::render_rays / accumulate_weights_rays / render_backward_rays -- colour, leaf weights and gradients
+// along caller-supplied rays, over the HIP C ABI (vr_render_rays, vr_accumulate_weights_rays,
+// vr_render_backward_rays; include/volrend_hip.h has the semantics).  What an optimiser of a PlenOctree calls
+// per step with rays drawn from all its training images; the reference renderer has no counterpart.
+// Asynchronous like launch_renderer: each returns after enqueueing one launch on `stream` (a hipStream_t passed
+// as void*); each throws std::runtime_error ("vr_render_rays: ..." etc.) where the C call refuses its arguments.
+#pragma once
+#include <cstdint>
+
+#include "volrend/renderer_kernel.hpp"
+#include "volrend/weights.hpp"
+
+namespace volrend {
+
+// n rays: device, float32 [n][3] each, world space; a direction may have any finite non-zero length.  Ray i is
+// the ray of a pixel entered behind screen2worlddir's matrix product, marched as an offscreen frame without
+// mesh depth: a list built from a camera gives that frame's bits.  64 consecutive rays share a wave; the
+// library does not reorder them.
+struct Rays {
+    const float* origins = nullptr;
+    const float* dirs = nullptr;
+    int64_t n = 0;
+};
+
+//   rgba   device, [n] RGBA8: the composite over background_brightness;  accum  device, float32 [n][4]:
+//   trace_ray's output before the composite.  nullptr = not wanted, at least one.  render_depth and
+//   enable_probe are refused.
+void render_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, void* rgba, float* accum,
+                 void* stream, int fp_mode = VR_FP_STRICT);
+
+// accumulate_weights (weights.hpp) over the rays of a list; no ray: only the file-order table is uploaded.
+void accumulate_weights_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
+                             const LeafWeights& out, void* stream, int fp_mode = VR_FP_STRICT);
+
+// render_backward (grad.hpp) over the rays of a list: grad_accum is float32 [n][4], row i for ray i.
+void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
+                          const float* grad_accum, float* grad_data, void* stream, int fp_mode = VR_FP_STRICT);
+
+// Sizes n_slots launch slots so that no later ray call of <= n rays on them allocates (vr_reserve_rays).
+void reserve_rays(const N3Tree& tree, int64_t n, int n_slots = 2);
+
+}  // namespace volrend

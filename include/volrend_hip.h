@@ -392,6 +392,54 @@ int vr_accumulate_weights(vr_tree_t tree, int n_frames, const VrCamera* cams,
  * leaves out a basis function of the tree (right after, before any device work). */
 int vr_render_backward(vr_tree_t tree, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
                        int fp_mode, const float* grad_accum, float* grad_data, void* stream);
+/* ---- Ray lists: render, weigh and differentiate caller-supplied rays ---- */
+/* The three calls above take their rays from the pixels of VrCameras; an optimiser draws its rays at random
+ * from many images of different size and intrinsics.  These take n rays as two device arrays.  Ray i is THE RAY
+ * OF A PIXEL, ENTERED BEHIND screen2worlddir's MATRIX PRODUCT (volrend.cu:29-31):
+ *   dir = dirs[i], normalised as screen2worlddir normalises (in FP model fp_mode); cen = origins[i]
+ * and from there on exactly what a pixel's ray goes through, as an OFFSCREEN frame without mesh depth
+ * (t_max = 1e9): maybe_world2ndc, offset + scale * cen, the rot_dirs rotation of the view direction,
+ * _get_delta_scale, the ray/box test, trace_ray.  Consequences:
+ *   - a list built from a camera -- origin transform[9..11], direction the product of the 3x3 part of
+ *     transform with the pixel's (x, y, -1) as screen2worlddir forms it -- gives bit for bit what the frame
+ *     call gives for that pixel: RGBA8, accumulators, leaf weights;
+ *   - results do not depend on the order of the rays, on n, or on how a list is split into calls (the backward
+ *     sum is the exception, exactly as for frames);
+ *   - 64 consecutive rays share a wave.  The library does not reorder them: coherence is the caller's business;
+ *   - finite origins and finite non-zero directions are the contract; anything else is outside it, as a
+ *     non-finite pose is for frames.
+ * Each call keeps the contract of its frame sibling: enqueue only, on a launch slot, on the tree's device
+ * whatever the thread's current device is, step_size <= 0 / NaN refused, the sample guard reports through
+ * vr_tree_status, the tree is only read.  0 <= n < 2^30; n == 0 is VR_OK and launches nothing (for the weights
+ * and backward calls it still uploads the file-order table, as their n_frames == 0 does).
+ * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed or any device call: NULL tree / rays / origins /
+ * dirs / opt / out, every output NULL, unknown fp_mode, n outside the range, a bad step_size.
+ * Not offered for lists: a per-ray t_max / mesh depth, AOV planes, tile sharding, any reordering of the rays,
+ * gradients with respect to the rays. */
+typedef struct VrRays {       /* device, [n][3] float32 each, tightly packed, world space */
+    const float* origins;
+    const float* dirs;        /* any finite non-zero length */
+} VrRays;
+typedef struct VrRayOut {     /* device; NULL = not wanted, at least one non-NULL */
+    void*  rgba;              /* [n] RGBA8: the offscreen composite over background_brightness */
+    float* accum;             /* [n][4] float32: trace_ray's out[] before the composite (what VrFrame.accum receives) */
+} VrRayOut;
+/* Colour.  All of opt is honoured as an offscreen frame honours it (basis_minmax, rot_dirs, render_bbox, SG / ASG
+ * trees); VR_ERR_UNSUPPORTED: render_depth (not what a ray list is for) and enable_probe (the probe disc is a
+ * set of pixel positions).  A call without rgba uses 4 bytes per ray of its launch slot as scratch. */
+int vr_render_rays(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
+                   const VrRayOut* out, void* stream);
+/* vr_accumulate_weights over the rays of a list: its outputs, the file's node numbering, the accumulate-into
+ * rule and its refusals. */
+int vr_accumulate_weights_rays(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
+                               int fp_mode, const VrLeafWeights* out, void* stream);
+/* vr_render_backward over the rays of a list: grad_accum is [n][4], row i for ray i; grad_data, the formulas
+ * and the refusals (render_depth, enable_probe, rot_dirs, a narrowed basis_minmax, SG / ASG trees) are its. */
+int vr_render_backward_rays(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
+                            int fp_mode, const float* grad_accum, float* grad_data, void* stream);
+/* Sizes n_slots (1..8) launch slots so that no later ray call of <= n rays on them allocates or blocks (the
+ * colour record plus the scratch of a call without rgba: 80-232 bytes per ray).  Optional; synchronous. */
+int vr_reserve_rays(vr_tree_t tree, int64_t n, int n_slots);
 /* Pre-allocates the ray buffers of two launch slots for batches of up to n_frames whole
  * width x height frames (128-228 bytes per ray): a render loop on one stream lives in one slot,
  * two alternating streams in two, so no later vr_render / vr_render_batch of that size (or

@@ -79,6 +79,14 @@ class VrLeafWeights(C.Structure):
     _fields_ = [("max_weight", C.c_void_p), ("hits", C.c_void_p)]
 
 
+class VrRays(C.Structure):
+    _fields_ = [("origins", C.c_void_p), ("dirs", C.c_void_p)]
+
+
+class VrRayOut(C.Structure):
+    _fields_ = [("rgba", C.c_void_p), ("accum", C.c_void_p)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -122,6 +130,13 @@ PROTOTYPES = {
                                         C.c_int, C.POINTER(VrLeafWeights), C.c_void_p]),
     "vr_render_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vr_render_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
+                                 C.POINTER(VrRayOut), C.c_void_p]),
+    "vr_accumulate_weights_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),
+                                             C.c_int, C.POINTER(VrLeafWeights), C.c_void_p]),
+    "vr_render_backward_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),
+                                          C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vr_reserve_rays": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     "vr_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "vr_reserve_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_int]),

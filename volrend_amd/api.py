@@ -495,6 +495,42 @@ class N3Tree:
         return render_backward(self, cam, transforms, options, grad_accum, grad_data=grad_data, fp_mode=fp_mode,
                                stream=stream)
 
+    # ---- ray lists (vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays) ----
+    def reserve_rays(self, n: int, n_slots: int = 2) -> None:
+        """Sizes ``n_slots`` launch slots so that no later ray call of up to ``n`` rays on them allocates
+        (vr_reserve_rays)."""
+        _abi.check(_abi.lib().vr_reserve_rays(self.handle, int(n), int(n_slots)))
+
+    def render_rays(self, origins, dirs, options: "RenderOptions", *, want=("accum",), rgba=None, accum=None,
+                    fp_mode: int = _abi.FP_STRICT, stream=None, n=None) -> dict:
+        """Colour along caller-supplied rays -- vr_render_rays, one launch, enqueued on ``stream``.
+
+        ``origins`` / ``dirs``: float32 [n, 3], contiguous, on the tree's device, world space; a direction may have
+        any finite non-zero length (or raw device pointers with ``n``).  Ray i is the ray of a pixel entered
+        behind screen2worlddir's matrix product: the direction is normalised, then everything an offscreen frame
+        does follows, so a list built from a camera gives that frame's bits.  ``want``: "accum" (float32 [n, 4]:
+        trace_ray's output before the composite) and / or "rgba" (uint8 [n, 4]: composited over
+        background_brightness); a tensor passed as ``rgba`` / ``accum`` is wanted too and is written.  Returns a
+        dict of torch tensors.  64 consecutive rays share a wave; the library does not reorder them.
+        render_depth and enable_probe are refused."""
+        return render_rays(self, origins, dirs, options, want=want, rgba=rgba, accum=accum, fp_mode=fp_mode,
+                           stream=stream, n=n)
+
+    def accumulate_weights_rays(self, origins, dirs, options: "RenderOptions", *, max_weight=None, hits=None,
+                                want=("max_weight",), fp_mode: int = _abi.FP_STRICT, stream=None, n=None) -> dict:
+        """``accumulate_weights`` over the rays of a list (as ``render_rays`` takes them) --
+        vr_accumulate_weights_rays, one launch.  No rays: only the file-order table is put on the device."""
+        return accumulate_weights_rays(self, origins, dirs, options, max_weight=max_weight, hits=hits, want=want,
+                                       fp_mode=fp_mode, stream=stream, n=n)
+
+    def render_backward_rays(self, origins, dirs, options: "RenderOptions", grad_accum, *, grad_data=None,
+                             fp_mode: int = _abi.FP_STRICT, stream=None, n=None):
+        """``render_backward`` over the rays of a list (as ``render_rays`` takes them) -- vr_render_backward_rays,
+        one launch.  ``grad_accum``: float32 [n, 4], row i for ray i: dL/d of the four numbers ``render_rays``
+        returns as "accum".  Returns the float32 tensor [capacity, N, N, N, data_dim] added into."""
+        return render_backward_rays(self, origins, dirs, options, grad_accum, grad_data=grad_data, fp_mode=fp_mode,
+                                    stream=stream, n=n)
+
     # ---- the values of the device copy, in place (vr_tree_update_data / vr_tree_read_data) ----
     def update_data(self, data, stream=None) -> None:
         """Overwrites the values of the DEVICE copy with ``data`` -- vr_tree_update_data, enqueued on ``stream``:
@@ -818,6 +854,138 @@ def render_backward(tree, cam: Camera, transforms, options: RenderOptions, grad_
         g_ptr = _ptr(grad_accum) + first * frame_bytes if m else (_ptr(grad_accum) or _ptr(grad_data))
         _abi.check(L.vr_render_backward(tree.handle, m, cams, C.byref(o), int(fp_mode), g_ptr, _ptr(grad_data),
                                         _stream_ptr(stream)))
+    return grad_data
+
+
+def _ray_list(tree, origins, dirs, n=None):
+    """Checks a ray list -> (VrRays, n, a device for outputs or None).  Tensors: float32, [n, 3], contiguous, CUDA;
+    raw device pointers need ``n``.  Raises ValueError before any C call and before the tree is asked anything."""
+    rays = _abi.VrRays()
+    tensors = []
+    for name, x in (("origins", origins), ("dirs", dirs)):
+        if isinstance(x, int) and not isinstance(x, bool):
+            if n is None:
+                raise ValueError(f"{name} is a raw pointer: pass n")
+            setattr(rays, name, x)
+            continue
+        if not (hasattr(x, "is_contiguous") and hasattr(x, "data_ptr")):
+            raise ValueError(f"{name} must be a torch tensor or a raw device pointer, got {type(x)}")
+        if str(x.dtype) != "torch.float32":
+            raise ValueError(f"{name} must be float32, not {x.dtype}")
+        if x.dim() != 2 or x.shape[1] != 3 or (n is not None and x.shape[0] != n):
+            raise ValueError(f"{name} must have shape [{'n' if n is None else n}, 3], not {tuple(x.shape)}")
+        if not x.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        n = int(x.shape[0])
+        tensors.append((name, x))
+        setattr(rays, name, int(x.data_ptr()))
+    dev = None
+    for name, x in tensors:  # (a host tensor is refused before the tree is asked anything)
+        if not x.is_cuda:
+            raise ValueError(f"{name} must be on the tree's device, not {x.device}")
+    for name, x in tensors:
+        dev = tree.info()["device"] if dev is None else dev
+        if x.device.index != dev:
+            raise ValueError(f"{name} must be on the tree's device cuda:{dev}, not {x.device}")
+    if tensors:
+        dev = tensors[0][1].device
+    if n < 0:
+        raise ValueError("n is negative")
+    return rays, int(n), dev
+
+
+def _ray_buffer(buf, name: str, shape, dtype: str):
+    """An output or gradient of a ray call: a raw pointer, or a contiguous tensor of ``shape`` and ``dtype``."""
+    if isinstance(buf, int) and not isinstance(buf, bool):
+        return buf
+    if buf is None or not hasattr(buf, "is_contiguous"):
+        raise ValueError(f"{name} must be a torch tensor")
+    if tuple(buf.shape) != tuple(shape) or not buf.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous tensor of shape {tuple(shape)}, not {tuple(buf.shape)}")
+    if str(buf.dtype) != "torch." + dtype:
+        raise ValueError(f"{name} must be {dtype}, not {buf.dtype}")
+    return buf
+
+
+def _tree_device(tree, dev):
+    if dev is not None:
+        return dev
+    import torch
+    return torch.device("cuda", tree.info()["device"])
+
+
+def render_rays(tree, origins, dirs, options: RenderOptions, *, want=("accum",), rgba=None, accum=None,
+                fp_mode: int = _abi.FP_STRICT, stream=None, n=None) -> dict:
+    """``N3Tree.render_rays`` (documented there).  Outputs may also be raw device pointers, returned as passed."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in ("rgba", "accum") for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"want names 'rgba' and / or 'accum', each once: {want!r}")
+    rays, n, dev = _ray_list(tree, origins, dirs, n)
+    res = {}
+    outs = (("rgba", rgba, "uint8"), ("accum", accum, "float32"))
+    for name, buf, dt in outs:  # (what the caller passed is checked before anything is allocated)
+        if buf is not None:
+            res[name] = _ray_buffer(buf, name, (n, 4), dt)
+    for name, buf, dt in outs:
+        if buf is None and name in want:
+            import torch
+            res[name] = torch.empty((n, 4), dtype=getattr(torch, dt), device=_tree_device(tree, dev))
+    if not res:
+        raise ValueError("no output is wanted: name 'rgba' and / or 'accum'")
+    if n == 0:  # (empty tensors have no address to pass, and nothing would be launched)
+        return res
+    out = _abi.VrRayOut()
+    out.rgba, out.accum = _ptr(res.get("rgba")), _ptr(res.get("accum"))
+    o = options.to_c()
+    _abi.check(_abi.lib().vr_render_rays(tree.handle, n, C.byref(rays), C.byref(o), int(fp_mode), C.byref(out),
+                                         _stream_ptr(stream)))
+    return res
+
+
+def accumulate_weights_rays(tree, origins, dirs, options: RenderOptions, *, max_weight=None, hits=None,
+                            want=("max_weight",), fp_mode: int = _abi.FP_STRICT, stream=None, n=None) -> dict:
+    """``N3Tree.accumulate_weights_rays`` (documented there)."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if any(w not in ("max_weight", "hits") for w in want) or len(set(want)) != len(want):
+        raise ValueError(f"want names 'max_weight' and / or 'hits', each once: {want!r}")
+    rays, n, dev = _ray_list(tree, origins, dirs, n)
+    shape = (tree.capacity, tree.N, tree.N, tree.N)
+    res = {}
+    outs = (("max_weight", max_weight, "float32"), ("hits", hits, "int32"))
+    for name, buf, dt in outs:  # (what the caller passed is checked before anything is allocated)
+        if buf is not None:
+            res[name] = _ray_buffer(buf, name, shape, dt)
+    for name, buf, dt in outs:
+        if buf is None and name in want:
+            import torch
+            res[name] = torch.zeros(shape, dtype=getattr(torch, dt), device=_tree_device(tree, dev))
+    out = _abi.VrLeafWeights()
+    out.max_weight, out.hits = _ptr(res.get("max_weight")), _ptr(res.get("hits"))
+    if n == 0:  # (an empty tensor has no address, and nothing is read: any non-NULL pointer stands for it)
+        rays.origins = rays.dirs = out.max_weight or out.hits
+    o = options.to_c()
+    _abi.check(_abi.lib().vr_accumulate_weights_rays(tree.handle, n, C.byref(rays), C.byref(o), int(fp_mode),
+                                                     C.byref(out), _stream_ptr(stream)))
+    return res
+
+
+def render_backward_rays(tree, origins, dirs, options: RenderOptions, grad_accum, *, grad_data=None,
+                         fp_mode: int = _abi.FP_STRICT, stream=None, n=None):
+    """``N3Tree.render_backward_rays`` (documented there)."""
+    rays, n, dev = _ray_list(tree, origins, dirs, n)
+    grad_accum = _ray_buffer(grad_accum, "grad_accum", (n, 4), "float32")
+    shape_d = (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim)
+    if grad_data is None:
+        import torch
+        grad_data = torch.zeros(shape_d, dtype=torch.float32, device=_tree_device(tree, dev))
+    else:
+        grad_data = _ray_buffer(grad_data, "grad_data", shape_d, "float32")
+    g_ptr = _ptr(grad_accum)
+    if n == 0:  # (as accumulate_weights_rays)
+        rays.origins = rays.dirs = g_ptr = _ptr(grad_data)
+    o = options.to_c()
+    _abi.check(_abi.lib().vr_render_backward_rays(tree.handle, n, C.byref(rays), C.byref(o), int(fp_mode), g_ptr,
+                                                  _ptr(grad_data), _stream_ptr(stream)))
     return grad_data
 
 

@@ -7,6 +7,7 @@
 #include "volrend/aov.hpp"
 #include "volrend/grad.hpp"
 #include "volrend/internal/check.hpp"
+#include "volrend/rays.hpp"
 #include "volrend/renderer_kernel.hpp"
 #include "volrend/weights.hpp"
 
@@ -136,6 +137,34 @@ void render_backward(const N3Tree& tree, const Camera& cam, const std::vector<co
     };
     if (transforms.empty()) launch(0, 0, nullptr);  // (no pose at all: one call with n = 0, the warm-up)
     else for_camera_chunks(cam, transforms, launch);
+}
+
+void render_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, void* rgba, float* accum,
+                 void* stream, int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const VrRays r{rays.origins, rays.dirs};
+    const VrRayOut out{rgba, accum};
+    internal::vr_check(vr_render_rays(tree.device, rays.n, &r, &o, fp_mode, &out, stream), "vr_render_rays");
+}
+
+void accumulate_weights_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
+                             const LeafWeights& out, void* stream, int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const VrRays r{rays.origins, rays.dirs};
+    internal::vr_check(vr_accumulate_weights_rays(tree.device, rays.n, &r, &o, fp_mode, &out, stream),
+                       "vr_accumulate_weights_rays");
+}
+
+void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
+                          const float* grad_accum, float* grad_data, void* stream, int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const VrRays r{rays.origins, rays.dirs};
+    internal::vr_check(vr_render_backward_rays(tree.device, rays.n, &r, &o, fp_mode, grad_accum, grad_data, stream),
+                       "vr_render_backward_rays");
+}
+
+void reserve_rays(const N3Tree& tree, int64_t n, int n_slots) {
+    internal::vr_check(vr_reserve_rays(tree.device, n, n_slots), "vr_reserve_rays");
 }
 
 void launch_renderer_aov(const N3Tree& tree, const Camera& cam, const RenderOptions& options,

@@ -1,6 +1,7 @@
 // vr_dev_rays.h -- a ray from pixel to pixel: ray-id order, ray generation up to the ray/box test,
 // the compositing tail, the ray buffer raygen_kernel writes and render_kernel reads, and the ray
-// queues ray generation compacts its rays into and the persistent waves draw their chunks from.
+// queues ray generation compacts its rays into and the persistent waves draw their chunks from, and the front
+// of the ray-list launches (list_ray).
 // Device code only.
 #pragma once
 #include "vr_device_math.h"
@@ -114,32 +115,16 @@ __device__ __forceinline__ uint8_t* pixel_ptr(const KParams& p, const FrameDesc&
     return pixel_address(p, fd, r.k, r.lx, r.ly, r.x, r.y);
 }
 
-// Ray generation + trace_ray prologue up to the ray/box test
-// (volrend.cu:135-148, rt_core.cuh:74-92).  vdir = (rotated) view direction for the basis.
-template <int FMA>
-__device__ __forceinline__ void setup_ray(const KParams& p, const PixelRef& r, Ray& ray,
-                                          float* vdir) {
+// A ray from (cen, dir) on: world-space origin and NORMALISED world-space direction -- where screen2worlddir
+// (volrend.cu:22-32) leaves a pixel's ray -- through maybe_world2ndc, the world->tree transform, the
+// view-direction rotation, _get_delta_scale and the ray/box test (volrend.cu:34-71, rt_core.cuh:52-92).
+// The tail of setup_ray, and all of a caller-supplied ray (vr_render_rays: list_ray below).  vdir = the (rotated)
+// view direction for the basis; tmax_of() = the ray's far limit before the division by delta_scale (a
+// pixel's mesh depth; 1e9 without one), asked where the pixel's ray asks it.
+template <int FMA, typename TmaxOf>
+__device__ __forceinline__ void setup_ray_from(const KParams& p, float* cen, float* dir, Ray& ray, float* vdir,
+                                               TmaxOf&& tmax_of) {
     using P = Policy<FMA>;
-    const FrameDesc& fd = p.frames[r.frame];
-    ray.out[0] = ray.out[1] = ray.out[2] = ray.out[3] = 0.f;
-    ray.light = 1.f;
-    ray.alive = ray.entered = ray.stopped = false;
-    ray.t = 0.f;
-    if (p.N <= 0) return;  // enable_draw = tree.N > 0
-    float dir[3], cen[3];
-    // screen2worlddir, volrend.cu:22-32 (no +0.5 pixel centre offset)
-    float xyz[3];
-    xyz[0] = P::nmadd(0.5f, (float)p.width, (float)r.x) / p.fx;
-    xyz[1] = -(P::nmadd(0.5f, (float)p.height, (float)r.y)) / p.fy;
-    xyz[2] = -1.0f;
-    float xf[12];
-#pragma unroll
-    for (int i = 0; i < 12; ++i) xf[i] = fd.xf[i];
-    mv3<FMA>(xf, xyz, dir);
-    normalize3<FMA>(dir);
-    cen[0] = xf[9];
-    cen[1] = xf[10];
-    cen[2] = xf[11];
     vdir[0] = dir[0];
     vdir[1] = dir[1];
     vdir[2] = dir[2];
@@ -158,8 +143,7 @@ __device__ __forceinline__ void setup_ray(const KParams& p, const PixelRef& r, R
 #pragma unroll
     for (int i = 0; i < 3; ++i) cen[i] = P::madd(p.scale[i], cen[i], p.offset[i]);
 
-    float tmax_bg = 1e9f;
-    if (!p.offscreen && fd.depth) tmax_bg = fd.depth[(int64_t)r.y * p.width + r.x];
+    float tmax_bg = tmax_of();
 
     if (p.rot_enabled) {  // rodrigues, volrend.cu:57-71 (uniform part done on host)
         float cr[3];
@@ -211,6 +195,44 @@ __device__ __forceinline__ void setup_ray(const KParams& p, const PixelRef& r, R
     ray.entered = true;
     ray.t = tmin;
     ray.alive = tmin < tmax;
+}
+
+// What every ray starts from (the part of setup_ray in front of enable_draw).
+__device__ __forceinline__ void reset_ray(Ray& ray) {
+    ray.out[0] = ray.out[1] = ray.out[2] = ray.out[3] = 0.f;
+    ray.light = 1.f;
+    ray.alive = ray.entered = ray.stopped = false;
+    ray.t = 0.f;
+}
+
+// Ray generation + trace_ray prologue up to the ray/box test
+// (volrend.cu:135-148, rt_core.cuh:74-92).  vdir = (rotated) view direction for the basis.
+template <int FMA>
+__device__ __forceinline__ void setup_ray(const KParams& p, const PixelRef& r, Ray& ray,
+                                          float* vdir) {
+    using P = Policy<FMA>;
+    const FrameDesc& fd = p.frames[r.frame];
+    reset_ray(ray);
+    if (p.N <= 0) return;  // enable_draw = tree.N > 0
+    float dir[3], cen[3];
+    // screen2worlddir, volrend.cu:22-32 (no +0.5 pixel centre offset)
+    float xyz[3];
+    xyz[0] = P::nmadd(0.5f, (float)p.width, (float)r.x) / p.fx;
+    xyz[1] = -(P::nmadd(0.5f, (float)p.height, (float)r.y)) / p.fy;
+    xyz[2] = -1.0f;
+    float xf[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xf[i] = fd.xf[i];
+    mv3<FMA>(xf, xyz, dir);
+    normalize3<FMA>(dir);
+    cen[0] = xf[9];
+    cen[1] = xf[10];
+    cen[2] = xf[11];
+    setup_ray_from<FMA>(p, cen, dir, ray, vdir, [&]() -> float {
+        float tmax_bg = 1e9f;
+        if (!p.offscreen && fd.depth) tmax_bg = fd.depth[(int64_t)r.y * p.width + r.x];
+        return tmax_bg;
+    });
 }
 
 // End of trace_ray + the compositing tail of render_kernel (rt_core.cuh:176-194,
@@ -409,6 +431,63 @@ __device__ __forceinline__ uint32_t reserve_ray_slots(const KParams& p, unsigned
         __syncthreads();
         return wave_base[wave];
     }
+}
+
+// ---------------------------------------------------------------------------
+// Ray lists (vr_internal.h RayList): the front of the three *_raygen_rays_kernel.
+// ---------------------------------------------------------------------------
+// The 12 march words every record starts with.
+__device__ __forceinline__ void store_march_words(uint32_t* rb, const Ray& nr) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        ray_word(rb, kRayCen + i) = f2u(nr.cen[i]);
+        ray_word(rb, kRayDir + i) = f2u(nr.dir[i]);
+        ray_word(rb, kRayInvDir + i) = f2u(nr.invdir[i]);
+    }
+    ray_word(rb, kRayT) = f2u(nr.t);
+    ray_word(rb, kRayTmax) = f2u(nr.tmax);
+    ray_word(rb, kRayDeltaScale) = f2u(nr.delta_scale);
+}
+
+// Ray `id` = (workgroup, wave, lane) of a list, set up as the ray of a pixel is behind screen2worlddir's matrix
+// product: dir = normalize3<FMA>(dirs[id]), cen = origins[id], then setup_ray_from as an offscreen frame
+// without mesh depth.  Every lane of the workgroup calls (GW = waves per workgroup); returns whether the lane
+// holds a ray of the list (id < n) -- ray.alive then says whether it enters the volume.
+// A wave's 64 triples are 768 contiguous bytes of each array, 768-byte aligned: they are read as whole
+// lines -- lane l takes floats l, 64 + l, 128 + l -- and turned into triples through LDS (as query_kernel
+// turns its points; the stride-3 reads are free of bank conflicts).
+template <int FMA, int GW>
+__device__ __forceinline__ bool list_ray(const KParams& p, const RayList& rl, int lane, int wave, uint32_t& id,
+                                         Ray& ray, float* vdir) {
+    typedef __attribute__((address_space(1))) const float vr_gcfloat_t;
+    __shared__ float tr[GW][2][3 * kWave];
+    const int64_t first = ((int64_t)blockIdx.x * GW + wave) * kWave;  // the wave's first ray
+    const int64_t left = rl.n - first;
+    const int count = left <= 0 ? 0 : (left < kWave ? (int)left : kWave);
+    vr_gcfloat_t* const so = (vr_gcfloat_t*)rl.origins + first * 3;
+    vr_gcfloat_t* const sd = (vr_gcfloat_t*)rl.dirs + first * 3;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int f = c * kWave + lane;
+        if (f < count * 3) {  // (nothing is read behind the list's last float)
+            tr[wave][0][f] = so[f];
+            tr[wave][1][f] = sd[f];
+        }
+    }
+    __syncthreads();
+    id = (uint32_t)first + (uint32_t)lane;
+    reset_ray(ray);
+    if (lane >= count) return false;
+    if (p.N <= 0) return true;  // enable_draw = tree.N > 0
+    float cen[3], dir[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        cen[c] = tr[wave][0][lane * 3 + c];
+        dir[c] = tr[wave][1][lane * 3 + c];
+    }
+    normalize3<FMA>(dir);
+    setup_ray_from<FMA>(p, cen, dir, ray, vdir, []() -> float { return 1e9f; });
+    return true;
 }
 
 }  // namespace

@@ -102,6 +102,26 @@ __global__ __launch_bounds__(kWave* GW) void grad_raygen_kernel(const KParams p)
     ray_word(rb, kGradRayPixel) = pixel;
 }
 
+// grad_raygen_rays_kernel: the same for a ray list (vr_render_backward_rays): the ray is list_ray()'s, and its
+// row of grad_accum is its index in the list.
+template <int FMA, int GW>
+__global__ __launch_bounds__(kWave* GW) void grad_raygen_rays_kernel(const KParams p, const RayList rl) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    uint32_t id;
+    Ray nr;
+    float vdir[3] = {0.f, 0.f, 0.f};
+    const bool valid = list_ray<FMA, GW>(p, rl, lane, wave, id, nr, vdir) && nr.alive;
+    const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
+    const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
+    if (!valid) return;
+    uint32_t* rb = ray_slot(p.ray_buf_rw, kGradRayWords, my_base + lane_rank(m_valid));
+    store_march_words(rb, nr);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) ray_word(rb, kGradRayVdir + i) = f2u(vdir[i]);
+    ray_word(rb, kGradRayPixel) = id;
+}
+
 // ---------------------------------------------------------------------------
 // grad_kernel: the persistent march (weights_kernel's frame: one wave per workgroup, chunks of ray ids,
 // batched refill, the sample guard), two phases per ray and the wave-wide scatter described at the top.
@@ -412,9 +432,15 @@ void launch_march_basis(const KParams& p, const GradParams& gp, dim3 grid, hipSt
 
 template <int FMA>
 hipError_t launch_fp(const KParams& p, const GradParams& gp, int n_cus, int waves_override, int gen_waves,
-                     hipStream_t s) {
+                     hipStream_t s, const RayList* rays) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
-    if (gen_waves >= 16)
+    if (rays && gen_waves >= 16)
+        hipLaunchKernelGGL((grad_raygen_rays_kernel<FMA, 16>), dim3((unsigned)((total_blocks + 15) / 16)),
+                           dim3(kWave * 16), 0, s, p, *rays);
+    else if (rays)
+        hipLaunchKernelGGL((grad_raygen_rays_kernel<FMA, 4>), dim3((unsigned)((total_blocks + 3) / 4)),
+                           dim3(kWave * 4), 0, s, p, *rays);
+    else if (gen_waves >= 16)
         hipLaunchKernelGGL((grad_raygen_kernel<FMA, 16>), dim3((unsigned)((total_blocks + 15) / 16)),
                            dim3(kWave * 16), 0, s, p);
     else
@@ -430,10 +456,10 @@ hipError_t launch_fp(const KParams& p, const GradParams& gp, int n_cus, int wave
 }  // namespace
 
 hipError_t launch_grad(const KParams& p, const GradParams& gp, int fp_mode, int n_cus, int waves_override,
-                       int gen_waves, hipStream_t stream) {
+                       int gen_waves, hipStream_t stream, const RayList* rays) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    return fp_mode == VR_FP_FMA ? launch_fp<1>(p, gp, n_cus, waves_override, gen_waves, stream)
-                                : launch_fp<0>(p, gp, n_cus, waves_override, gen_waves, stream);
+    return fp_mode == VR_FP_FMA ? launch_fp<1>(p, gp, n_cus, waves_override, gen_waves, stream, rays)
+                                : launch_fp<0>(p, gp, n_cus, waves_override, gen_waves, stream, rays);
 }
 
 }  // namespace vr

@@ -237,10 +237,31 @@ struct WeightParams {
     const int32_t* file_node;   // device node -> the file's node (VrTreeOpaque.file_node)
 };
 
+// ---------------------------------------------------------------------------
+// Ray lists (vr_render_rays, vr_accumulate_weights_rays, vr_render_backward_rays): the rays of a launch come
+// from two caller arrays and not from locate() and a pose.  Only ray generation differs -- the kernels
+// raygen_rays_kernel, weights_raygen_rays_kernel and grad_raygen_rays_kernel take KParams unchanged plus this
+// second argument and write the records of their frame siblings into the same queues; the march kernels are
+// the frame launches'.  To them a list is ONE offscreen pseudo-frame kRayListWidth pixels wide whose pixel
+// y * width + x is ray i: x = i & (kRayListWidth - 1), y = i >> kRayListShift (both below 2^15: i < 2^30),
+// frames[0].rgba / .accum = the arrays of the call.  That is all the colour march reads of a frame's geometry
+// (finish_ray: KParams.width, and the record's pixel address); the other two read none of it.
+// ---------------------------------------------------------------------------
+constexpr int kRayListShift = 15;
+constexpr int kRayListWidth = 1 << kRayListShift;
+struct RayList {
+    const float* origins;  // device, [n][3], world space
+    const float* dirs;     // device, [n][3], world space, any finite non-zero length
+    int64_t n;
+};
+// whole blocks of 64 rays: what KParams.total_rays holds for a list (lanes with id >= n stay idle)
+__host__ __device__ inline uint32_t ray_list_slots(int64_t n) { return (uint32_t)(((n + 63) >> 6) << 6); }
+
 // vr_weights.hip: ray generation + the persistent march of a leaf-weight launch (the frame table and the
 // queue reset are launch_prepare's).  check_first: the max reads the word before it issues the atomic.
+// rays: the launch marches this list (its ray generation reads it) and not the pixels of the frame table.
 hipError_t launch_weights(const KParams& p, const WeightParams& w, int fp_mode, int n_cus, int waves_override,
-                          int gen_waves, bool check_first, hipStream_t stream);
+                          int gen_waves, bool check_first, hipStream_t stream, const RayList* rays = nullptr);
 
 // ---------------------------------------------------------------------------
 // Backward launches (vr_render_backward): the march of a leaf-weight launch that shades inline and scatters
@@ -261,8 +282,9 @@ struct GradParams {
 };
 
 // vr_grad.hip: ray generation + the persistent two-phase march of a backward launch
+// (rays: as launch_weights; GradParams.grad_accum is then [n][4], row i for ray i)
 hipError_t launch_grad(const KParams& p, const GradParams& g, int fp_mode, int n_cus, int waves_override,
-                       int gen_waves, hipStream_t stream);
+                       int gen_waves, hipStream_t stream, const RayList* rays = nullptr);
 
 // ---------------------------------------------------------------------------
 // Value passes (vr_tree_update_data / vr_tree_read_data, vr_update.hip): the tree's values between the file's
@@ -289,8 +311,9 @@ hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream
 hipError_t launch_render_aov(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
                              int gen_waves, hipStream_t stream);
 hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream);
+// (rays: as launch_weights; the frame table then holds the list's one pseudo-frame)
 hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
-                         hipStream_t stream);
+                         hipStream_t stream, const RayList* rays = nullptr);
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
                         hipStream_t stream);
 

@@ -1,5 +1,6 @@
 // vr_launch.cpp -- launches (include/volrend_hip.h): vr_render_batch, vr_render_aov, vr_accumulate_weights,
-// vr_render_backward, vr_reserve*, vr_tree_status*, the value passes vr_tree_update_data / vr_tree_read_data
+// vr_render_backward, their ray-list siblings vr_render_rays / vr_accumulate_weights_rays /
+// vr_render_backward_rays, vr_reserve*, vr_tree_status*, the value passes vr_tree_update_data / vr_tree_read_data
 // (which share the file-order table of the march launches), the launch geometry and the launch-slot ring.  Built with -ffp-contract=off (the host-side
 // Rodrigues pre-computation below must round like the oracle).
 #include <hip/hip_runtime.h>
@@ -33,6 +34,9 @@ int ray_tail_words_of(const VrTreeOpaque* t) {
 size_t ray_buffer_bytes(uint32_t total_rays, int words_per_ray) {
     return vr::ray_slots(total_rays) * (size_t)words_per_ray * sizeof(uint32_t);
 }
+
+// vr_render_rays without an rgba array: the pixel words the march stores anyway, behind the records
+size_t list_pixel_bytes(uint32_t total_rays) { return (size_t)total_rays * 4; }
 
 // Replaces the ray buffer of a slot the caller owns (it holds the launch mutex, or has marked the
 // slot `growing` and dropped it) by one of `bytes`.  The slot's last launch must have finished
@@ -116,6 +120,24 @@ int launch_geometry(int width, int height, int tile_w, int tile_h, int rank, int
 
 namespace {  // the steps of a launch: vr_render_batch, vr_render_aov, vr_accumulate_weights, vr_render_backward
 
+// launch_geometry for a list of n rays (vr::RayList): the one pseudo-frame of vr::kRayListWidth pixels a row
+// whose pixel y * width + x is ray i, as whole blocks of 64 rays.  `what` names the function in the refusal.
+int list_geometry(const char* what, int64_t n, vr::KParams& k) {
+    if (n < 0 || n >= (1ll << 30))  // (the limit of launch_geometry: 32-bit byte offsets into the ray buffer)
+        return fail(VR_ERR_INVALID_ARGUMENT, "%s: n=%lld outside [0, 2^30)", what, (long long)n);
+    k.total_rays = vr::ray_list_slots(n);
+    k.n_wave_blocks = k.total_rays >> 6;
+    k.n_frames = n > 0 ? 1 : 0;
+    k.width = vr::kRayListWidth;
+    k.height = (int32_t)((n + vr::kRayListWidth - 1) >> vr::kRayListShift);
+    k.fx = k.fy = 1.f;  // (nothing reads them: a list has no pixels to turn into directions)
+    k.pitch = (int64_t)k.width * 4;
+    k.tile_w = k.width;
+    k.tile_h = (k.height + 7) & ~7;
+    k.tiles_x = k.tiles_y = k.world = k.n_local_tiles = 1;
+    return VR_OK;
+}
+
 // The view checks: the launch has a focal length, and frame i the intrinsics of frame 0.
 int check_focal(const VrCamera& cam) {
     if (!(cam.fx != 0.f) || !(cam.fy != 0.f)) return fail(VR_ERR_INVALID_ARGUMENT, "focal length must be non-zero");
@@ -181,12 +203,15 @@ int validate_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRend
     return VR_OK;
 }
 
-// What the march reads of the caller's arguments: the intrinsics and four options.
+// What the march reads of the caller's arguments: the intrinsics (cam = NULL: a ray list, whose pseudo-frame
+// list_geometry left in `k`) and four options.
 void fill_march_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptions* opt) {
-    k.width = cam->width;
-    k.height = cam->height;
-    k.fx = cam->fx;
-    k.fy = cam->fy;
+    if (cam) {
+        k.width = cam->width;
+        k.height = cam->height;
+        k.fx = cam->fx;
+        k.fy = cam->fy;
+    }
     k.step_size = opt->step_size;
     k.sigma_thresh = opt->sigma_thresh;
     k.stop_thresh = opt->stop_thresh;
@@ -194,7 +219,7 @@ void fill_march_params(vr::KParams& k, const VrCamera* cam, const VrRenderOption
 }
 
 // The part of KParams that comes from the caller: intrinsics, options, the launch-uniform half of
-// the view-direction rotation, and how the frames are written (`f` = the first frame).
+// the view-direction rotation, and how the frames are written (`f` = the first frame; cam = NULL: a ray list).
 void fill_caller_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptions* opt, const VrFrame* f) {
     fill_march_params(k, cam, opt);
     k.background_brightness = opt->background_brightness;
@@ -233,6 +258,8 @@ void fill_caller_params(vr::KParams& k, const VrCamera* cam, const VrRenderOptio
 //   * super_block: 4 (blocks visited in 4 x 4 super-blocks: consecutive chunks are screen neighbours in
 //     both directions) for launches of three frames and more, row-major for the small ones, which it
 //     costs 2 % (measured at one frame; four frames: no difference).
+// A colour launch of a ray list takes the colour rule's 256; super_block orders the blocks of a SCREEN and is
+// never consulted for a list (its ray generation does not call locate()).
 constexpr int kColourChunkCap = 256, kGuidedChunkCap = 4096;
 int auto_chunk_max(const Tuning& tn, bool colour) {
     return tn.chunk_max > 0 ? tn.chunk_max : colour ? kColourChunkCap : kGuidedChunkCap;
@@ -402,6 +429,18 @@ int enqueue_tables(const vr::KParams& k, const VrCamera* cams, hipStream_t hs, c
     return VR_OK;
 }
 
+// The same for a ray list: its one pseudo-frame (no pose; rgba / accum = the arrays ray i indexes, NULL for a
+// leaf-weight or backward launch, which only needs the queue reset).
+int enqueue_list_table(const vr::KParams& k, void* rgba, float* accum, hipStream_t hs) {
+    vr::FrameTable tbl;
+    memset(&tbl, 0, sizeof(tbl));
+    tbl.n = 1;
+    tbl.f[0].rgba = static_cast<uint8_t*>(rgba);
+    tbl.f[0].accum = accum;
+    HIP_TRY(vr::launch_prepare(k, tbl, hs));
+    return VR_OK;
+}
+
 // waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
 // two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
 // 4 waves find room there much earlier (vr_render.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
@@ -409,6 +448,14 @@ int enqueue_tables(const vr::KParams& k, const VrCamera* cams, hipStream_t hs, c
 // 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
 int raygen_waves(const Tuning& tn, int n_frames) {
     return tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
+}
+// A ray list: the same reasoning by ray count.  The frame rule was measured at 800 x 800 pixels, where "two
+// frames" are 1 280 000 rays: lists up to kRayListSmall rays -- an optimiser's step, which runs beside the tail
+// of the step before it -- generate in workgroups of 4 waves, larger ones in 16.  UNMEASURED for lists: the
+// boundary is the frame rule's, restated in rays.  (List ray generation has no one-wave flavour.)
+constexpr int64_t kRayListSmall = 2 * 800 * 800;
+int raygen_waves_list(const Tuning& tn, int64_t n) {
+    return tn.raygen_waves > 0 ? (tn.raygen_waves >= 16 ? 16 : 4) : (n <= kRayListSmall ? 4 : 16);
 }
 
 // vr_render_batch (aovs = NULL) and vr_render_aov: one launch, in steps.  Into the stream go, behind the slot's
@@ -493,7 +540,8 @@ int ensure_file_nodes(VrTreeOpaque* t) {
 
 // What a leaf-weight launch and a backward launch share once their arguments are checked: the file-order
 // table, an offscreen frame without mesh depth, probe, depth mode or view-direction rotation, a slot for rays
-// of `ray_words` words, the pose table, and then launch(k, tuning, stream).
+// of `ray_words` words, the pose table (cams = NULL, a ray list: the pseudo-frame), and then
+// launch(k, tuning, stream).
 template <typename Launch>
 int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, vr::KParams& k,
                  int ray_words, void* stream, Launch&& launch) {
@@ -501,8 +549,8 @@ int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRender
     hipStream_t hs = static_cast<hipStream_t>(stream);
     std::unique_lock<std::mutex> guard(t->launch_mutex);
     if (int rc = ensure_file_nodes(t)) return rc;
-    if (n_frames == 0) return VR_OK;  // the warm-up call
-    fill_march_params(k, &cams[0], opt);
+    if (n_frames == 0) return VR_OK;  // the warm-up call (a ray list: n == 0)
+    fill_march_params(k, cams ? &cams[0] : nullptr, opt);  // (cams = NULL: a ray list, `k` holds list_geometry's frame)
     k.offscreen = 1;
     k.layout = VR_LAYOUT_FRAME;
     k.pitch = (int64_t)k.width * 4;
@@ -513,28 +561,55 @@ int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRender
     if (int rc = acquire_slot(t, guard, hs, k, ray_buffer_bytes(k.total_rays, ray_words), slot)) return rc;
     SlotTurn turn;
     if (int rc = turn.begin(t->slots[slot], hs)) return rc;
-    if (int rc = enqueue_tables(k, cams, hs)) return rc;
+    if (int rc = cams ? enqueue_tables(k, cams, hs) : enqueue_list_table(k, nullptr, nullptr, hs)) return rc;
     HIP_TRY(launch(k, tn, hs));
     return VR_OK;  // (`turn` records the slot's event)
 }
 
-int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
-                       const VrLeafWeights* out, void* stream) {
-    vr::KParams k;
-    memset(&k, 0, sizeof(k));
-    if (int rc = validate_weights(t, n_frames, cams, opt, fp_mode, out, k)) return rc;
+// The checks of a ray list that need no tree, in front of the function's own: the list itself, the FP model, the
+// count and the step.  Leaves the list's geometry in `k` and the list in `rl`.
+int validate_rays(const char* what, vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
+                  int fp_mode, const void* out, vr::KParams& k, vr::RayList& rl) {
+    if (!t || !rays || !rays->origins || !rays->dirs || !opt || !out)
+        return fail(VR_ERR_INVALID_ARGUMENT, "%s: NULL argument", what);
+    if (fp_mode != VR_FP_STRICT && fp_mode != VR_FP_FMA)
+        return fail(VR_ERR_INVALID_ARGUMENT, "%s: unknown fp_mode %d", what, fp_mode);
+    if (int rc = list_geometry(what, n, k)) return rc;
+    if (int rc = check_step_size(opt)) return rc;
+    rl.origins = rays->origins;
+    rl.dirs = rays->dirs;
+    rl.n = n;
+    return VR_OK;
+}
+
+// vr_accumulate_weights (rays = NULL) and vr_accumulate_weights_rays (cams = NULL; n_frames = 1, or 0 for an
+// empty list): `k` holds the checked geometry.
+int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const vr::RayList* rays,
+                       const VrRenderOptions* opt, int fp_mode, const VrLeafWeights* out, vr::KParams& k, void* stream) {
     return march_launch(t, n_frames, cams, opt, k, vr::kWeightRayWords, stream,
                         [&](const vr::KParams& kp, const Tuning& tn, hipStream_t hs) {
                             vr::WeightParams w;
                             w.max_weight = reinterpret_cast<uint32_t*>(out->max_weight);
                             w.hits = out->hits;
                             w.file_node = t->file_node_dev.get<int32_t>();
-                            return vr::launch_weights(kp, w, fp_mode, t->n_cus, tn.waves_per_cu,
-                                                      raygen_waves(tn, n_frames), tn.weights_check != 0, hs);
+                            const int gen = rays ? raygen_waves_list(tn, rays->n) : raygen_waves(tn, n_frames);
+                            return vr::launch_weights(kp, w, fp_mode, t->n_cus, tn.waves_per_cu, gen,
+                                                      tn.weights_check != 0, hs, rays);
                         });
 }
 
 // ---- vr_render_backward ----
+
+// What the backward refuses of the options without a tree (`what` names the function).
+int check_backward_options(const char* what, const VrRenderOptions* opt) {
+    if (opt->render_depth)
+        return fail(VR_ERR_UNSUPPORTED, "%s with render_depth: the depth visualisation has no derivative here", what);
+    if (opt->enable_probe)
+        return fail(VR_ERR_UNSUPPORTED, "%s with enable_probe: pixels under the probe disc are not traced", what);
+    if (!(opt->rot_dirs[0] == 0.f) || !(opt->rot_dirs[1] == 0.f) || !(opt->rot_dirs[2] == 0.f))
+        return fail(VR_ERR_UNSUPPORTED, "%s with rot_dirs: the view direction is not rotated", what);
+    return VR_OK;
+}
 
 // Everything that can be refused without following the tree handle.
 int validate_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
@@ -542,42 +617,76 @@ int validate_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrR
     if (!t || !opt || !grad_accum || !grad_data || (n_frames > 0 && !cams))
         return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (int rc = validate_march(n_frames, cams, opt, fp_mode, k)) return rc;
-    if (opt->render_depth)
-        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward with render_depth: the depth visualisation has no derivative here");
-    if (opt->enable_probe)
-        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward with enable_probe: pixels under the probe disc are not traced");
-    if (!(opt->rot_dirs[0] == 0.f) || !(opt->rot_dirs[1] == 0.f) || !(opt->rot_dirs[2] == 0.f))
-        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward with rot_dirs: the view direction is not rotated");
-    return VR_OK;
+    return check_backward_options("vr_render_backward", opt);
 }
 
 // What needs the tree: the formats the backward kernels shade, and the whole basis.
-int check_backward_tree(const VrTreeOpaque* t, const VrRenderOptions* opt) {
+int check_backward_tree(const VrTreeOpaque* t, const VrRenderOptions* opt, const char* what) {
     const int format = t->desc.format, basis_dim = t->desc.basis_dim;
     if (format == VR_FORMAT_SG || format == VR_FORMAT_ASG)
-        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward: SG / ASG trees are not supported");
+        return fail(VR_ERR_UNSUPPORTED, "%s: SG / ASG trees are not supported", what);
     if (vr::basis_flavour(format, basis_dim) != vr::BASIS_RGBA &&
         (opt->basis_minmax[0] > 0 || opt->basis_minmax[1] < basis_dim - 1))
-        return fail(VR_ERR_UNSUPPORTED, "vr_render_backward: basis_minmax [%d, %d] leaves out basis functions of the tree (%d)",
+        return fail(VR_ERR_UNSUPPORTED, "%s: basis_minmax [%d, %d] leaves out basis functions of the tree (%d)", what,
                     opt->basis_minmax[0], opt->basis_minmax[1], basis_dim);
     return VR_OK;
 }
 
-int render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
-                    const float* grad_accum, float* grad_data, void* stream) {
-    vr::KParams k;
-    memset(&k, 0, sizeof(k));
-    if (int rc = validate_backward(t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, k)) return rc;
-    if (int rc = check_backward_tree(t, opt)) return rc;
+// vr_render_backward (rays = NULL) and vr_render_backward_rays (cams = NULL), as accumulate_weights.
+int render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const vr::RayList* rays,
+                    const VrRenderOptions* opt, int fp_mode, const float* grad_accum, float* grad_data,
+                    vr::KParams& k, void* stream) {
+    if (int rc = check_backward_tree(t, opt, rays ? "vr_render_backward_rays" : "vr_render_backward")) return rc;
     return march_launch(t, n_frames, cams, opt, k, vr::kGradRayWords, stream,
                         [&](const vr::KParams& kp, const Tuning& tn, hipStream_t hs) {
                             vr::GradParams g;
                             g.grad_accum = grad_accum;
                             g.grad_data = grad_data;
                             g.file_node = t->file_node_dev.get<int32_t>();
-                            return vr::launch_grad(kp, g, fp_mode, t->n_cus, tn.waves_per_cu,
-                                                   raygen_waves(tn, n_frames), hs);
+                            const int gen = rays ? raygen_waves_list(tn, rays->n) : raygen_waves(tn, n_frames);
+                            return vr::launch_grad(kp, g, fp_mode, t->n_cus, tn.waves_per_cu, gen, hs, rays);
                         });
+}
+
+// ---- vr_render_rays ----
+
+// One colour launch of a ray list: render_launch's steps with the list's pseudo-frame for the frame table.  A
+// call without rgba still has the march store a pixel word per ray: 4 bytes per ray of the slot's ray buffer,
+// behind the records.
+int render_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
+                const VrRayOut* out, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    vr::RayList rl;
+    if (int rc = validate_rays("vr_render_rays", t, n, rays, opt, fp_mode, out, k, rl)) return rc;
+    if (!out->rgba && !out->accum) return fail(VR_ERR_INVALID_ARGUMENT, "vr_render_rays: both outputs are NULL");
+    if (opt->render_depth)
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_rays with render_depth: the depth visualisation is not what a ray list is for");
+    if (opt->enable_probe)
+        return fail(VR_ERR_UNSUPPORTED, "vr_render_rays with enable_probe: the probe disc is a set of pixel positions");
+    if (n == 0) return VR_OK;
+    DeviceGuard device_guard(t->device);
+    VrFrame f;
+    memset(&f, 0, sizeof(f));
+    f.offscreen = 1;
+    f.layout = VR_LAYOUT_FRAME;
+    f.fp_mode = fp_mode;
+    fill_caller_params(k, nullptr, opt, &f);
+    k.any_accum = out->accum ? 1 : 0;
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    std::unique_lock<std::mutex> guard(t->launch_mutex);
+    fill_tree_params(k, t);  // (under the mutex: vr_touch_enable / vr_touch_count (re)allocate the bitmaps)
+    const Tuning tn = t->tn;  // (a copy: the mutex is dropped once in acquire_slot, while a slot grows)
+    fill_tuning_params(k, t, tn, true);
+    const size_t records = ray_buffer_bytes(k.total_rays, vr::kRayWords + k.ray_tail_words);
+    unsigned slot;
+    if (int rc = acquire_slot(t, guard, hs, k, records + (out->rgba ? 0 : list_pixel_bytes(k.total_rays)), slot)) return rc;
+    void* const rgba = out->rgba ? out->rgba : static_cast<void*>(t->slots[slot].rays.get<char>() + records);
+    SlotTurn turn;
+    if (int rc = turn.begin(t->slots[slot], hs)) return rc;
+    if (int rc = enqueue_list_table(k, rgba, out->accum, hs)) return rc;
+    HIP_TRY(vr::launch_render(k, fp_mode, t->n_cus, tn.waves_per_cu, raygen_waves_list(tn, n), hs, &rl));
+    return VR_OK;  // (`turn` records the slot's event)
 }
 
 // ---- vr_tree_update_data / vr_tree_read_data ----
@@ -631,6 +740,19 @@ int tree_data_pass(vr_tree_t t, void* data_dev, int dtype, void* stream, bool up
     return VR_OK;
 }
 
+// vr_reserve_tiles / vr_reserve_rays: the ray buffers of the first n_slots slots hold `need` bytes.
+int reserve_slots(VrTreeOpaque* t, int n_slots, size_t need) {
+    DeviceGuard device_guard(t->device);
+    std::lock_guard<std::mutex> guard(t->launch_mutex);
+    for (int i = 0; i < n_slots; ++i) {
+        LaunchSlot& ls = t->slots[i];
+        if (ls.growing || ls.rays.bytes() >= need) continue;
+        const hipError_t e = replace_ray_buffer(ls, need);
+        if (e != hipSuccess) return fail(hip_code(e), "ray buffer of %zu bytes: %s", need, hipGetErrorString(e));
+    }
+    return VR_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -645,12 +767,56 @@ int vr_tree_read_data(vr_tree_t t, void* data_dev, int dtype, void* stream) {
 
 int vr_render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
                        const float* grad_accum, float* grad_data, void* stream) {
-    return render_backward(t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, stream);
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = validate_backward(t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, k)) return rc;
+    return render_backward(t, n_frames, cams, nullptr, opt, fp_mode, grad_accum, grad_data, k, stream);
+}
+
+int vr_render_backward_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
+                            const float* grad_accum, float* grad_data, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    vr::RayList rl;
+    if (!grad_accum) return fail(VR_ERR_INVALID_ARGUMENT, "vr_render_backward_rays: NULL argument");
+    if (int rc = validate_rays("vr_render_backward_rays", t, n, rays, opt, fp_mode, grad_data, k, rl)) return rc;
+    if (int rc = check_backward_options("vr_render_backward_rays", opt)) return rc;
+    return render_backward(t, k.n_frames, nullptr, &rl, opt, fp_mode, grad_accum, grad_data, k, stream);
 }
 
 int vr_accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
                           int fp_mode, const VrLeafWeights* out, void* stream) {
-    return accumulate_weights(t, n_frames, cams, opt, fp_mode, out, stream);
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (int rc = validate_weights(t, n_frames, cams, opt, fp_mode, out, k)) return rc;
+    return accumulate_weights(t, n_frames, cams, nullptr, opt, fp_mode, out, k, stream);
+}
+
+int vr_accumulate_weights_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
+                               const VrLeafWeights* out, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    vr::RayList rl;
+    if (int rc = validate_rays("vr_accumulate_weights_rays", t, n, rays, opt, fp_mode, out, k, rl)) return rc;
+    if (!out->max_weight && !out->hits)
+        return fail(VR_ERR_INVALID_ARGUMENT, "vr_accumulate_weights_rays: both outputs are NULL");
+    return accumulate_weights(t, k.n_frames, nullptr, &rl, opt, fp_mode, out, k, stream);
+}
+
+int vr_render_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
+                   const VrRayOut* out, void* stream) {
+    return render_rays(t, n, rays, opt, fp_mode, out, stream);
+}
+
+// the slots sized for the largest ray call of n rays: colour records plus the pixel words of a call without rgba
+int vr_reserve_rays(vr_tree_t t, int64_t n, int n_slots) {
+    if (!t) return fail(VR_ERR_INVALID_ARGUMENT, "vr_reserve_rays: tree is NULL");
+    if (n_slots < 1 || n_slots > (int)kLaunchSlots)
+        return fail(VR_ERR_INVALID_ARGUMENT, "vr_reserve_rays: n_slots=%d outside [1,%u]", n_slots, kLaunchSlots);
+    vr::KParams geo;
+    if (int rc = list_geometry("vr_reserve_rays", n, geo)) return rc;
+    return reserve_slots(t, n_slots, ray_buffer_bytes(geo.total_rays, vr::kRayWords + ray_tail_words_of(t)) +
+                                         list_pixel_bytes(geo.total_rays));
 }
 
 int vr_render_batch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
@@ -674,16 +840,7 @@ int vr_reserve_tiles(vr_tree_t t, int width, int height, int n_frames, int tile_
     // exactly the ray count vr_render_batch computes, for rank 0 (which holds the most tiles)
     vr::KParams geo;
     if (int rc = launch_geometry(width, height, tile_w, tile_h, 0, world, n_frames, geo)) return rc;
-    const size_t need = ray_buffer_bytes(geo.total_rays, vr::kRayWords + ray_tail_words_of(t));
-    DeviceGuard device_guard(t->device);
-    std::lock_guard<std::mutex> guard(t->launch_mutex);
-    for (int i = 0; i < n_slots; ++i) {
-        LaunchSlot& ls = t->slots[i];
-        if (ls.growing || ls.rays.bytes() >= need) continue;
-        const hipError_t e = replace_ray_buffer(ls, need);
-        if (e != hipSuccess) return fail(hip_code(e), "ray buffer of %zu bytes: %s", need, hipGetErrorString(e));
-    }
-    return VR_OK;
+    return reserve_slots(t, n_slots, ray_buffer_bytes(geo.total_rays, vr::kRayWords + ray_tail_words_of(t)));
 }
 
 // two slots of whole frames: what a render loop on one stream (one slot) or on two alternating

@@ -167,6 +167,44 @@ __device__ __forceinline__ void store_aov(const AovParams& a, int frame, uint32_
     if (pl.transmittance) *(vr_gfloat_t*)(reinterpret_cast<char*>(pl.transmittance) + off) = tr;
 }
 
+// The record of a colour ray (vr_internal.h kRay*), into ray slot `slot`: what raygen_rays_kernel appends for a
+// ray that enters the volume -- the tail of raygen_kernel, word for word.  (raygen_kernel keeps its own copy:
+// calling this function from it changes the machine code of the frame kernels, tools/kernel_digest.py.)
+template <int FMA, bool FULL>
+__device__ __forceinline__ void store_colour_ray(const KParams& p, uint32_t slot, const Ray& nr, uint32_t xy,
+                                                 uint8_t* px, int frame, const float* vdir) {
+    uint32_t* rb = ray_slot(p.ray_buf_rw, kRayWords + p.ray_tail_words, slot);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        ray_word(rb, kRayCen + i) = f2u(nr.cen[i]);
+        ray_word(rb, kRayDir + i) = f2u(nr.dir[i]);
+        ray_word(rb, kRayInvDir + i) = f2u(nr.invdir[i]);
+    }
+    ray_word(rb, kRayT) = f2u(nr.t);
+    ray_word(rb, kRayTmax) = f2u(nr.tmax);
+    ray_word(rb, kRayDeltaScale) = f2u(nr.delta_scale);
+    ray_word(rb, kRayXy) = xy;
+    ray_word(rb, kRayPixelLo) = (uint32_t)reinterpret_cast<uint64_t>(px);
+    ray_word(rb, kRayPixelHi) = (uint32_t)(reinterpret_cast<uint64_t>(px) >> 32);
+    ray_word(rb, kRayFrame) = (uint32_t)frame;
+    if (p.ray_vdir) {
+        // SH trees: the (rotated) view direction travels, its basis is evaluated when a lane takes
+        // the ray (3 words instead of up to 25: the ray buffer is written and read once per ray)
+#pragma unroll
+        for (int i = 0; i < 3; ++i) ray_word(rb, kRayTail + i) = f2u(vdir[i]);
+    } else if (p.basis_words > 0) {
+        // rt_core.cuh:96-103: basis of the view direction, zeroed outside basis_minmax
+        float b[VR_MAX_BASIS];
+#pragma unroll
+        for (int i = 0; i < VR_MAX_BASIS; ++i) b[i] = 0.f;
+        precalc_basis<FMA, FULL>(p, vdir, b);
+#pragma unroll
+        for (int i = 0; i < VR_MAX_BASIS; ++i)
+            if (i < p.basis_words)
+                ray_word(rb, kRayTail + i) = f2u((i < p.basis_min || i > p.basis_max) ? 0.f : b[i]);
+    }
+}
+
 // names and arguments of the kernel pair of this pass (the colour pair; the AOV pair: behind raygen_kernel)
 #define VR_RENDER_KERNEL render_kernel
 #define VR_RAYGEN_KERNEL raygen_kernel
@@ -742,6 +780,41 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
 #undef VR_KERNEL_AOV
 #undef VR_KERNEL_AOV_LOCAL
 
+// ---------------------------------------------------------------------------
+// raygen_rays_kernel: raygen_kernel for a ray list (vr_render_rays; vr_internal.h RayList): one lane per ray,
+// 64 consecutive rays per wave in the caller's order.  The ray comes from list_ray() instead of locate() +
+// setup_ray; its "pixel" is element `id` of the pseudo-frame's arrays.  A ray that misses the volume is
+// composited and stored here, the others are compacted into the queues as raygen_kernel's records -- lanes
+// behind the list's end neither reserve nor store.  (Compiled in the first pass of this file only: a list
+// has no AOV planes.)
+// ---------------------------------------------------------------------------
+template <int FMA, bool FULL, int GW>
+__global__ __launch_bounds__(kWave* GW) void raygen_rays_kernel(const KParams p, const RayList rl) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    uint32_t id;
+    Ray nr;
+    float vdir[3] = {0.f, 0.f, 1.f};
+    const bool has = list_ray<FMA, GW>(p, rl, lane, wave, id, nr, vdir);
+    bool valid = false;
+    uint8_t* px = nullptr;
+    uint32_t xy = 0;
+    if (has) {
+        xy = (id & (uint32_t)(kRayListWidth - 1)) | ((id >> kRayListShift) << 16);
+        px = p.frames[0].rgba + (int64_t)id * 4;
+        if (nr.alive) {
+            valid = true;
+        } else {
+            RayCounters z;  // a ray without a single sample
+            finish_ray<FMA, false>(p, nr, z, px, xy, 0);  // (COUNT: counters and depth mode, which a list never has)
+        }
+    }
+    const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
+    const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
+    if (!valid) return;
+    store_colour_ray<FMA, FULL>(p, my_base + lane_rank(m_valid), nr, xy, px, 0, vdir);
+}
+
 // Writes the per-launch frame table into device memory and resets the ray queue.
 // (Stream-ordered replacement for a pinned-memory H2D copy + memset.)
 __global__ void prepare_launch_kernel(FrameTable tbl, FrameDesc* frames, uint32_t* queue_head) {
@@ -877,9 +950,10 @@ hipError_t launch_fp(const KParams& p, const AovParams& a, int64_t total_blocks,
 }
 
 // Ray generation + the persistent march of one launch (the probe overlay is launch_render's own).
+// rays: a ray list takes the place of the frames' pixels (never with AOV planes).
 template <bool AOV>
 hipError_t launch_march(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
-                        int gen_waves, hipStream_t stream) {
+                        int gen_waves, hipStream_t stream, const RayList* rays = nullptr) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
     {   // ray generation: gen_waves wave blocks (8x8 pixels each) per workgroup
         const bool full = needs_full(p);
@@ -887,12 +961,15 @@ hipError_t launch_march(const KParams& p, const AovParams& a, int fp_mode, int n
     do {                                                                                            \
         const dim3 grid_((unsigned)((total_blocks + GW_ - 1) / GW_)), block_(kWave * GW_);          \
         if constexpr (AOV) hipLaunchKernelGGL((raygen_aov_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, a); \
+        else if (rays) {                                                                            \
+            if constexpr (GW_ >= 4) hipLaunchKernelGGL((raygen_rays_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, *rays); \
+        }                                                                                           \
         else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p);    \
     } while (0)
 #define VR_GEN_GW(FMA_, FULL_)                                                                      \
     do {                                                                                            \
         if (gen_waves >= 16) VR_GEN(FMA_, FULL_, 16);                                               \
-        else if (gen_waves >= 4) VR_GEN(FMA_, FULL_, 4);                                            \
+        else if (gen_waves >= 4 || rays) VR_GEN(FMA_, FULL_, 4);  /* (a list: 16 or 4) */           \
         else VR_GEN(FMA_, FULL_, 1);                                                                \
     } while (0)
         if (fp_mode == VR_FP_FMA) {
@@ -917,9 +994,9 @@ hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t s
 }
 
 hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
-                         hipStream_t stream) {
+                         hipStream_t stream, const RayList* rays) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    const hipError_t e = launch_march<false>(p, AovParams{}, fp_mode, n_cus, waves_override, gen_waves, stream);
+    const hipError_t e = launch_march<false>(p, AovParams{}, fp_mode, n_cus, waves_override, gen_waves, stream, rays);
     if (e != hipSuccess || !p.enable_probe || p.probe_disp_size <= 0) return e;
     const int side = p.probe_disp_size + 5;
     const dim3 pgrid((unsigned)((side * side + 255) / 256), (unsigned)p.n_frames);

@@ -67,6 +67,21 @@ __global__ __launch_bounds__(kWave* GW) void weights_raygen_kernel(const KParams
     ray_word(rb, kRayDeltaScale) = f2u(nr.delta_scale);
 }
 
+// weights_raygen_rays_kernel: the same for a ray list (vr_accumulate_weights_rays): the ray is list_ray()'s.
+template <int FMA, int GW>
+__global__ __launch_bounds__(kWave* GW) void weights_raygen_rays_kernel(const KParams p, const RayList rl) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = threadIdx.x >> 6;
+    uint32_t id;
+    Ray nr;
+    float vdir[3];  // (nothing here reads it)
+    const bool valid = list_ray<FMA, GW>(p, rl, lane, wave, id, nr, vdir) && nr.alive;
+    const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
+    const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
+    if (!valid) return;
+    store_march_words(ray_slot(p.ray_buf_rw, kWeightRayWords, my_base + lane_rank(m_valid)), nr);
+}
+
 // ---------------------------------------------------------------------------
 // weights_kernel: the persistent march.  One wave per workgroup; a wave owns a chunk of consecutive ray
 // ids (grab_chunk) and refills its idle lanes once refill_min of them wait; the sample guard is
@@ -250,9 +265,15 @@ void launch_march_check(const KParams& p, const WeightParams& w, bool check_firs
 
 template <int FMA>
 hipError_t launch_fp(const KParams& p, const WeightParams& w, int n_cus, int waves_override, int gen_waves,
-                     bool check_first, hipStream_t s) {
+                     bool check_first, hipStream_t s, const RayList* rays) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
-    if (gen_waves >= 16)
+    if (rays && gen_waves >= 16)
+        hipLaunchKernelGGL((weights_raygen_rays_kernel<FMA, 16>), dim3((unsigned)((total_blocks + 15) / 16)),
+                           dim3(kWave * 16), 0, s, p, *rays);
+    else if (rays)
+        hipLaunchKernelGGL((weights_raygen_rays_kernel<FMA, 4>), dim3((unsigned)((total_blocks + 3) / 4)),
+                           dim3(kWave * 4), 0, s, p, *rays);
+    else if (gen_waves >= 16)
         hipLaunchKernelGGL((weights_raygen_kernel<FMA, 16>), dim3((unsigned)((total_blocks + 15) / 16)),
                            dim3(kWave * 16), 0, s, p);
     else
@@ -276,10 +297,10 @@ hipError_t launch_fp(const KParams& p, const WeightParams& w, int n_cus, int wav
 }  // namespace
 
 hipError_t launch_weights(const KParams& p, const WeightParams& w, int fp_mode, int n_cus, int waves_override,
-                          int gen_waves, bool check_first, hipStream_t stream) {
+                          int gen_waves, bool check_first, hipStream_t stream, const RayList* rays) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    return fp_mode == VR_FP_FMA ? launch_fp<1>(p, w, n_cus, waves_override, gen_waves, check_first, stream)
-                                : launch_fp<0>(p, w, n_cus, waves_override, gen_waves, check_first, stream);
+    return fp_mode == VR_FP_FMA ? launch_fp<1>(p, w, n_cus, waves_override, gen_waves, check_first, stream, rays)
+                                : launch_fp<0>(p, w, n_cus, waves_override, gen_waves, check_first, stream, rays);
 }
 
 }  // namespace vr
