@@ -261,3 +261,35 @@ def test_clone_device_bytes_and_colour_before_and_after(torch_cuda):
         for x in (t, c, c2):
             if x is not None:
                 x.free_device()
+
+
+def test_sample_guard_sets_the_status_bit(torch_cuda):
+    """The case of tests/test_gpu_grad.py::test_sample_guard_sets_the_status_bit (the weights march is the
+    backward's first march over the same rays): max_iter = 2 cuts every wave whose rays outlive its first pass
+    of march rounds.  The call returns and the bit is set; a cut ray contributes a prefix of its samples, so
+    no slot counts more hits or holds a larger weight than after the full march."""
+    torch = torch_cuda
+    from volrend_amd import api
+    tree = common.small_scene(depth=6, basis_dim=9, seed=941)
+    tr, w, h, f = common.camera_for(pose_idx=3, size=96)
+    cam = api.Camera(w, h, f, f)
+    want = ("max_weight", "hits")
+    t = api.N3Tree.from_synth(tree)
+    try:
+        full = t.accumulate_weights(cam, [tr], api.RenderOptions(), want=want)
+        torch.cuda.synchronize()
+        assert t.status() == 0 and bool((full["hits"] != 0).any())
+        t.set_tuning(max_iter=2)
+        try:
+            cut = t.accumulate_weights(cam, [tr], api.RenderOptions(), want=want)
+            torch.cuda.synchronize()
+            assert t.status() & 1, "rays were cut by the guard but the status word says nothing"
+            assert t.status(reset=True) & 1 and t.status() == 0
+        finally:
+            t.set_tuning(max_iter=1 << 22)
+        hits_full, hits_cut = (host(r["hits"]).view(np.uint32) for r in (full, cut))
+        mw_full, mw_cut = (host(r["max_weight"]) for r in (full, cut))
+        assert (hits_cut <= hits_full).all()
+        assert (mw_cut <= mw_full).all()
+    finally:
+        t.free_device()

@@ -388,7 +388,7 @@ __device__ __forceinline__ void grab_chunk(const KParams& p, int lane, uint32_t&
     }
 }
 
-// Ray generation's compaction (raygen_kernel, weights_raygen_kernel; GW = waves per workgroup, every
+// Ray generation's compaction (raygen_kernel, march_raygen_kernel; GW = waves per workgroup, every
 // lane of the workgroup calls): m_valid = the wave's lanes whose ray enters the volume.  Returns the ray
 // slot of the wave's first such lane; the others follow by lane_rank(m_valid).
 // Wave ballot + mbcnt prefix inside the wave, a scan over the workgroup's waves, and
@@ -434,7 +434,7 @@ __device__ __forceinline__ uint32_t reserve_ray_slots(const KParams& p, unsigned
 }
 
 // ---------------------------------------------------------------------------
-// Ray lists (vr_internal.h RayList): the front of the three *_raygen_rays_kernel.
+// Ray lists (vr_internal.h RayList): the front of raygen_rays_kernel and march_raygen_rays_kernel.
 // ---------------------------------------------------------------------------
 // The 12 march words every record starts with.
 __device__ __forceinline__ void store_march_words(uint32_t* rb, const Ray& nr) {

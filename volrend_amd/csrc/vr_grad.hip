@@ -3,11 +3,11 @@
 // (rt_core.cuh:66-196) to the density and the record entries of every leaf slot a hit sample fell into, and
 // the contributions are ADDED into grad_data, which is indexed as the file's data array is.
 //
-// The march is weights_kernel's (vr_weights.hip): ray generation, the point query, the step, the attenuation
-// and the stop test are the device functions the colour kernels use, so which samples exist, their leaves,
-// delta_t and where the ray stops have the bits trace_ray gives them in either FP model.  Those are constants
-// of the differentiation; only sigma and the record entries are variables (include/volrend_hip.h has the
-// formulas).  Built with -ffp-contract=off; see vr_device_math.h.
+// The march is weights_kernel's (vr_weights.hip): ray generation (vr_dev_march.h), the point
+// query, the step, the attenuation and the stop test are the device functions the colour kernels use, so
+// which samples exist, their leaves, delta_t and where the ray stops have the bits trace_ray gives them in
+// either FP model.  Those are constants of the differentiation; only sigma and the record entries are
+// variables (include/volrend_hip.h has the formulas).  Built with -ffp-contract=off; see vr_device_math.h.
 //
 // Two marches per ray.  The sigma contribution of sample i needs R_i = sum_{j > i} w_j G_j, a SUFFIX sum, and
 // the totals T_{K+1} and C^ = sum_j w_j G_j; a ray has any number of samples, so nothing per sample can be
@@ -35,18 +35,13 @@
 // LDS table of basis values written at refill.  SH16: 49 lanes cover 196 contiguous bytes; SH25: two
 // instructions of 64 + 11 elements; records shorter than half a wave (SH9: 28 floats, SH4: 13, RGBA and the
 // single-coefficient case: 4) pack 2 / 4 / 16 hits into one instruction, each lane group a run of its own.
-#include "vr_device_math.h"
-#include "vr_internal.h"
-#include "vr_dev_layout.h"
-#include "vr_dev_query.h"
-#include "vr_dev_rays.h"
+#include "vr_dev_march.h"
 #include "vr_dev_shade.h"
 
 namespace vr {
 
 namespace {
 
-enum { kGradQueryN2 = 0, kGradQueryN2Blocked = 1, kGradQueryGeneric = 2 };
 constexpr int kGradWaves = 4;  // per SIMD (profiles/render_backward_kernel_resources.txt)
 
 typedef __attribute__((address_space(1))) float vr_gfloat_t;
@@ -62,75 +57,19 @@ struct GradTraits {
 };
 
 // ---------------------------------------------------------------------------
-// grad_raygen_kernel: weights_raygen_kernel plus what the shading needs: the view direction and the
-// pixel's index into grad_accum.  kGradRayWords words per ray.
-// ---------------------------------------------------------------------------
-template <int FMA, int GW>
-__global__ __launch_bounds__(kWave* GW) void grad_raygen_kernel(const KParams p) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    const uint32_t id = (uint32_t)(((int64_t)blockIdx.x * GW + wave) * kWave + lane);
-    bool valid = false;
-    Ray nr;
-    nr.alive = false;
-    float vdir[3] = {0.f, 0.f, 0.f};
-    uint32_t pixel = 0;
-    if (id < p.total_rays) {
-        const PixelRef r = locate(p, id);
-        if (r.in_image) {
-            setup_ray<FMA>(p, r, nr, vdir);
-            valid = nr.alive;
-            // (< 2^30: launch_geometry)
-            pixel = ((uint32_t)r.frame * (uint32_t)p.height + (uint32_t)r.y) * (uint32_t)p.width + (uint32_t)r.x;
-        }
-    }
-    const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
-    const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
-    if (!valid) return;
-    const uint32_t slot = my_base + lane_rank(m_valid);
-    uint32_t* rb = ray_slot(p.ray_buf_rw, kGradRayWords, slot);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        ray_word(rb, kRayCen + i) = f2u(nr.cen[i]);
-        ray_word(rb, kRayDir + i) = f2u(nr.dir[i]);
-        ray_word(rb, kRayInvDir + i) = f2u(nr.invdir[i]);
-        ray_word(rb, kGradRayVdir + i) = f2u(vdir[i]);
-    }
-    ray_word(rb, kRayT) = f2u(nr.t);
-    ray_word(rb, kRayTmax) = f2u(nr.tmax);
-    ray_word(rb, kRayDeltaScale) = f2u(nr.delta_scale);
-    ray_word(rb, kGradRayPixel) = pixel;
-}
-
-// grad_raygen_rays_kernel: the same for a ray list (vr_render_backward_rays): the ray is list_ray()'s, and its
-// row of grad_accum is its index in the list.
-template <int FMA, int GW>
-__global__ __launch_bounds__(kWave* GW) void grad_raygen_rays_kernel(const KParams p, const RayList rl) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = threadIdx.x >> 6;
-    uint32_t id;
-    Ray nr;
-    float vdir[3] = {0.f, 0.f, 0.f};
-    const bool valid = list_ray<FMA, GW>(p, rl, lane, wave, id, nr, vdir) && nr.alive;
-    const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
-    const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
-    if (!valid) return;
-    uint32_t* rb = ray_slot(p.ray_buf_rw, kGradRayWords, my_base + lane_rank(m_valid));
-    store_march_words(rb, nr);
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ray_word(rb, kGradRayVdir + i) = f2u(vdir[i]);
-    ray_word(rb, kGradRayPixel) = id;
-}
-
-// ---------------------------------------------------------------------------
 // grad_kernel: the persistent march (weights_kernel's frame: one wave per workgroup, chunks of ray ids,
 // batched refill, the sample guard), two phases per ray and the wave-wide scatter described at the top.
+// The frame is WRITTEN OUT here and not taken from vr_dev_march.h, which states the same steps for
+// weights_kernel: over march_refill / sample_guard / march_sample this kernel held two more VGPRs and ran
+// 0.2-0.4 % slower (EXPERIMENTS.md "One march frame").  A change to the refill rule, the guard or the queue
+// protocol there is made here too.  Rays are GradRecord records: the view direction and the pixel's index
+// into grad_accum follow the march words.
 // ---------------------------------------------------------------------------
 template <int FMA, int QUERY, int BASIS>
 __global__ __launch_bounds__(kWave, kGradWaves) void grad_kernel(const KParams p, const GradParams gp) {
     using P = Policy<FMA>;
     using GT = GradTraits<BASIS>;
-    constexpr bool N2 = QUERY != kGradQueryGeneric;
+    constexpr bool N2 = QUERY != kQueryGeneric;
     __shared__ float s_basis[GT::kBasisRows * kWave];  // [b][lane]: basis value b of the lane's ray
     __shared__ uint32_t s_slot[kWave];                 // the hits of this round, compacted
     __shared__ float s_f[4][kWave];                    // channel factors 0..2, the sigma term
@@ -283,7 +222,7 @@ __global__ __launch_bounds__(kWave, kGradWaves) void grad_kernel(const KParams p
                 float cube_sz = 0.f;
                 int levels;
                 uint32_t word, leaf;
-                if (N2) leaf = query_n2<false, (QUERY == kGradQueryN2Blocked ? 1 : 0)>(p, pos, &levels, &word, cur);
+                if (N2) leaf = query_n2<false, (QUERY == kQueryN2Blocked ? 1 : 0)>(p, pos, &levels, &word, cur);
                 else leaf = (uint32_t)query_generic<FMA, false>(p, pos, &cube_sz, &levels, &word);
                 const float dda = dda_unit<FMA>(pos, invdir);
                 const float t_subcube = N2 ? __builtin_amdgcn_ldexpf(dda, -levels) : dda / cube_sz;
@@ -434,22 +373,12 @@ template <int FMA>
 hipError_t launch_fp(const KParams& p, const GradParams& gp, int n_cus, int waves_override, int gen_waves,
                      hipStream_t s, const RayList* rays) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
-    if (rays && gen_waves >= 16)
-        hipLaunchKernelGGL((grad_raygen_rays_kernel<FMA, 16>), dim3((unsigned)((total_blocks + 15) / 16)),
-                           dim3(kWave * 16), 0, s, p, *rays);
-    else if (rays)
-        hipLaunchKernelGGL((grad_raygen_rays_kernel<FMA, 4>), dim3((unsigned)((total_blocks + 3) / 4)),
-                           dim3(kWave * 4), 0, s, p, *rays);
-    else if (gen_waves >= 16)
-        hipLaunchKernelGGL((grad_raygen_kernel<FMA, 16>), dim3((unsigned)((total_blocks + 15) / 16)),
-                           dim3(kWave * 16), 0, s, p);
-    else
-        hipLaunchKernelGGL((grad_raygen_kernel<FMA, 4>), dim3((unsigned)((total_blocks + 3) / 4)),
-                           dim3(kWave * 4), 0, s, p);
+    launch_march_raygen<FMA, GradRecord>(p, gen_waves, s, rays);
     const dim3 grid(persistent_grid(total_blocks, n_cus, waves_override > 0 ? waves_override : 4 * kGradWaves));
-    if (!uses_lookup(p)) launch_march_basis<FMA, kGradQueryGeneric>(p, gp, grid, s);
-    else if (p.brick_blocked) launch_march_basis<FMA, kGradQueryN2Blocked>(p, gp, grid, s);
-    else launch_march_basis<FMA, kGradQueryN2>(p, gp, grid, s);
+    const int query = query_kind(p);
+    if (query == kQueryGeneric) launch_march_basis<FMA, kQueryGeneric>(p, gp, grid, s);
+    else if (query == kQueryN2Blocked) launch_march_basis<FMA, kQueryN2Blocked>(p, gp, grid, s);
+    else launch_march_basis<FMA, kQueryN2>(p, gp, grid, s);
     return hipGetLastError();
 }
 

@@ -240,7 +240,7 @@ struct WeightParams {
 // ---------------------------------------------------------------------------
 // Ray lists (vr_render_rays, vr_accumulate_weights_rays, vr_render_backward_rays): the rays of a launch come
 // from two caller arrays and not from locate() and a pose.  Only ray generation differs -- the kernels
-// raygen_rays_kernel, weights_raygen_rays_kernel and grad_raygen_rays_kernel take KParams unchanged plus this
+// raygen_rays_kernel (vr_render.hip) and march_raygen_rays_kernel (vr_dev_march.h) take KParams unchanged plus this
 // second argument and write the records of their frame siblings into the same queues; the march kernels are
 // the frame launches'.  To them a list is ONE offscreen pseudo-frame kRayListWidth pixels wide whose pixel
 // y * width + x is ray i: x = i & (kRayListWidth - 1), y = i >> kRayListShift (both below 2^15: i < 2^30),

@@ -540,11 +540,11 @@ int ensure_file_nodes(VrTreeOpaque* t) {
 
 // What a leaf-weight launch and a backward launch share once their arguments are checked: the file-order
 // table, an offscreen frame without mesh depth, probe, depth mode or view-direction rotation, a slot for rays
-// of `ray_words` words, the pose table (cams = NULL, a ray list: the pseudo-frame), and then
-// launch(k, tuning, stream).
+// of `ray_words` words, the pose table (cams = NULL, a ray list: `rays`, the pseudo-frame), and then
+// launch(k, tuning, waves per ray-generation workgroup, stream).
 template <typename Launch>
-int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, vr::KParams& k,
-                 int ray_words, void* stream, Launch&& launch) {
+int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const vr::RayList* rays, const VrRenderOptions* opt,
+                 vr::KParams& k, int ray_words, void* stream, Launch&& launch) {
     DeviceGuard device_guard(t->device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
     std::unique_lock<std::mutex> guard(t->launch_mutex);
@@ -562,7 +562,7 @@ int march_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRender
     SlotTurn turn;
     if (int rc = turn.begin(t->slots[slot], hs)) return rc;
     if (int rc = cams ? enqueue_tables(k, cams, hs) : enqueue_list_table(k, nullptr, nullptr, hs)) return rc;
-    HIP_TRY(launch(k, tn, hs));
+    HIP_TRY(launch(k, tn, rays ? raygen_waves_list(tn, rays->n) : raygen_waves(tn, n_frames), hs));
     return VR_OK;  // (`turn` records the slot's event)
 }
 
@@ -586,13 +586,12 @@ int validate_rays(const char* what, vr_tree_t t, int64_t n, const VrRays* rays, 
 // empty list): `k` holds the checked geometry.
 int accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const vr::RayList* rays,
                        const VrRenderOptions* opt, int fp_mode, const VrLeafWeights* out, vr::KParams& k, void* stream) {
-    return march_launch(t, n_frames, cams, opt, k, vr::kWeightRayWords, stream,
-                        [&](const vr::KParams& kp, const Tuning& tn, hipStream_t hs) {
+    return march_launch(t, n_frames, cams, rays, opt, k, vr::kWeightRayWords, stream,
+                        [&](const vr::KParams& kp, const Tuning& tn, int gen, hipStream_t hs) {
                             vr::WeightParams w;
                             w.max_weight = reinterpret_cast<uint32_t*>(out->max_weight);
                             w.hits = out->hits;
                             w.file_node = t->file_node_dev.get<int32_t>();
-                            const int gen = rays ? raygen_waves_list(tn, rays->n) : raygen_waves(tn, n_frames);
                             return vr::launch_weights(kp, w, fp_mode, t->n_cus, tn.waves_per_cu, gen,
                                                       tn.weights_check != 0, hs, rays);
                         });
@@ -637,13 +636,12 @@ int render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const vr::R
                     const VrRenderOptions* opt, int fp_mode, const float* grad_accum, float* grad_data,
                     vr::KParams& k, void* stream) {
     if (int rc = check_backward_tree(t, opt, rays ? "vr_render_backward_rays" : "vr_render_backward")) return rc;
-    return march_launch(t, n_frames, cams, opt, k, vr::kGradRayWords, stream,
-                        [&](const vr::KParams& kp, const Tuning& tn, hipStream_t hs) {
+    return march_launch(t, n_frames, cams, rays, opt, k, vr::kGradRayWords, stream,
+                        [&](const vr::KParams& kp, const Tuning& tn, int gen, hipStream_t hs) {
                             vr::GradParams g;
                             g.grad_accum = grad_accum;
                             g.grad_data = grad_data;
                             g.file_node = t->file_node_dev.get<int32_t>();
-                            const int gen = rays ? raygen_waves_list(tn, rays->n) : raygen_waves(tn, n_frames);
                             return vr::launch_grad(kp, g, fp_mode, t->n_cus, tn.waves_per_cu, gen, hs, rays);
                         });
 }
