@@ -206,7 +206,8 @@ def test_product_sources_carry_no_experiment_hooks_and_the_patch_applies(tmp_pat
     csrc = os.path.join(ROOT, "volrend_amd", "csrc")
     for f in ("vr_render.hip", "vr_tree_kernels.hip", "vr_dev_layout.h", "vr_dev_shade.h", "vr_dev_query.h",
               "vr_dev_rays.h", "vr_api.cpp", "vr_internal.h", "vr_device_math.h", "vr_host.h", "vr_upload.cpp",
-              "vr_launch.cpp", "vr_tree_walk.h", "vr_tree_walk.cpp", "vr_h2d.h", "vr_h2d.cpp"):
+              "vr_launch.cpp", "vr_launch_plan.h", "vr_launch_plan.cpp", "vr_slots.cpp", "vr_values.cpp",
+              "vr_tree_walk.h", "vr_tree_walk.cpp", "vr_h2d.h", "vr_h2d.cpp"):
         text = open(os.path.join(csrc, f)).read()
         assert not re.search(r"VR_EXP_|\bTL3?_[A-Z]|VR_ABLATE|VR_TIMELINE|vr_experiment_hooks", text), f
     assert not os.path.exists(os.path.join(csrc, "vr_experiment_hooks.h"))

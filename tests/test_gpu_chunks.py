@@ -1,7 +1,7 @@
 """-m gpu: the ray hand-out of render_kernel / render_aov_kernel is scheduling only.
 
 A wave takes its rays from the queue of its XCD in guided chunks of at most `chunk_max` rays (tuning key;
-0 = the host's rule for the kind of launch, vr_launch.cpp auto_chunk_max) and refills its idle lanes from the
+0 = the host's rule for the kind of launch, vr_launch_plan.cpp plan_launch) and refills its idle lanes from the
 chunk in hand.  Whatever the cap, the refill threshold, the number of waves and of queues: every frame of a
 batch equals the oracle byte for byte, the status word stays 0, the AOV planes equal those of the
 chunk_max=4096 launch, launches whose queues hold less than a chunk -- or nothing -- end, and the sample

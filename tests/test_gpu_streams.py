@@ -1,4 +1,4 @@
-"""-m gpu: launches in flight on several streams (the launch-slot ring of vr_launch.cpp).
+"""-m gpu: launches in flight on several streams (the launch-slot ring of vr_slots.cpp).
 
 Every launch carries per-launch scratch in device memory; a slot is reused only behind the
 event of the launch that held it last.  3 streams x 6 launches (> 8 slots, different poses and

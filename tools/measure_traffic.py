@@ -61,7 +61,8 @@ SOURCES = ["volrend_amd/csrc/vr_render.hip", "volrend_amd/csrc/vr_dev_layout.h",
            "volrend_amd/csrc/vr_dev_query.h", "volrend_amd/csrc/vr_dev_rays.h", "volrend_amd/csrc/vr_device_math.h",
            "volrend_amd/csrc/vr_internal.h", "volrend_amd/csrc/vr_api.cpp", "include/volrend_hip.h",
            "volrend_amd/csrc/vr_host.h", "volrend_amd/csrc/vr_upload.cpp", "volrend_amd/csrc/vr_launch.cpp",
-           "include/volrend/internal/hip_owners.hpp"]
+           "volrend_amd/csrc/vr_launch_plan.h", "volrend_amd/csrc/vr_launch_plan.cpp", "volrend_amd/csrc/vr_slots.cpp",
+           "volrend_amd/csrc/vr_values.cpp", "include/volrend/internal/hip_owners.hpp"]
 
 
 def kernel_source_hash() -> str:

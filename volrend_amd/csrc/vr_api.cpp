@@ -1,7 +1,8 @@
 // vr_api.cpp -- the C ABI of libvolrend_hip.so (include/volrend_hip.h), host side: version, errors,
-// devices, defaults, tuning, statistics and touch bitmaps, tile assembly, probe, read-back.
+// devices, defaults, tuning, statistics, status and touch bitmaps, tile assembly, probe, read-back.
 // Upload, clone and free are in vr_upload.cpp (its host walks in vr_tree_walk.cpp, its copy pipeline in
-// vr_h2d.cpp), launches in vr_launch.cpp.
+// vr_h2d.cpp), launches in vr_launch.cpp (their scheduling rules in vr_launch_plan.cpp, the launch-slot ring and
+// vr_reserve* in vr_slots.cpp), the value passes in vr_values.cpp.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -211,6 +212,29 @@ int vr_sched_stats(vr_tree_t t, uint64_t out[vr::kSchedStats], int reset) {
     DeviceGuard guard(t->device);
     HIP_TRY(hipMemcpy(out, t->sched_stats.get(), vr::kSchedStats * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (reset) HIP_TRY(hipMemset(t->sched_stats.get(), 0, vr::kSchedStats * sizeof(uint64_t)));
+    return VR_OK;
+}
+
+int vr_tree_status(vr_tree_t t, uint32_t* status, int reset) {
+    if (!t || !status) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard guard(t->device);
+    HIP_TRY(hipMemcpy(status, t->status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(t->status.get(), 0, sizeof(uint32_t)));
+    return VR_OK;
+}
+
+int vr_tree_status_on(vr_tree_t t, uint32_t* status, int reset, void* stream) {
+    if (!t || !status) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard guard(t->device);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    // a pinned word per calling thread: the copy is asynchronous and ordered on `hs` alone.
+    // Portable: the thread may read the status of trees on several devices through it.
+    thread_local uint32_t* pinned = nullptr;
+    if (!pinned) HIP_TRY(hipHostMalloc((void**)&pinned, sizeof(uint32_t), hipHostMallocPortable));
+    HIP_TRY(hipMemcpyAsync(pinned, t->status.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, hs));
+    if (reset) HIP_TRY(hipMemsetAsync(t->status.get(), 0, sizeof(uint32_t), hs));
+    HIP_TRY(hipStreamSynchronize(hs));
+    *status = *pinned;
     return VR_OK;
 }
 

@@ -1,7 +1,8 @@
-// vr_host.h -- shared by the host sources of libvolrend_hip.so (vr_api.cpp, vr_upload.cpp,
-// vr_launch.cpp, vr_query.cpp).  Host only (not for the .hip units); nothing here is exported from the
-// library.  Two host units stand beside it with headers of their own: vr_tree_walk.{h,cpp} (the walks
-// of an upload over the child array; no HIP) and vr_h2d.{h,cpp} (the upload's staged copy pipeline).
+// vr_host.h -- shared by the host sources of libvolrend_hip.so (vr_api.cpp, vr_upload.cpp, vr_launch.cpp,
+// vr_slots.cpp, vr_values.cpp, vr_query.cpp).  Host only (not for the .hip units); nothing here is exported
+// from the library.  Three host units stand beside it with headers of their own: vr_tree_walk.{h,cpp} (the walks
+// of an upload over the child array; no HIP), vr_launch_plan.{h,cpp} (struct Tuning and the scheduling rules of a
+// launch; no HIP) and vr_h2d.{h,cpp} (the upload's staged copy pipeline).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 #include <vector>
 
 #include "vr_internal.h"
+#include "vr_launch_plan.h"  // struct Tuning, and the scheduling rules of a launch
 
 #pragma GCC visibility push(hidden)
 
@@ -33,33 +35,6 @@ inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? VR_ERR_OUT
                         __LINE__);                                                                    \
     } while (0)
 
-// Scheduling / layout knobs.  They never change results.  Every tree carries its OWN copy
-// (vr_tree_set_tuning), taken at upload from the process defaults; the defaults come from
-// the environment (VR_MARCH_MAX, VR_REFILL_MIN, VR_WAVES_PER_CU, ... read once) and
-// vr_set_tuning, which only affects trees uploaded afterwards.  vr_api.cpp keeps the table of
-// keys, variables and clamps.
-struct Tuning {
-    int march_max = 12;
-    int refill_min = 20;
-    int drain_flush = 16;  // drain phase: partial round for a blocked ray when <= this many lanes march (0 = off;
-                           // measured 4..64, profiles/r05_experiments.jsonl: one frame per launch -13 %, two / four -5 %)
-    int waves_per_cu = 0;   // 0: what the kernel flavour fits (vr_render.hip waves_per_cu<>)
-    int frame_group = 0;   // poses per ray-order group (0 = all poses of the launch, 1 = frame-major)
-    int super_block = 0;   // 8x8 blocks per super-block edge in the ray order (1 = row-major); 0 = auto: by the kind and
-                           // size of the launch (auto_super_block, vr_launch.cpp)
-    int records_nt = -1;   // record stream non-temporal: -1 = by lookup-structure size, 0 / 1 = forced
-    int xcd_queues = 1;
-    int chunk_max = 0;     // cap of the guided chunk a wave takes from its queue at once (multiple of 64); 0 = auto:
-                           // by the kind of launch (auto_chunk_max, vr_launch.cpp)
-    int raygen_waves = 0;  // waves per ray-generation workgroup: 16 / 4 / 1; 0 = by launch size (vr_render_batch)
-    int top_levels = 0;    // lookup structure built at upload (vr_dev_layout.h); 0 = auto
-    int brick_levels = 3;
-    int brick_blocked = -1;  // 8^3 bricks in 4 x 4 x 2 line blocks: -1 = when the lookup structure exceeds 128 MB, 0 / 1 = forced
-    int max_iter = 1 << 22;  // the sample guard (vr_render.hip); the one knob that is NOT scheduling-only:
-                             // a launch that trips it reports through vr_tree_status (tests lower it)
-    int weights_check = 1;   // vr_accumulate_weights: read max_weight[slot] first and issue the atomic max only
-                             // for a larger weight (0: one atomic per positive weight; vr_weights.hip, EXPERIMENTS.md)
-};
 Tuning default_tuning();  // the process defaults, for a tree being uploaded
 
 constexpr unsigned kLaunchSlots = 8;
@@ -122,5 +97,42 @@ void fill_tree_params(vr::KParams& k, const VrTreeOpaque* t);  // the tree's par
 int tile_geometry(int width, int height, int tile_w, int tile_h, int rank, int world, vr::KParams& k);
 int launch_geometry(int width, int height, int tile_w, int tile_h, int rank, int world, int n_frames,
                     vr::KParams& k);
+// launch_geometry for a list of n rays (vr::RayList): the one pseudo-frame of vr::kRayListWidth pixels a row
+// whose pixel y * width + x is ray i, as whole blocks of 64 rays.  `what` names the function in the refusal.
+int list_geometry(const char* what, int64_t n, vr::KParams& k);
+
+// What a launch needs of its slot's ray buffer: the records, and behind them the pixel words the march stores
+// for a vr_render_rays without an rgba array.
+inline size_t ray_buffer_bytes(uint32_t total_rays, int words_per_ray) {
+    return vr::ray_slots(total_rays) * (size_t)words_per_ray * sizeof(uint32_t);
+}
+inline size_t list_pixel_bytes(uint32_t total_rays) { return (size_t)total_rays * 4; }
+
+// Launch slot: per-launch scratch in device memory (ring, see LaunchSlot).  Picks the slot of this
+// launch, points `k` at its scratch and makes its ray buffer large enough (`need` bytes).  `guard` holds the
+// launch mutex on entry and on return, and is dropped in between while a slot grows.  (vr_slots.cpp)
+int acquire_slot(VrTreeOpaque* t, std::unique_lock<std::mutex>& guard, hipStream_t hs, vr::KParams& k,
+                 size_t need, unsigned& slot);
+
+// A launch's turn at its slot; begin() is the only way to take one.  Whoever used the slot last (any stream)
+// must have finished before its scratch is rewritten: begin() makes the stream wait for it (a failed wait
+// leaves the slot as it was).  From then on kernels of the launch may be in the stream: whatever happens
+// afterwards (a later enqueue failing), the slot's event is recorded behind them and the slot is marked used,
+// so that the next user of the slot -- any stream -- waits for whatever did get enqueued.
+class SlotTurn {
+    LaunchSlot* slot_ = nullptr;
+    hipStream_t stream_ = nullptr;
+public:
+    int begin(LaunchSlot& ls, hipStream_t hs);
+    ~SlotTurn();
+};
+
+// The device copy `dev` of a host table of the tree (`entries` words; `name` for the messages), made on the
+// first call that needs it -- under the launch mutex, that call's one host-blocking step -- and then counted in
+// device_bytes.  ensure_file_nodes: the device-node -> file-node table of the leaf-weight, backward and value
+// calls.  (vr_values.cpp)
+int ensure_device_table(VrTreeOpaque* t, DeviceBuffer& dev, const std::vector<int32_t>& host, size_t entries,
+                        const char* name);
+int ensure_file_nodes(VrTreeOpaque* t);
 
 #pragma GCC visibility pop

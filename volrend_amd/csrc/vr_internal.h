@@ -1,4 +1,4 @@
-// vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp, vr_upload.cpp, vr_launch.cpp) and
+// vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp, vr_upload.cpp, vr_launch.cpp, vr_slots.cpp, vr_values.cpp) and
 // the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_grad.hip, vr_update.hip, vr_tree_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,57 @@
+// vr_launch_plan.cpp -- the scheduling rules of a march launch (vr_launch_plan.h).  Standard C++ only.
+#include "vr_launch_plan.h"
+
+namespace {
+
+// The knobs that are "auto" (0) by default, resolved for one launch.  `colour`: a colour or AOV launch
+// (render_kernel / render_aov_kernel); the leaf-weight and backward launches keep the values they were
+// measured with (guided chunks of up to 4096 rays, row-major block order).
+//   * chunk_max: the cap of a wave's guided chunk (grab_chunk, vr_dev_rays.h).  256 for colour launches of
+//     any shape: four block-poses.  With 4096 one wave marched an 8x8 pixel block through all the poses of a
+//     64-frame launch, one after the other, and the lines it fetched for pose k were long evicted from its
+//     XCD's L2 at pose k + 1; with 256 the poses of a block go to 16 waves of the XCD at about the same time
+//     (fabric reads per C1 frame -7 %).  Below 256 the reads fall further (-24 % at 64) and the time RISES:
+//     a wave whose lanes hold unrelated blocks loses more in its own L1 than the L2 gains -- also with
+//     grabs that cost the wave no latency (EXPERIMENTS.md, round 7).  Small launches never reach the cap:
+//     the guided size of a one-frame launch is 64.
+//   * super_block: 4 (blocks visited in 4 x 4 super-blocks: consecutive chunks are screen neighbours in
+//     both directions) for launches of three frames and more, row-major for the small ones, which it
+//     costs 2 % (measured at one frame; four frames: no difference).
+// A colour launch of a ray list takes the colour rule's 256; super_block orders the blocks of a SCREEN and is
+// never consulted for a list (its ray generation does not call locate()).
+constexpr int kColourChunkCap = 256, kGuidedChunkCap = 4096;
+
+// waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
+// two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
+// 4 waves find room there much earlier (vr_render.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
+// two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
+// 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
+int raygen_waves(const Tuning& tn, int n_frames) {
+    return tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
+}
+// A ray list: the same reasoning by ray count.  The frame rule was measured at 800 x 800 pixels, where "two
+// frames" are 1 280 000 rays: lists up to kRayListSmall rays -- an optimiser's step, which runs beside the tail
+// of the step before it -- generate in workgroups of 4 waves, larger ones in 16.  UNMEASURED for lists: the
+// boundary is the frame rule's, restated in rays.  (List ray generation has no one-wave flavour.)
+constexpr int64_t kRayListSmall = 2 * 800 * 800;
+int raygen_waves_list(const Tuning& tn, int64_t n) {
+    return tn.raygen_waves > 0 ? (tn.raygen_waves >= 16 ? 16 : 4) : (n <= kRayListSmall ? 4 : 16);
+}
+
+}  // namespace
+
+LaunchPlan plan_launch(LaunchKind kind, RaySource source, int n_frames, int64_t list_rays, const Tuning& tn,
+                       uint64_t lookup_bytes) {
+    const bool colour = kind == LaunchKind::kColour || kind == LaunchKind::kAov;
+    const bool list = source == RaySource::kList;
+    LaunchPlan p;
+    p.chunk_max = tn.chunk_max > 0 ? tn.chunk_max : colour ? kColourChunkCap : kGuidedChunkCap;
+    p.super_block = tn.super_block > 0 ? tn.super_block : (colour && !list && n_frames > 2) ? 4 : 1;
+    p.raygen_waves = list ? raygen_waves_list(tn, list_rays) : raygen_waves(tn, n_frames);
+    // lookup structure (top + bricks) beyond 4x the aggregate L2 (8 x 4 MiB on MI355X): the record
+    // stream would keep evicting it -- see the DMA loads in vr_render.hip
+    p.records_nt = tn.records_nt >= 0 ? tn.records_nt : lookup_bytes > (128ull << 20);
+    p.frame_group = tn.frame_group < 1 || tn.frame_group > n_frames ? n_frames : tn.frame_group;
+    p.n_queues = tn.xcd_queues ? kPlanQueues : 1;
+    return p;
+}
