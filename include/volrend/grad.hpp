@@ -5,6 +5,7 @@
 // Asynchronous like launch_renderer: returns after enqueueing on `stream` (a hipStream_t passed as void*);
 // throws std::runtime_error ("vr_render_backward: ...") where the C call refuses its arguments.
 #pragma once
+#include <cstdint>
 #include <vector>
 
 #include "volrend/renderer_kernel.hpp"
@@ -23,5 +24,13 @@ namespace volrend {
 void render_backward(const N3Tree& tree, const Camera& cam, const std::vector<const float*>& transforms,
                      const RenderOptions& options, const float* grad_accum, float* grad_data, void* stream,
                      int fp_mode = VR_FP_STRICT);
+
+// The same, and the slots the call adds into are marked in `touched` (vr_render_backward_touched): device,
+// ceil(capacity * N^3 / 32) words, one bit per child slot in grad_data's slot order (bit s & 31 of word s >> 5);
+// ORed into, zeroed once by the caller.  The set of marked slots is bit-reproducible.  What tree_step (step.hpp)
+// consumes.
+void render_backward(const N3Tree& tree, const Camera& cam, const std::vector<const float*>& transforms,
+                     const RenderOptions& options, const float* grad_accum, float* grad_data, uint32_t* touched,
+                     void* stream, int fp_mode = VR_FP_STRICT);
 
 }  // namespace volrend

@@ -36,6 +36,11 @@ void accumulate_weights_rays(const N3Tree& tree, const Rays& rays, const RenderO
 void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
                           const float* grad_accum, float* grad_data, void* stream, int fp_mode = VR_FP_STRICT);
 
+// The same, marking the slots it adds into in `touched` (grad.hpp; vr_render_backward_rays_touched).
+void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
+                          const float* grad_accum, float* grad_data, uint32_t* touched, void* stream,
+                          int fp_mode = VR_FP_STRICT);
+
 // Sizes n_slots launch slots so that no later ray call of <= n rays on them allocates (vr_reserve_rays).
 void reserve_rays(const N3Tree& tree, int64_t n, int n_slots = 2);
 

@@ -270,6 +270,53 @@ int vr_tree_info(vr_tree_t tree, VrTreeInfo* info);
 enum { VR_DATA_F16 = 0, VR_DATA_F32 = 1 };
 int vr_tree_update_data(vr_tree_t tree, const void* data_dev, int dtype, void* stream);
 int vr_tree_read_data(vr_tree_t tree, void* data_dev, int dtype, void* stream);
+/* ---- A sparse optimiser step, written into the tree in place ---- */
+/* The step of an optimiser loop over ONLY the leaf slots a batch of rays hit: vr_render_rays -> (the caller's
+ * loss) -> vr_render_backward_rays_touched -> vr_tree_step.  Its cost follows the rays and the slots they hit,
+ * not the size of the tree: no dense gradient is zeroed, no dense optimiser pass runs, and the tree is not
+ * rewritten whole (vr_tree_update_data).  All five arrays are device memory on the tree's device, indexed as
+ * VrTreeDesc.data and grad_data are; `touched` is the bitmap the marked backward calls OR into: one bit per child
+ * slot s = file node * N^3 + child slot, bit s & 31 of word s >> 5, ceil(capacity * N^3 / 32) words.
+ * For every set bit s < capacity * N^3 and every e in [0, data_dim), with i = s * data_dim + e, g = grad[i],
+ * lr_e = (e == data_dim - 1) ? lr_sigma : lr, in binary32 with one rounding per operator (no contraction, IEEE
+ * divide and square root):
+ *   VR_STEP_SGD   w = master[i] - lr_e * g
+ *   VR_STEP_ADAM  m' = beta1 * m[i] + omb1 * g,  v' = beta2 * v[i] + (omb2 * g) * g,
+ *                 w = master[i] - a_e * (m' / (sqrtf(v') / sbc2 + eps))
+ *                 omb1 = 1 - beta1, omb2 = 1 - beta2, sbc2 = sqrt(1 - beta2^step), a_e = lr_e / (1 - beta1^step):
+ *                 four scalars the host forms in binary64 and rounds once to binary32.  The moments of slots
+ *                 whose bit is clear do not move (sparse-Adam semantics).
+ * then master[i] = w (m[i] = m', v[i] = v'), grad[i] = +0, and the tree takes w rounded to binary16 to nearest
+ * even -- the rounding of vr_tree_update_data(VR_DATA_F32): coefficient entries into the padded record of the
+ * slot (the padding stays zero), the sigma entry into the slot's node word when the slot is a leaf; the sigma of
+ * an internal slot is ignored and its coefficients are stored, as the dense update does.  Bits at or beyond
+ * capacity * N^3 in the last word are ignored.  On completion every word of `touched` is 0.  Elements of slots
+ * whose bit is clear are neither read nor written, in any of the five arrays or in the tree.
+ * For a tree with a lookup structure the sigma fields of top grid and bricks are refreshed WHOLE behind the
+ * values kernel (as vr_tree_update_data does), so every device array of the tree is, bit for bit, what
+ * vr_tree_upload of the same child array would build from a data array that is binary16(master) in touched
+ * slots and the old values elsewhere: in both query modes, both brick orders, for quantised uploads and clones.
+ * Contract: that of vr_tree_update_data -- enqueue only on `stream`, on the tree's device whatever the thread's
+ * device, no launch slot; it WRITES the tree: later work on the same stream sees it, other streams are the
+ * caller's to order.  The first call puts three tables on the device under the tree's mutex (then counted in
+ * VrTreeInfo.device_bytes): a 4-bytes-per-node table file node -> device node, the file-order table and the
+ * brick-root table.
+ * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed or any device call: NULL tree / s / master / grad /
+ * touched, unknown kind, VR_STEP_ADAM with NULL m or v, with step < 1 or with a beta outside [0, 1), non-finite
+ * lr, lr_sigma or eps.  Nothing is VR_ERR_UNSUPPORTED. */
+enum { VR_STEP_SGD = 0, VR_STEP_ADAM = 1 };
+typedef struct VrStep {
+    float*    master;    /* [capacity*N^3*data_dim] float32, file order: the values the tree's binary16 are rounded from */
+    float*    grad;      /* same shape: read, then set to +0 in every touched slot */
+    uint32_t* touched;   /* the bitmap of the marked backward calls: read, then cleared */
+    float*    m;         /* Adam moments, same shape; NULL for SGD */
+    float*    v;
+    int32_t   kind;      /* VR_STEP_SGD / VR_STEP_ADAM */
+    float     lr, lr_sigma;  /* coefficient entries / the sigma entry of a record */
+    float     beta1, beta2, eps;
+    int32_t   step;      /* Adam: 1, 2, ... for the bias correction */
+} VrStep;
+int vr_tree_step(vr_tree_t tree, const VrStep* s, void* stream);
 
 /* ---- render ----------------------------------------------------------- */
 void vr_default_options(VrRenderOptions* opt);
@@ -437,6 +484,20 @@ int vr_accumulate_weights_rays(vr_tree_t tree, int64_t n, const VrRays* rays, co
  * and the refusals (render_depth, enable_probe, rot_dirs, a narrowed basis_minmax, SG / ASG trees) are its. */
 int vr_render_backward_rays(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
                             int fp_mode, const float* grad_accum, float* grad_data, void* stream);
+/* vr_render_backward / vr_render_backward_rays that ALSO mark the slots they add into.  `touched`: device, one
+ * bit per child slot in the indexing of VrTreeDesc.child, grad_data / data_dim and VrLeafWeights (s = file node *
+ * N^3 + child slot; bit s & 31 of word s >> 5; ceil(capacity * N^3 / 32) words).  The call ORs into it; the
+ * caller zeroes it once.  A bit is set exactly for every slot that receives a hit sample's contributions, i.e.
+ * whose run of grad_data the call adds into: a set that does not depend on any order, so the bitmap IS
+ * bit-reproducible although grad_data is not.  Everything else -- contract, launch slot, refusals, the n == 0
+ * behaviour, the formulas -- is that of the unmarked sibling; NULL touched is VR_ERR_INVALID_ARGUMENT, refused
+ * before the tree handle is followed.  What vr_tree_step consumes. */
+int vr_render_backward_touched(vr_tree_t tree, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                               int fp_mode, const float* grad_accum, float* grad_data, uint32_t* touched,
+                               void* stream);
+int vr_render_backward_rays_touched(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
+                                    int fp_mode, const float* grad_accum, float* grad_data, uint32_t* touched,
+                                    void* stream);
 /* Sizes n_slots (1..8) launch slots so that no later ray call of <= n rays on them allocates or blocks (the
  * colour record plus the scratch of a call without rgba: 80-232 bytes per ray).  Optional; synchronous. */
 int vr_reserve_rays(vr_tree_t tree, int64_t n, int n_slots);

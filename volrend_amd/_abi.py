@@ -25,6 +25,8 @@ SPACES = {"world": SPACE_WORLD, "tree": SPACE_TREE}
 DEPTH_TREE, DEPTH_WORLD = 0, 1  # vr_render_aov depth_units
 DEPTH_UNITS = {"tree": DEPTH_TREE, "world": DEPTH_WORLD}
 DATA_F16, DATA_F32 = 0, 1  # vr_tree_update_data / vr_tree_read_data dtype
+STEP_SGD, STEP_ADAM = 0, 1  # VrStep.kind
+STEP_KINDS = {"sgd": STEP_SGD, "adam": STEP_ADAM}
 MAX_BASIS = 25
 
 
@@ -87,6 +89,12 @@ class VrRayOut(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("accum", C.c_void_p)]
 
 
+class VrStep(C.Structure):
+    _fields_ = [("master", C.c_void_p), ("grad", C.c_void_p), ("touched", C.c_void_p), ("m", C.c_void_p),
+                ("v", C.c_void_p), ("kind", C.c_int32), ("lr", C.c_float), ("lr_sigma", C.c_float),
+                ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int32)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -130,6 +138,11 @@ PROTOTYPES = {
                                         C.c_int, C.POINTER(VrLeafWeights), C.c_void_p]),
     "vr_render_backward": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
                                      C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vr_render_backward_touched": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VrCamera), C.POINTER(VrRenderOptions),
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vr_render_backward_rays_touched": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),
+                                                  C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vr_tree_step": (C.c_int, [C.c_void_p, C.POINTER(VrStep), C.c_void_p]),
     "vr_render_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
                                  C.POINTER(VrRayOut), C.c_void_p]),
     "vr_accumulate_weights_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),

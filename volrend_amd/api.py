@@ -481,7 +481,7 @@ class N3Tree:
 
     # ---- gradients of a rendered batch (vr_render_backward) ----------------
     def render_backward(self, cam: "Camera", transforms, options: "RenderOptions", grad_accum, *, grad_data=None,
-                        fp_mode: int = _abi.FP_STRICT, stream=None):
+                        fp_mode: int = _abi.FP_STRICT, stream=None, touched=None):
         """The derivative of a rendered batch with respect to the tree's values -- vr_render_backward,
         enqueued on ``stream``, one launch per 512 poses.
 
@@ -491,9 +491,14 @@ class N3Tree:
         contributions were ADDED into: ``grad_data`` when given (contiguous, float32), else one allocated
         zeroed.  The sum uses float atomics: two runs may differ in the last bits.  The march is that of
         ``accumulate_weights`` (offscreen, no mesh depth); render_depth, enable_probe, rot_dirs, a narrowed
-        basis_minmax and SG / ASG trees are refused."""
+        basis_minmax and SG / ASG trees are refused.
+
+        ``touched``: an int32 tensor of ``touched_words()`` words selects the marked call
+        (vr_render_backward_touched): the bit of every slot the call adds into is ORed into it -- bit s & 31 of
+        word s >> 5, s = file node * N^3 + child slot; zero it once.  The marks are bit-reproducible; ``step``
+        consumes them."""
         return render_backward(self, cam, transforms, options, grad_accum, grad_data=grad_data, fp_mode=fp_mode,
-                               stream=stream)
+                               stream=stream, touched=touched)
 
     # ---- ray lists (vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays) ----
     def reserve_rays(self, n: int, n_slots: int = 2) -> None:
@@ -524,12 +529,33 @@ class N3Tree:
                                        fp_mode=fp_mode, stream=stream, n=n)
 
     def render_backward_rays(self, origins, dirs, options: "RenderOptions", grad_accum, *, grad_data=None,
-                             fp_mode: int = _abi.FP_STRICT, stream=None, n=None):
+                             fp_mode: int = _abi.FP_STRICT, stream=None, n=None, touched=None):
         """``render_backward`` over the rays of a list (as ``render_rays`` takes them) -- vr_render_backward_rays,
         one launch.  ``grad_accum``: float32 [n, 4], row i for ray i: dL/d of the four numbers ``render_rays``
-        returns as "accum".  Returns the float32 tensor [capacity, N, N, N, data_dim] added into."""
+        returns as "accum".  Returns the float32 tensor [capacity, N, N, N, data_dim] added into.  ``touched``: as
+        ``render_backward`` takes it (vr_render_backward_rays_touched)."""
         return render_backward_rays(self, origins, dirs, options, grad_accum, grad_data=grad_data, fp_mode=fp_mode,
-                                    stream=stream, n=n)
+                                    stream=stream, n=n, touched=touched)
+
+    # ---- a sparse optimiser step, in place (vr_tree_step) ----
+    def touched_words(self) -> int:
+        """Words of a ``touched`` bitmap of this tree: ceil(capacity * N^3 / 32)."""
+        return touched_words(self)
+
+    def step(self, master, grad, touched, *, kind="sgd", lr, lr_sigma=None, m=None, v=None, betas=(0.9, 0.999),
+             eps: float = 1e-8, step: int = 1, stream=None) -> None:
+        """An optimiser step over ONLY the slots marked in ``touched``, written into the DEVICE copy in place --
+        vr_tree_step, enqueued on ``stream``.
+
+        ``master`` / ``grad`` (and ``m`` / ``v`` for kind="adam"): float32 tensors of capacity * N^3 * data_dim
+        elements, contiguous, on the tree's device, indexed like the file's ``data`` array; ``touched``: the int32
+        bitmap a marked ``render_backward`` / ``render_backward_rays`` filled.  In every marked slot ``master``
+        moves by the rule of include/volrend_hip.h (``lr_sigma``: the rate of the sigma entry, default ``lr``;
+        Adam's moments of unmarked slots stand still), the tree takes float16(master), ``grad`` becomes +0; then
+        the bitmap is zero.  Unmarked slots are neither read nor written.  WRITES the tree, ordered as
+        ``update_data`` is; the host arrays of this object go stale."""
+        tree_step(self, master, grad, touched, kind=kind, lr=lr, lr_sigma=lr_sigma, m=m, v=v, betas=betas, eps=eps,
+                  step=step, stream=stream)
 
     # ---- the values of the device copy, in place (vr_tree_update_data / vr_tree_read_data) ----
     def update_data(self, data, stream=None) -> None:
@@ -827,10 +853,34 @@ def accumulate_weights(tree, cam: Camera, transforms, options: RenderOptions, *,
     return res
 
 
+def touched_words(tree) -> int:
+    """Words of a ``touched`` bitmap of this tree: ceil(capacity * N^3 / 32)."""
+    return (tree.capacity * tree.N ** 3 + 31) // 32
+
+
+def _touched_ptr(tree, touched) -> int:
+    """Checks a ``touched`` bitmap -- an int32 tensor of ``touched_words(tree)`` elements, contiguous, CUDA (or a raw
+    device pointer) -> its address.  Raises ValueError before any C call."""
+    if isinstance(touched, int) and not isinstance(touched, bool):
+        return touched
+    if not (hasattr(touched, "is_contiguous") and hasattr(touched, "data_ptr")):
+        raise ValueError(f"touched must be a torch tensor or a raw device pointer, got {type(touched)}")
+    if str(touched.dtype) != "torch.int32":
+        raise ValueError(f"touched must be int32 (32 slots a word), not {touched.dtype}")
+    n = touched_words(tree)
+    if touched.numel() != n or not touched.is_contiguous():
+        raise ValueError(f"touched must be a contiguous tensor of ceil(capacity * N^3 / 32) = {n} words, "
+                         f"not {tuple(touched.shape)}")
+    if not touched.is_cuda:
+        raise ValueError(f"touched must be on the tree's device, not {touched.device}")
+    return int(touched.data_ptr())
+
+
 def render_backward(tree, cam: Camera, transforms, options: RenderOptions, grad_accum, *, grad_data=None,
-                    fp_mode: int = _abi.FP_STRICT, stream=None):
+                    fp_mode: int = _abi.FP_STRICT, stream=None, touched=None):
     """``N3Tree.render_backward`` (documented there)."""
     n = len(transforms)
+    t_ptr = None if touched is None else _touched_ptr(tree, touched)
     shape_g = (n, cam.height, cam.width, 4)
     shape_d = (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim)
     for name, buf, shape in (("grad_accum", grad_accum, shape_g), ("grad_data", grad_data, shape_d)):
@@ -852,8 +902,12 @@ def render_backward(tree, cam: Camera, transforms, options: RenderOptions, grad_
         cams = _cameras_c(cam, [transforms[first + i] for i in range(m)]) if m else None
         # (no pose: an empty tensor has no address, and nothing is read -- any non-NULL pointer stands for it)
         g_ptr = _ptr(grad_accum) + first * frame_bytes if m else (_ptr(grad_accum) or _ptr(grad_data))
-        _abi.check(L.vr_render_backward(tree.handle, m, cams, C.byref(o), int(fp_mode), g_ptr, _ptr(grad_data),
-                                        _stream_ptr(stream)))
+        if t_ptr is None:
+            _abi.check(L.vr_render_backward(tree.handle, m, cams, C.byref(o), int(fp_mode), g_ptr, _ptr(grad_data),
+                                            _stream_ptr(stream)))
+        else:
+            _abi.check(L.vr_render_backward_touched(tree.handle, m, cams, C.byref(o), int(fp_mode), g_ptr,
+                                                    _ptr(grad_data), t_ptr, _stream_ptr(stream)))
     return grad_data
 
 
@@ -970,9 +1024,10 @@ def accumulate_weights_rays(tree, origins, dirs, options: RenderOptions, *, max_
 
 
 def render_backward_rays(tree, origins, dirs, options: RenderOptions, grad_accum, *, grad_data=None,
-                         fp_mode: int = _abi.FP_STRICT, stream=None, n=None):
+                         fp_mode: int = _abi.FP_STRICT, stream=None, n=None, touched=None):
     """``N3Tree.render_backward_rays`` (documented there)."""
     rays, n, dev = _ray_list(tree, origins, dirs, n)
+    t_ptr = None if touched is None else _touched_ptr(tree, touched)
     grad_accum = _ray_buffer(grad_accum, "grad_accum", (n, 4), "float32")
     shape_d = (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim)
     if grad_data is None:
@@ -984,8 +1039,12 @@ def render_backward_rays(tree, origins, dirs, options: RenderOptions, grad_accum
     if n == 0:  # (as accumulate_weights_rays)
         rays.origins = rays.dirs = g_ptr = _ptr(grad_data)
     o = options.to_c()
-    _abi.check(_abi.lib().vr_render_backward_rays(tree.handle, n, C.byref(rays), C.byref(o), int(fp_mode), g_ptr,
-                                                  _ptr(grad_data), _stream_ptr(stream)))
+    if t_ptr is None:
+        _abi.check(_abi.lib().vr_render_backward_rays(tree.handle, n, C.byref(rays), C.byref(o), int(fp_mode), g_ptr,
+                                                      _ptr(grad_data), _stream_ptr(stream)))
+    else:
+        _abi.check(_abi.lib().vr_render_backward_rays_touched(tree.handle, n, C.byref(rays), C.byref(o), int(fp_mode),
+                                                              g_ptr, _ptr(grad_data), t_ptr, _stream_ptr(stream)))
     return grad_data
 
 
@@ -1048,6 +1107,33 @@ def read_data(tree, dtype=None, out=None, stream=None):
     ptr, code = _data_buffer(tree, out, "out")
     _abi.check(_abi.lib().vr_tree_read_data(tree.handle, ptr, code, _stream_ptr(stream)))
     return out
+
+
+def tree_step(tree, master, grad, touched, *, kind="sgd", lr, lr_sigma=None, m=None, v=None, betas=(0.9, 0.999),
+              eps: float = 1e-8, step: int = 1, stream=None) -> None:
+    """``N3Tree.step`` (documented there)."""
+    if kind not in _abi.STEP_KINDS:
+        raise ValueError(f"kind names 'sgd' or 'adam', not {kind!r}")
+    s = _abi.VrStep()
+    for name, x in (("master", master), ("grad", grad), ("m", m), ("v", v)):
+        if x is None:
+            if name in ("m", "v") and kind == "sgd":
+                continue
+            raise ValueError(f"{name} is missing" + (" (kind='adam' needs both moments)" if name in ("m", "v") else ""))
+        if isinstance(x, int) and not isinstance(x, bool):   # a raw device pointer
+            setattr(s, name, x)
+            continue
+        if hasattr(x, "is_contiguous") and str(x.dtype) != "torch.float32":
+            raise ValueError(f"{name} must be float32, not {x.dtype}")
+        ptr, code = _data_buffer(tree, x, name)
+        if code != _abi.DATA_F32:
+            raise ValueError(f"{name} must be float32")
+        setattr(s, name, ptr)
+    s.touched = _touched_ptr(tree, touched)
+    s.kind = _abi.STEP_KINDS[kind]
+    s.lr, s.lr_sigma = float(lr), float(lr if lr_sigma is None else lr_sigma)
+    s.beta1, s.beta2, s.eps, s.step = float(betas[0]), float(betas[1]), float(eps), int(step)
+    _abi.check(_abi.lib().vr_tree_step(tree.handle, C.byref(s), _stream_ptr(stream)))
 
 
 def set_tuning(**kw) -> None:

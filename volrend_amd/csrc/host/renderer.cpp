@@ -139,6 +139,21 @@ void render_backward(const N3Tree& tree, const Camera& cam, const std::vector<co
     else for_camera_chunks(cam, transforms, launch);
 }
 
+void render_backward(const N3Tree& tree, const Camera& cam, const std::vector<const float*>& transforms,
+                     const RenderOptions& options, const float* grad_accum, float* grad_data, uint32_t* touched,
+                     void* stream, int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const size_t frame_floats = (size_t)cam.width * (size_t)cam.height * 4;
+    const auto launch = [&](size_t first, int n, const VrCamera* cams) {
+        internal::vr_check(vr_render_backward_touched(tree.device, n, cams, &o, fp_mode,
+                                                      grad_accum ? grad_accum + first * frame_floats : nullptr,
+                                                      grad_data, touched, stream),
+                           "vr_render_backward_touched");
+    };
+    if (transforms.empty()) launch(0, 0, nullptr);
+    else for_camera_chunks(cam, transforms, launch);
+}
+
 void render_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, void* rgba, float* accum,
                  void* stream, int fp_mode) {
     const VrRenderOptions o = to_c(options);
@@ -161,6 +176,15 @@ void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOpti
     const VrRays r{rays.origins, rays.dirs};
     internal::vr_check(vr_render_backward_rays(tree.device, rays.n, &r, &o, fp_mode, grad_accum, grad_data, stream),
                        "vr_render_backward_rays");
+}
+
+void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
+                          const float* grad_accum, float* grad_data, uint32_t* touched, void* stream, int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const VrRays r{rays.origins, rays.dirs};
+    internal::vr_check(vr_render_backward_rays_touched(tree.device, rays.n, &r, &o, fp_mode, grad_accum, grad_data,
+                                                       touched, stream),
+                       "vr_render_backward_rays_touched");
 }
 
 void reserve_rays(const N3Tree& tree, int64_t n, int n_slots) {

@@ -46,6 +46,7 @@ constexpr int kGradWaves = 4;  // per SIMD (profiles/render_backward_kernel_reso
 
 typedef __attribute__((address_space(1))) float vr_gfloat_t;
 typedef __attribute__((address_space(1))) const int32_t vr_gcint_t;
+typedef __attribute__((address_space(1))) uint32_t vr_guint_t;
 
 template <int BASIS>
 struct GradTraits {
@@ -65,8 +66,26 @@ struct GradTraits {
 // protocol there is made here too.  Rays are GradRecord records: the view direction and the pixel's index
 // into grad_accum follow the march words.
 // ---------------------------------------------------------------------------
-template <int FMA, int QUERY, int BASIS>
-__global__ __launch_bounds__(kWave, kGradWaves) void grad_kernel(const KParams p, const GradParams gp) {
+// What a grad_kernel flavour takes of GradParams: the unmarked kernels the three pointers they always took (their
+// kernel arguments, and with them their code, are what they were before the marked calls existed).
+template <bool MARK>
+struct GradArgs {
+    const float* grad_accum;
+    float* grad_data;
+    const int32_t* file_node;
+    explicit GradArgs(const GradParams& g) : grad_accum(g.grad_accum), grad_data(g.grad_data), file_node(g.file_node) {}
+};
+template <>
+struct GradArgs<true> : GradArgs<false> {
+    uint32_t* touched;
+    explicit GradArgs(const GradParams& g) : GradArgs<false>(g), touched(g.touched) {}
+};
+
+// MARK: the flavour of the marked calls (vr_render_backward_touched): the lanes that own an emitting hit also
+// set the slot's bit of `touched`, one vector atomic OR per march round in front of the scatter's
+// n_emit * kChunks adds.  A compile-time flavour: the unmarked kernels hold no trace of it.
+template <int FMA, int QUERY, int BASIS, bool MARK = false>
+__global__ __launch_bounds__(kWave, kGradWaves) void grad_kernel(const KParams p, const GradArgs<MARK> gp) {
     using P = Policy<FMA>;
     using GT = GradTraits<BASIS>;
     constexpr bool N2 = QUERY != kQueryGeneric;
@@ -304,6 +323,12 @@ __global__ __launch_bounds__(kWave, kGradWaves) void grad_kernel(const KParams p
             const unsigned long long m_emit = __builtin_amdgcn_ballot_w64(emit);
             if (m_emit != 0ull) {
                 const int n_emit = __builtin_popcountll(m_emit);
+                if constexpr (MARK) {
+                    // (result unused: the non-returning hardware OR; bits only ever get set, so no order matters)
+                    if (emit)
+                        __hip_atomic_fetch_or((vr_guint_t*)gp.touched + (e_slot >> 5), 1u << (e_slot & 31u),
+                                              __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
                 if (emit) {
                     const uint32_t k = lane_rank(m_emit);
                     s_slot[k] = e_slot;
@@ -354,11 +379,11 @@ __global__ __launch_bounds__(kWave, kGradWaves) void grad_kernel(const KParams p
     }
 }
 
-template <int FMA, int QUERY>
+template <int FMA, int QUERY, bool MARK>
 void launch_march_basis(const KParams& p, const GradParams& gp, dim3 grid, hipStream_t s) {
     switch (basis_flavour(p.format, p.basis_dim)) {
 #define VR_GRAD(B) \
-    case B: hipLaunchKernelGGL((grad_kernel<FMA, QUERY, B>), grid, dim3(kWave), 0, s, p, gp); break
+    case B: hipLaunchKernelGGL((grad_kernel<FMA, QUERY, B, MARK>), grid, dim3(kWave), 0, s, p, GradArgs<MARK>(gp)); break
         VR_GRAD(BASIS_RGBA);
         VR_GRAD(BASIS_1);
         VR_GRAD(BASIS_4);
@@ -369,6 +394,13 @@ void launch_march_basis(const KParams& p, const GradParams& gp, dim3 grid, hipSt
     }
 }
 
+template <int FMA, bool MARK>
+void launch_march_query(int query, const KParams& p, const GradParams& gp, dim3 grid, hipStream_t s) {
+    if (query == kQueryGeneric) launch_march_basis<FMA, kQueryGeneric, MARK>(p, gp, grid, s);
+    else if (query == kQueryN2Blocked) launch_march_basis<FMA, kQueryN2Blocked, MARK>(p, gp, grid, s);
+    else launch_march_basis<FMA, kQueryN2, MARK>(p, gp, grid, s);
+}
+
 template <int FMA>
 hipError_t launch_fp(const KParams& p, const GradParams& gp, int n_cus, int waves_override, int gen_waves,
                      hipStream_t s, const RayList* rays) {
@@ -376,9 +408,8 @@ hipError_t launch_fp(const KParams& p, const GradParams& gp, int n_cus, int wave
     launch_march_raygen<FMA, GradRecord>(p, gen_waves, s, rays);
     const dim3 grid(persistent_grid(total_blocks, n_cus, waves_override > 0 ? waves_override : 4 * kGradWaves));
     const int query = query_kind(p);
-    if (query == kQueryGeneric) launch_march_basis<FMA, kQueryGeneric>(p, gp, grid, s);
-    else if (query == kQueryN2Blocked) launch_march_basis<FMA, kQueryN2Blocked>(p, gp, grid, s);
-    else launch_march_basis<FMA, kQueryN2>(p, gp, grid, s);
+    if (gp.touched) launch_march_query<FMA, true>(query, p, gp, grid, s);
+    else launch_march_query<FMA, false>(query, p, gp, grid, s);
     return hipGetLastError();
 }
 

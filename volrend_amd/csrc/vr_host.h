@@ -82,6 +82,7 @@ struct VrTreeOpaque : TreeShape {
     DeviceBuffer file_node_dev;  // its device copy, made by the first vr_accumulate_weights (then in device_bytes)
     std::vector<int32_t> brick_root;  // n_bricks: the node of each brick, ascending (host; empty without bricks)
     DeviceBuffer brick_root_dev;  // its device copy, made by the first vr_tree_update_data / vr_tree_read_data (then in device_bytes)
+    DeviceBuffer node_of_file_dev;  // file node -> device node, the inverse of file_node: made by the first vr_tree_step (then in device_bytes)
     LaunchSlot slots[kLaunchSlots];
     unsigned launch_seq = 0;
     std::mutex launch_mutex;  // slot bookkeeping + enqueue order of one launch; guards `tn`

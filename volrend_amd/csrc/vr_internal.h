@@ -279,6 +279,7 @@ struct GradParams {
     const float* grad_accum;    // [n_frames][height][width][4]: dL / d out[0..3]
     float* grad_data;           // [capacity * N3 * data_dim], file order; added into
     const int32_t* file_node;   // device node -> the file's node (VrTreeOpaque.file_node)
+    uint32_t* touched;          // marked calls: one bit per slot, file order, ORed into; NULL = the unmarked kernels
 };
 
 // vr_grad.hip: ray generation + the persistent two-phase march of a backward launch
@@ -305,6 +306,27 @@ hipError_t launch_read_values(const UpdateArgs& a, int n_cus, hipStream_t stream
 // the sigma fields of the leaf entries of top grid and bricks, from the node words (after an update)
 hipError_t launch_refresh_lookup(const uint32_t* nodes, const int32_t* brick_root, int n_bricks, uint2* top,
                                  uint32_t* bricks, int top_levels, int brick_levels, hipStream_t stream);
+
+// The sparse step (vr_tree_step, vr_update.hip): an optimiser step over the slots of a bitmap, written into master,
+// moments and tree.  The scalars are what the host formed in binary64 and rounded once.
+struct StepArgs {
+    uint32_t* nodes;            // device layout (vr_dev_layout.h)
+    uint16_t* leaves;
+    const int32_t* node_of_file;  // the file's node -> device node (the inverse of VrTreeOpaque.file_node)
+    float* master;              // [capacity * N3 * data_dim], file order
+    float* grad;
+    float* m;                   // Adam; NULL for SGD
+    float* v;
+    uint32_t* touched;          // n_words words: read, then cleared
+    int64_t n_words;
+    int64_t n_slots;            // capacity * N3: bits at or beyond it are ignored
+    int32_t N3, data_dim;
+    int32_t stride_h;           // fp16 elements between padded records
+    int32_t adam;
+    float lr, lr_sigma;         // SGD: lr_e; Adam: a_e = lr_e / (1 - beta1^step)
+    float beta1, beta2, omb1, omb2, sbc2, eps;
+};
+hipError_t launch_step_values(const StepArgs& a, int n_cus, hipStream_t stream);
 
 // vr_render.hip: the kernels of a launch
 hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream);

@@ -1,5 +1,6 @@
 // vr_launch.cpp -- the march launches (include/volrend_hip.h): vr_render_batch, vr_render_aov, vr_accumulate_weights,
-// vr_render_backward and their ray-list siblings vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays:
+// vr_render_backward and their ray-list siblings vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays
+// (the backward calls also in their marked form, *_touched):
 // argument checks, launch geometry, KParams, and the ONE sequence they all go through (run_launch).  The scheduling
 // rules are vr_launch_plan.cpp, the launch-slot ring is vr_slots.cpp.  Built with -ffp-contract=off (the host-side
 // Rodrigues pre-computation below must round like the oracle).
@@ -470,12 +471,12 @@ int check_backward_options(const char* what, const VrRenderOptions* opt) {
 }
 
 // Everything that can be refused without following the tree handle.
-int validate_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
-                      const float* grad_accum, const float* grad_data, vr::KParams& k) {
+int validate_backward(const char* what, vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
+                      int fp_mode, const float* grad_accum, const float* grad_data, vr::KParams& k) {
     if (!t || !opt || !grad_accum || !grad_data || (n_frames > 0 && !cams))
         return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
     if (int rc = validate_march(n_frames, cams, opt, fp_mode, k)) return rc;
-    return check_backward_options("vr_render_backward", opt);
+    return check_backward_options(what, opt);
 }
 
 // What needs the tree: the formats the backward kernels shade, and the whole basis.
@@ -490,17 +491,31 @@ int check_backward_tree(const VrTreeOpaque* t, const VrRenderOptions* opt, const
     return VR_OK;
 }
 
-// vr_render_backward and vr_render_backward_rays (`what`), as weights_launch.
+// vr_render_backward, vr_render_backward_rays and their marked siblings (`what`; touched = NULL: unmarked), as
+// weights_launch.
 int backward_launch(const char* what, vr_tree_t t, const Views& v, const VrRenderOptions* opt, int fp_mode,
-                    const float* grad_accum, float* grad_data, vr::KParams& k, void* stream) {
+                    const float* grad_accum, float* grad_data, uint32_t* touched, vr::KParams& k, void* stream) {
     if (int rc = check_backward_tree(t, opt, what)) return rc;
     return march_launch(t, LaunchKind::kBackward, v, opt, k, stream, [&](const Turn& u) {
         vr::GradParams g;
         g.grad_accum = grad_accum;
         g.grad_data = grad_data;
         g.file_node = t->file_node_dev.get<int32_t>();
+        g.touched = touched;  // (NULL: the unmarked kernels)
         return vr::launch_grad(u.k, g, fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs, v.rays());
     });
+}
+
+// vr_render_backward_rays (touched = NULL) and vr_render_backward_rays_touched (`what`).
+int backward_rays(const char* what, vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
+                  int fp_mode, const float* grad_accum, float* grad_data, uint32_t* touched, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    Views v;
+    if (!grad_accum) return fail(VR_ERR_INVALID_ARGUMENT, "%s: NULL argument", what);
+    if (int rc = validate_rays(what, t, n, rays, opt, fp_mode, grad_data, k, v)) return rc;
+    if (int rc = check_backward_options(what, opt)) return rc;
+    return backward_launch(what, t, v, opt, fp_mode, grad_accum, grad_data, touched, k, stream);
 }
 
 }  // namespace
@@ -511,19 +526,32 @@ int vr_render_backward(vr_tree_t t, int n_frames, const VrCamera* cams, const Vr
                        const float* grad_accum, float* grad_data, void* stream) {
     vr::KParams k;
     memset(&k, 0, sizeof(k));
-    if (int rc = validate_backward(t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, k)) return rc;
-    return backward_launch("vr_render_backward", t, Views{cams, n_frames}, opt, fp_mode, grad_accum, grad_data, k, stream);
+    if (int rc = validate_backward("vr_render_backward", t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, k)) return rc;
+    return backward_launch("vr_render_backward", t, Views{cams, n_frames}, opt, fp_mode, grad_accum, grad_data, nullptr,
+                           k, stream);
+}
+
+int vr_render_backward_touched(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt, int fp_mode,
+                               const float* grad_accum, float* grad_data, uint32_t* touched, void* stream) {
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    if (!touched) return fail(VR_ERR_INVALID_ARGUMENT, "vr_render_backward_touched: NULL argument");
+    if (int rc = validate_backward("vr_render_backward_touched", t, n_frames, cams, opt, fp_mode, grad_accum, grad_data, k))
+        return rc;
+    return backward_launch("vr_render_backward_touched", t, Views{cams, n_frames}, opt, fp_mode, grad_accum, grad_data,
+                           touched, k, stream);
 }
 
 int vr_render_backward_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
                             const float* grad_accum, float* grad_data, void* stream) {
-    vr::KParams k;
-    memset(&k, 0, sizeof(k));
-    Views v;
-    if (!grad_accum) return fail(VR_ERR_INVALID_ARGUMENT, "vr_render_backward_rays: NULL argument");
-    if (int rc = validate_rays("vr_render_backward_rays", t, n, rays, opt, fp_mode, grad_data, k, v)) return rc;
-    if (int rc = check_backward_options("vr_render_backward_rays", opt)) return rc;
-    return backward_launch("vr_render_backward_rays", t, v, opt, fp_mode, grad_accum, grad_data, k, stream);
+    return backward_rays("vr_render_backward_rays", t, n, rays, opt, fp_mode, grad_accum, grad_data, nullptr, stream);
+}
+
+int vr_render_backward_rays_touched(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
+                                    const float* grad_accum, float* grad_data, uint32_t* touched, void* stream) {
+    if (!touched) return fail(VR_ERR_INVALID_ARGUMENT, "vr_render_backward_rays_touched: NULL argument");
+    return backward_rays("vr_render_backward_rays_touched", t, n, rays, opt, fp_mode, grad_accum, grad_data, touched,
+                         stream);
 }
 
 int vr_accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,

@@ -1,4 +1,4 @@
-// vr_update.hip -- gfx950 kernels of vr_tree_update_data / vr_tree_read_data: the values of an uploaded tree
+// vr_update.hip -- gfx950 kernels of vr_tree_update_data / vr_tree_read_data / vr_tree_step: the values of an uploaded tree
 // moved between the file's array (node numbering and record [R.., G.., B.., sigma] of VrTreeDesc.data) and
 // the device layout (vr_dev_layout.h), in either direction, and the refresh of the sigma fields of the
 // lookup structure.  The topology is never touched: which slot is a leaf is read from the node words.
@@ -198,6 +198,124 @@ __global__ void refresh_bricks_kernel(const uint32_t* nodes, const int32_t* bric
     bricks[gid] = (e & 0xFFFF0000u) | (nodes[(uint64_t)node * 8u + slot] & 0xFFFFu);
 }
 
+// Sparse step (vr_tree_step): ONE streaming pass over the bitmap of touched slots, no scratch in global memory, no
+// atomics.  A wave takes kWave consecutive words, one per lane, and skips them on an all-zero ballot (the common
+// case where rays are few).  Otherwise the lanes write the positions of their set bits, in order, into a per-wave
+// LDS table (a prefix sum of the popcounts places them), and the wave walks the table with its lanes ACROSS the
+// data_dim elements of a slot: the file-side run is contiguous (SH16: 196 bytes of master, grad and the moments
+// each).  Records shorter than half a wave pack kWave / data_dim slots into one instruction, each lane group a run
+// of its own (as GradTraits::kPack).  A slot costs two dependent trips to memory (its device node, then its node
+// word), and the slots of a batch cluster -- a wave may own two thousand of them -- so kStepFlight slots are in
+// flight per lane at a time: all their loads are issued before the first value is formed (one slot at a time ran
+// at 0.5 TB/s on the bench tree, latency bound).  The wave that owns a word clears it.  The arithmetic is the
+// header's, one rounding per operator (-ffp-contract=off, IEEE divide and square root); the tree takes half_bits()
+// of the new value as update_values_kernel<true> stores it: coefficients into the padded record of the DEVICE slot
+// (the padding is never written), sigma through the leaf-bit rule of put_sigma.
+constexpr int kStepWaves = 4;
+constexpr int kStepSlots = kWave * 32;  // the slots of a wave's kWave words
+constexpr int kStepFlight = 8;          // slots in flight per lane
+
+__global__ __launch_bounds__(kStepWaves * kWave) void step_values_kernel(StepArgs a) {
+    __shared__ uint16_t s_list[kStepWaves][kStepSlots];  // positions of the set bits of the wave's words, ascending
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & (kWave - 1);
+    uint16_t* list = s_list[wave];
+    const int dd = a.data_dim;
+    const int pack = dd * 2 <= kWave ? kWave / dd : 1;  // slots per wave instruction
+    const int chunks = (dd + kWave - 1) / kWave;        // wave instructions per slot
+    const int my_sub = pack > 1 ? lane / dd : 0;
+    const int my_elem = pack > 1 ? lane - my_sub * dd : lane;
+    const uint32_t N3 = (uint32_t)a.N3;
+    const bool pow2 = (N3 & (N3 - 1u)) == 0u;
+    const int shift = __builtin_ctz(N3);
+    const int64_t n_groups = (a.n_words + kWave - 1) / kWave;
+    for (int64_t grp = (int64_t)blockIdx.x * kStepWaves + wave; grp < n_groups;
+         grp += (int64_t)gridDim.x * kStepWaves) {
+        const int64_t wi = grp * kWave + lane;
+        const uint32_t word = wi < a.n_words ? a.touched[wi] : 0u;
+        if (__builtin_amdgcn_ballot_w64(word != 0u) == 0ull) continue;
+        if (word != 0u) a.touched[wi] = 0u;
+        // where this lane's bits go: the number of set bits in the lanes below
+        const int count = __builtin_popcount(word);
+        int below = count;
+        for (int d = 1; d < kWave; d <<= 1) {
+            const int up = __shfl_up(below, d, kWave);
+            if (lane >= d) below += up;
+        }
+        const int total = __shfl(below, kWave - 1, kWave);
+        below -= count;
+        for (uint32_t b = word; b != 0u; b &= b - 1u) list[below++] = (uint16_t)(lane * 32 + __builtin_ctz(b));
+        // (one wave: its LDS operations execute in order; the compiler must not reorder them)
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const uint64_t base = (uint64_t)grp * kStepSlots;
+        for (int ck = 0; ck < chunks; ++ck) {
+            const int e = my_elem + ck * kWave;
+            const bool lane_on = my_sub < pack && e < dd;
+            const bool is_sigma = e == dd - 1;
+            const float lr = is_sigma ? a.lr_sigma : a.lr;
+            for (int k0 = 0; k0 < total; k0 += kStepFlight * pack) {
+                bool on[kStepFlight];
+                uint64_t i[kStepFlight], dslot[kStepFlight];
+                uint32_t in_node[kStepFlight], old_word[kStepFlight];
+                int32_t dnode[kStepFlight];
+                float g[kStepFlight], w[kStepFlight], m[kStepFlight], v[kStepFlight];
+                // every load of the kStepFlight slots first: the device nodes in front, the node words need them
+#pragma unroll
+                for (int u = 0; u < kStepFlight; ++u) {
+                    const int k = k0 + u * pack + my_sub;
+                    on[u] = lane_on && k < total;
+                    const uint64_t slot = base + (on[u] ? (uint32_t)list[k] : 0u);
+                    on[u] = on[u] && slot < (uint64_t)a.n_slots;  // bits at or beyond capacity * N3 stand for no slot
+                    const uint64_t node = pow2 ? slot >> shift : slot / N3;  // the file's node
+                    in_node[u] = (uint32_t)(slot - node * N3);
+                    i[u] = slot * (uint32_t)dd + (uint32_t)e;
+                    dnode[u] = on[u] ? a.node_of_file[node] : 0;
+                }
+#pragma unroll
+                for (int u = 0; u < kStepFlight; ++u) {
+                    g[u] = on[u] ? a.grad[i[u]] : 0.f;
+                    w[u] = on[u] ? a.master[i[u]] : 0.f;
+                    m[u] = on[u] && a.adam ? a.m[i[u]] : 0.f;
+                    v[u] = on[u] && a.adam ? a.v[i[u]] : 0.f;
+                }
+#pragma unroll
+                for (int u = 0; u < kStepFlight; ++u) {
+                    dslot[u] = (uint64_t)(uint32_t)dnode[u] * N3 + in_node[u];
+                    old_word[u] = on[u] && is_sigma ? a.nodes[dslot[u]] : 0u;
+                }
+#pragma unroll
+                for (int u = 0; u < kStepFlight; ++u) {
+                    if (!on[u]) continue;
+                    float w1;
+                    if (a.adam) {
+                        const float m1 = a.beta1 * m[u] + a.omb1 * g[u];
+                        const float v1 = a.beta2 * v[u] + (a.omb2 * g[u]) * g[u];
+                        w1 = w[u] - lr * (m1 / (__builtin_sqrtf(v1) / a.sbc2 + a.eps));
+                        a.m[i[u]] = m1;
+                        a.v[i[u]] = v1;
+                    } else {
+                        w1 = w[u] - lr * g[u];
+                    }
+                    a.master[i[u]] = w1;
+                    a.grad[i[u]] = 0.f;
+                    const uint32_t h = half_bits(w1);
+                    if (is_sigma) {
+                        uint32_t nw = old_word[u];
+                        put_sigma(&nw, h);  // (an internal slot keeps its word: its sigma is ignored)
+                        if (nw != old_word[u]) a.nodes[dslot[u]] = nw;
+                    } else {
+                        a.leaves[dslot[u] * (uint32_t)a.stride_h + (uint32_t)e] = (uint16_t)h;
+                    }
+                }
+            }
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
 // the staged kernels take this run of this array
 bool staged(const UpdateArgs& a) {
     const int64_t run = (int64_t)a.N3 * a.data_dim;
@@ -237,6 +355,13 @@ hipError_t launch_read_values(const UpdateArgs& a, int n_cus, hipStream_t stream
         if (a.f32) hipLaunchKernelGGL(read_values_generic_kernel<true>, grid, block, 0, stream, a);
         else hipLaunchKernelGGL(read_values_generic_kernel<false>, grid, block, 0, stream, a);
     }
+    return hipGetLastError();
+}
+
+hipError_t launch_step_values(const StepArgs& a, int n_cus, hipStream_t stream) {
+    const int64_t n_groups = (a.n_words + kWave - 1) / kWave;
+    const dim3 grid(stream_grid((n_groups + kStepWaves - 1) / kStepWaves, n_cus)), block(kStepWaves * kWave);
+    hipLaunchKernelGGL(step_values_kernel, grid, block, 0, stream, a);
     return hipGetLastError();
 }
 

@@ -418,7 +418,7 @@ int vr_tree_clone(vr_tree_t src, int device, vr_tree_t* out) {
     t->tn = src->tn;
     t->file_node = src->file_node;  // (its device copy is made on the clone's first vr_accumulate_weights)
     t->brick_root = src->brick_root;  // (likewise: on the clone's first vr_tree_update_data / vr_tree_read_data)
-    t->device_bytes -= src->file_node_dev.bytes() + src->brick_root_dev.bytes();
+    t->device_bytes -= src->file_node_dev.bytes() + src->brick_root_dev.bytes() + src->node_of_file_dev.bytes();
     // the re-laid-out arrays travel device to device (over xGMI between two GPUs of a node):
     // no second pass over PCIe, no second re-layout
     // direct peer access (xGMI / PCIe P2P) when the two devices have it: hipMemcpyPeer then moves

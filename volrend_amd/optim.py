@@ -6,6 +6,10 @@ it into the tree (``update_data``: to nearest even) and renders with the HIP ker
 derivative with respect to THE BINARY16 VALUES THE TREE HOLDS and is handed straight through to the float32
 master: the rounding is treated as the identity, as mixed-precision optimisers treat it.  A step smaller than
 half a binary16 ulp of a value therefore moves the master but not yet the render.
+
+``SparseTreeOptimizer`` is the loop whose cost follows the rays and not the size of the tree: ``render_rays`` ->
+(the caller's loss) -> the marked ``render_backward_rays`` -> ``tree_step`` over the slots the rays hit.  The tree
+is always current, so nothing is rewritten whole, no dense gradient is zeroed and no dense optimiser pass runs.
 """
 from __future__ import annotations
 
@@ -53,3 +57,48 @@ class TreeRays(torch.nn.Module):
 
     def forward(self, origins, dirs):
         return RenderRaysFunction.apply(self.data, self.tree, origins, dirs, self.options, self.fp_mode)
+
+
+class SparseTreeOptimizer:
+    """SGD or Adam over only the leaf slots a batch of rays hits, with the tree on the device kept current.
+
+    Owns ``master`` (float32, from ``read_data(float32)``), ``grad`` (float32, zero between steps), the bitmap
+    ``touched`` and, for kind="adam", the moments ``m`` and ``v`` -- all in the file's indexing.  One iteration:
+    ``accum = opt.render(origins, dirs)``; form dL/d accum; ``opt.backward(origins, dirs, grad_accum)``;
+    ``opt.step()``.  Several ``backward`` calls before one ``step`` accumulate.  Everything is enqueued on the
+    current stream.  The gradient is handed straight through the binary16 rounding, as ``TreeRays`` does; Adam's
+    moments of slots a step does not touch stand still (sparse-Adam semantics)."""
+
+    def __init__(self, tree: "api.N3Tree", kind: str = "sgd", lr: float = 1e-2, lr_sigma: "float | None" = None,
+                 betas=(0.9, 0.999), eps: float = 1e-8, options: "api.RenderOptions | None" = None,
+                 fp_mode: int = _abi.FP_STRICT):
+        if kind not in _abi.STEP_KINDS:
+            raise ValueError(f"kind names 'sgd' or 'adam', not {kind!r}")
+        self.tree, self.kind = tree, kind
+        self.lr, self.lr_sigma, self.betas, self.eps = lr, lr_sigma, tuple(betas), eps
+        self.options = options or api.RenderOptions()
+        self.fp_mode = int(fp_mode)
+        self.master = api.read_data(tree, dtype=torch.float32)
+        self.grad = torch.zeros_like(self.master)
+        self.touched = torch.zeros(api.touched_words(tree), dtype=torch.int32, device=self.master.device)
+        self.m = torch.zeros_like(self.master) if kind == "adam" else None
+        self.v = torch.zeros_like(self.master) if kind == "adam" else None
+        self.steps = 0
+
+    def render(self, origins, dirs):
+        """The accumulators [n, 4] of the rays, from the tree as it stands (no ``update_data``: it is current)."""
+        return api.render_rays(self.tree, origins, dirs, self.options, want=("accum",), fp_mode=self.fp_mode,
+                               stream=torch.cuda.current_stream(self.master.device))["accum"]
+
+    def backward(self, origins, dirs, grad_accum) -> None:
+        """Adds the rays' gradient into ``grad`` and marks the slots it lands in."""
+        api.render_backward_rays(self.tree, origins, dirs, self.options, grad_accum.contiguous().to(torch.float32),
+                                 grad_data=self.grad, fp_mode=self.fp_mode, touched=self.touched,
+                                 stream=torch.cuda.current_stream(self.master.device))
+
+    def step(self) -> None:
+        """The optimiser step over the marked slots; afterwards ``grad`` and ``touched`` are zero again."""
+        self.steps += 1
+        api.tree_step(self.tree, self.master, self.grad, self.touched, kind=self.kind, lr=self.lr,
+                      lr_sigma=self.lr_sigma, m=self.m, v=self.v, betas=self.betas, eps=self.eps, step=self.steps,
+                      stream=torch.cuda.current_stream(self.master.device))
