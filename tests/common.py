@@ -502,3 +502,53 @@ def mesh_underlay(w, h, seed=5):
     rng = np.random.default_rng(seed)
     return (rng.integers(0, 256, size=(h, w, 4), dtype=np.uint8),
             rng.uniform(2.0, 6.0, size=(h, w)).astype(np.float32))
+
+
+# ---- stand-ins for the Python API's argument checks (no GPU, no library) -------------------------
+class FakeTree:
+    """A duck-typed tree whose handle is never followed.  ``attrs``: the attributes it has (the defaults are
+    those of a 10-node N = 2 SH16 tree); ``info``: "raises" (the tree must not be asked anything), or the device
+    index ``info()`` answers.  ``info_calls`` counts either way."""
+    HANDLE = 0x1000
+
+    def __init__(self, info="raises", **attrs):
+        self._info, self.info_calls = info, 0
+        for k, v in dict(dict(handle=self.HANDLE, capacity=10, N=2, data_dim=49, data_format=("SH", 16)), **attrs).items():
+            if v is not None:   # (None: the fake does not have that attribute)
+                setattr(self, k, v)
+
+    def info(self):
+        self.info_calls += 1
+        if self._info == "raises":
+            raise AssertionError("the tree must not be asked anything")
+        return {"device": self._info}
+
+
+class FakeCudaTensor:
+    """What the argument checks read of a torch CUDA tensor, with no GPU behind it: the address is never followed."""
+
+    class _Dtype(str):
+        __repr__ = __str__ = lambda self: "torch." + str.__str__(self)
+
+    class _Device:
+        def __init__(self, kind, index):
+            self.type, self.index = kind, index
+
+        def __str__(self):
+            return self.type if self.index is None else f"{self.type}:{self.index}"
+
+    def __init__(self, shape, dtype="float32", ptr=0x7000, contiguous=True, is_cuda=True, index=0):
+        self.shape, self.dtype, self._ptr, self._contiguous = tuple(shape), self._Dtype(dtype), ptr, contiguous
+        self.is_cuda, self.device = is_cuda, self._Device("cuda" if is_cuda else "cpu", index if is_cuda else None)
+
+    def is_contiguous(self):
+        return self._contiguous
+
+    def data_ptr(self):
+        return self._ptr
+
+    def numel(self):
+        return int(np.prod(self.shape, dtype=np.int64))
+
+    def dim(self):
+        return len(self.shape)

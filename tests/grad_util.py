@@ -124,6 +124,14 @@ def poses(n, size=96, radius=4.0):
     return [common.camera_for(pose_idx=i % 8, size=size, radius=radius)[0] for i in range(n)]
 
 
+def decoy_pose(transform):
+    """`transform` turned round where it stands: right and back negated (still a rotation).  From a camera that
+    looked at the scene every ray now leaves it; the tests that use it check that first."""
+    d = np.array(transform, np.float32)
+    d[0:3], d[6:9] = -d[0:3], -d[6:9]
+    return d
+
+
 def upstream(kind, n, h, w, seed=7):
     """grad_accum of n frames, float32 [n, h, w, 4]."""
     if kind == "normal":

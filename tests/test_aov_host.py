@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+from tests import common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -125,14 +126,10 @@ def test_unsupported_through_c(L):
     assert rc == UNSUPPORTED and "counters" in msg and "frame 1" in msg
 
 
-class _FakeTree:
-    handle = TREE
-
-
 def test_refusals_through_python(L):
     from volrend_amd import api
     cam = api.Camera(64, 48, 50.0, 50.0)
-    t = _FakeTree()
+    t = common.FakeTree(handle=TREE, capacity=None, N=None, data_dim=None, data_format=None)
 
     def code(**kw):
         opts = kw.pop("opts", api.RenderOptions())

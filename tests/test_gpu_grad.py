@@ -287,3 +287,33 @@ def test_tree_dependent_refusals_write_nothing(torch_cuda):
         assert_parity(got.cpu().numpy(), ref, what="rgba with a narrowed basis_minmax")
     finally:
         t.free_device()
+
+
+def test_more_poses_than_one_launch_in_one_python_call(torch_cuda):
+    """513 poses at 40 x 40 in one call are two launches, the second reading grad_accum from frame 512 on: 512
+    decoys whose every ray misses the box (their grad_accum is finite non-zero garbage), then the real pose with
+    the reference's g.  A wrong byte offset reads the garbage, or zeros."""
+    torch = torch_cuda
+    from volrend_amd import _abi, api
+    ref = gu.reference("sh4", "default", 0, 1, 40)
+    n, real = _abi.MAX_BATCH, ref["trs"][0]
+    decoy = gu.decoy_pose(real)
+    g = torch.empty((n + 1, ref["h"], ref["w"], 4), dtype=torch.float32, device="cuda")
+    g[:n] = torch.from_numpy(sentinel((ref["h"], ref["w"], 4)) * np.float32(2.0 ** 40)).cuda()   # 1 .. 251
+    g[n] = torch.from_numpy(np.array(ref["g"][0])).cuda()
+    t = upload(ref)
+    try:
+        alone = t.accumulate_weights(api.Camera(ref["w"], ref["h"], ref["f"], ref["f"]), [decoy],
+                                     api.RenderOptions(**ref["opt"]), want=("max_weight", "hits"))
+        one = backward(torch, t, ref, 0)
+        many = backward(torch, t, ref, 0, g=g, trs=[decoy] * n + [real])
+        torch.cuda.synchronize()
+        assert t.status() == 0
+        alone = {k: v.cpu().numpy() for k, v in alone.items()}
+        one, many = one.cpu().numpy(), many.cpu().numpy()
+    finally:
+        t.free_device()
+    assert not alone["max_weight"].any() and not alone["hits"].any(), "the decoy pose reaches the tree"
+    assert_parity(many, ref, what="513 poses")
+    worst = float((np.abs(many.astype(np.float64) - one.astype(np.float64)) - 2 * gu.K * gu.unit(ref)).max())
+    assert worst <= 0, "513 poses and the real pose alone differ by more than two runs of the atomic sum may"

@@ -293,3 +293,30 @@ def test_sample_guard_sets_the_status_bit(torch_cuda):
         assert (mw_cut <= mw_full).all()
     finally:
         t.free_device()
+
+
+def test_more_poses_than_one_launch_in_one_python_call(torch_cuda):
+    """513 poses at 40 x 40 in one call are two launches: 512 decoys whose every ray misses the box, then the real
+    pose.  The result must be that of the real pose alone, bit for bit: a chunk loop that reuses the first
+    chunk's cameras gives zeros."""
+    torch = torch_cuda
+    from tests import grad_util as gu
+    from volrend_amd import _abi, api
+    ref = gu.reference("sh4", "default", 0, 1, 40)
+    real, both = ref["trs"][0], ("max_weight", "hits")
+    decoy = gu.decoy_pose(real)
+    cam, opts = api.Camera(ref["w"], ref["h"], ref["f"], ref["f"]), api.RenderOptions(**ref["opt"])
+    t = api.N3Tree.from_synth(ref["tree"])
+    try:
+        runs = [t.accumulate_weights(cam, trs, opts, want=both)
+                for trs in ([decoy], [real], [decoy] * _abi.MAX_BATCH + [real])]
+        torch.cuda.synchronize()
+        assert t.status() == 0
+        alone, one, many = ({k: host(v) for k, v in r.items()} for r in runs)
+    finally:
+        t.free_device()
+    for k in both:
+        assert not alone[k].any(), f"the decoy pose reaches the tree ({k})"
+    assert (one["max_weight"] > 0).any() and one["hits"].any(), "the real pose shows nothing"
+    for k in both:
+        assert np.array_equal(many[k].view(np.uint32), one[k].view(np.uint32)), k

@@ -8,6 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -97,19 +98,11 @@ def test_unsupported_options_through_c(L):
         assert rc == UNSUPPORTED and "rot_dirs" in msg
 
 
-class _FakeTree:
-    handle = TREE
-    capacity, N, data_dim = 10, 2, 49
-
-    def info(self):
-        raise AssertionError("the tree must not be asked anything")
-
-
 def test_refusals_through_python(L):
     torch = pytest.importorskip("torch")
     from volrend_amd import api
     cam = api.Camera(64, 48, 50.0, 50.0)
-    t = _FakeTree()
+    t = common.FakeTree(handle=TREE)
     tr = np.zeros(12, np.float32)
     good_g = torch.zeros((2, 48, 64, 4), dtype=torch.float32)
     good_d = torch.zeros((10, 2, 2, 2, 49), dtype=torch.float32)
@@ -128,12 +121,10 @@ def test_refusals_through_python(L):
     refused(g=None, match="grad_accum")
     refused(g=np.zeros((2, 48, 64, 4), np.float32), match="torch tensor")
 
-    # what the C call refuses comes back as VolrendError (the host tensors are never read: refused first)
+    # what the C call refuses comes back as VolrendError (raw pointers: nothing is read, refused first)
     def code(opts=None, transforms=(tr, tr), **kw):
         with pytest.raises(_abi.VolrendError) as e:
-            n = len(transforms)
-            api.render_backward(t, cam, list(transforms), opts or api.RenderOptions(),
-                                torch.zeros((n, 48, 64, 4)), grad_data=good_d, **kw)
+            api.render_backward(t, cam, list(transforms), opts or api.RenderOptions(), G, grad_data=D, **kw)
         return e.value.code
 
     assert code(fp_mode=5) == INVALID

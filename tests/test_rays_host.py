@@ -8,6 +8,7 @@ import subprocess
 
 import pytest
 
+from tests import common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -125,18 +126,10 @@ def test_reserve_rays_refusals(L):
         assert L.vr_reserve_rays(TREE, n, 2) == INVALID and b"n=" in L.vr_last_error()
 
 
-class _FakeTree:
-    handle = TREE
-    capacity, N, data_dim = 10, 2, 49
-
-    def info(self):
-        raise AssertionError("the tree must not be asked anything")
-
-
 def test_refusals_through_python(L):
     torch = pytest.importorskip("torch")
     from volrend_amd import api
-    t = _FakeTree()
+    t = common.FakeTree(handle=TREE)
     good = torch.zeros((100, 3), dtype=torch.float32)
     opts = api.RenderOptions()
     calls = {

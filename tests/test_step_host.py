@@ -10,7 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import step_util as su
+from tests import common, step_util as su
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -142,18 +142,10 @@ def test_marked_backward_refusals_through_c(L):
     assert lists(rays=empty)[0] == INVALID
 
 
-class _FakeTree:
-    handle = TREE
-    capacity, N, data_dim = 10, 2, 49
-
-    def info(self):
-        raise AssertionError("the tree must not be asked anything")
-
-
 def test_refusals_through_python(L):
     torch = pytest.importorskip("torch")
     from volrend_amd import api
-    t = _FakeTree()
+    t = common.FakeTree(handle=TREE)
     assert api.touched_words(t) == 3    # 80 slots
     shape = (10, 2, 2, 2, 49)
     x = torch.zeros(shape, dtype=torch.float32)

@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from tests import common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,18 +59,10 @@ def test_invalid_arguments_through_c(L, name):
     assert call(tree=None, dtype=1)[0] == INVALID and call(data=None, dtype=1)[0] == INVALID
 
 
-class _FakeTree:
-    handle = TREE
-    capacity, N, data_dim = 10, 2, 49
-
-    def info(self):
-        raise AssertionError("the tree must not be asked anything")
-
-
 def test_refusals_through_python(L):
     torch = pytest.importorskip("torch")
     from volrend_amd import api
-    t = _FakeTree()
+    t = common.FakeTree(handle=TREE)
     shape = (10, 2, 2, 2, 49)
 
     def refused(x, match):

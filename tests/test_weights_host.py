@@ -10,6 +10,7 @@ import tempfile
 import numpy as np
 import pytest
 
+from tests import common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -107,15 +108,10 @@ def test_invalid_arguments_through_c(L):
     assert _call(L, 1, cams, opt, out)[0] == INVALID
 
 
-class _FakeTree:
-    handle = TREE
-    capacity, N = 10, 2
-
-
 def test_refusals_through_python(L):
     from volrend_amd import api
     cam = api.Camera(64, 48, 50.0, 50.0)
-    t = _FakeTree()
+    t = common.FakeTree(handle=TREE, data_dim=None, data_format=None)
     tr = np.zeros(12, np.float32)
 
     def code(transforms=(tr, tr), opts=None, **kw):

@@ -1,0 +1,351 @@
+"""The operations on an uploaded tree other than rendering frames: point queries, leaf weights, gradients, ray
+lists, the values in place, the sparse step.  One function each: ``tree`` comes first and is duck-typed (``handle``,
+``capacity``, ``N``, ``data_dim``, ``data_format``, ``info()``), and ``N3Tree`` binds the same function as a method,
+so ``tree.render_rays(o, d, opts)`` is ``render_rays(tree, o, d, opts)``.
+
+Every operation reads ``tree.handle`` first (a tree that is not on the device is refused before any argument is looked
+at) and passes every buffer argument through ``_args.check``: a tensor-like object, an object with
+``__cuda_array_interface__`` or a raw device pointer; what a caller passes as an output is returned as passed."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _abi
+from ._args import F16, F32, I32, U8, _TYPESTR, Buf, _stream_ptr, allocate, check, outputs, parse_want, placeholder
+from ._frame import Camera, RenderOptions, _cameras_c
+
+_DATA_DTYPES = {F16: _abi.DATA_F16, F32: _abi.DATA_F32}
+
+
+def _pose_chunks(cam: Camera, transforms):
+    """``transforms`` in launches of at most ``_abi.MAX_BATCH`` poses -> (first, m, cams); no pose: one (0, 0, None)."""
+    n = len(transforms)
+    for first in range(0, max(n, 1), _abi.MAX_BATCH):
+        m = min(_abi.MAX_BATCH, n - first)
+        yield first, m, (_cameras_c(cam, [transforms[first + i] for i in range(m)]) if m else None)
+
+
+def _marked_call(plain, marked, touched, *args, stream) -> None:
+    """``plain``, or its ``_touched`` form ``marked`` with the bitmap's address when the caller wants the marks."""
+    if touched is None:
+        _abi.check(plain(*args, _stream_ptr(stream)))
+    else:
+        _abi.check(marked(*args, touched, _stream_ptr(stream)))
+
+
+def _leaf_specs(tree) -> dict:
+    shape = (tree.capacity, tree.N, tree.N, tree.N)
+    return {"max_weight": (F32, shape), "hits": (I32, shape)}
+
+
+def _leaf_weights_c(c) -> "_abi.VrLeafWeights":
+    out = _abi.VrLeafWeights()
+    out.max_weight, out.hits = c.ptr.get("max_weight"), c.ptr.get("hits")
+    return out
+
+
+def _data_buf(tree, name: str, x, dtypes=(F16, F32)) -> Buf:
+    n = tree.capacity * tree.N ** 3 * tree.data_dim
+    return Buf(name, x, dtypes, None, (n, f"capacity * N^3 * data_dim = {n} elements"))
+
+
+def _touched_buf(tree, touched) -> Buf:
+    n = touched_words(tree)
+    return Buf("touched", touched, (I32,), None, (n, f"ceil(capacity * N^3 / 32) = {n} words"))
+
+
+def _marks(tree, touched) -> list:
+    """The optional ``touched=`` of the backward calls."""
+    return [] if touched is None else [_touched_buf(tree, touched)]
+
+
+def _touched_ptr(tree, touched) -> int:
+    """Checks a ``touched`` bitmap -> its address."""
+    return check(tree, [_touched_buf(tree, touched)]).ptr["touched"]
+
+
+def _ray_bufs(origins, dirs) -> list:
+    return [Buf("origins", origins, (F32,), ("n", 3), rows=True), Buf("dirs", dirs, (F32,), ("n", 3), rows=True)]
+
+
+def _rays_c(c) -> "_abi.VrRays":
+    rays = _abi.VrRays()
+    rays.origins, rays.dirs = c.ptr["origins"], c.ptr["dirs"]
+    return rays
+
+
+# ---- bulk point queries (vr_query_points / vr_query_grid) --------------
+def _query_outputs(tree, c, want, shape, have_dirs: bool, space: str):
+    """Checks ``want`` / ``space`` and allocates the outputs [*shape(, k)] of the checked call ``c`` on the tree's
+    device -> (dict of tensors, VrQueryOut, space code).  Raises ValueError before any C call."""
+    widths = {"sigma": 0, "depth": 0, "local": 3, "coeffs": tree.data_dim - 1, "rgb": 3}
+    want = parse_want(want, widths, empty_ok=False)
+    if space not in _abi.SPACES:
+        raise ValueError(f"space must be 'world' or 'tree', not {space!r}")
+    if "rgb" in want and not have_dirs:
+        raise ValueError("rgb needs directions")
+    if "rgb" in want and tree.data_format[0] in ("SG", "ASG"):
+        raise ValueError("rgb of SG / ASG trees is not supported by the point queries")
+    specs = {w: (I32 if w == "depth" else F32, tuple(shape) + ((k,) if k else ())) for w, k in widths.items()}
+    res = allocate(c, specs, {}, want, zeros=False)
+    out = _abi.VrQueryOut()
+    for w in want:
+        setattr(out, w, c.ptr[w])
+    return {w: res[w] for w in want}, out, _abi.SPACES[space]
+
+
+def query_points(tree, points, dirs=None, *, want=("sigma",), space: str = "world", stream=None, n=None) -> dict:
+    """What the tree holds at ``points`` [n, 3] (float32, contiguous, on the tree's device; or a
+    raw device pointer with ``n``) -- vr_query_points, one launch, enqueued on ``stream``.
+
+    ``want``: any of "sigma" [n], "depth" [n] int32, "local" [n, 3], "coeffs" [n, data_dim - 1],
+    "rgb" [n, 3] (needs ``dirs`` [n, 3]; evaluated at the direction AS GIVEN, not normalised;
+    strict model).  ``space``: "world" (offset + scale * x is applied) or "tree".  Returns a dict
+    of torch tensors on the tree's device."""
+    handle = tree.handle
+    c = check(tree, [Buf(name, x, (F32,), ("n", 3), rows=True) for name, x in (("points", points), ("dirs", dirs))
+                     if x is not None or name == "points"], n)
+    res, out, sp = _query_outputs(tree, c, want, ("n",), dirs is not None, space)
+    if c.n == 0:  # (empty tensors have no address to pass)
+        return res
+    _abi.check(_abi.lib().vr_query_points(handle, c.n, c.ptr["points"], c.ptr.get("dirs"), sp, C.byref(out),
+                                          _stream_ptr(stream)))
+    return res
+
+
+def query_grid(tree, lo, hi, res, dir=None, *, want=("sigma",), space: str = "world", stream=None) -> dict:
+    """The same at the res[0] x res[1] x res[2] cell centres of the box ``lo``..``hi``, generated
+    on the device (vr_query_grid): cell (i, j, k) sits at lo + (i + 0.5) * ((hi - lo) / res) per
+    axis, in float32.  ``dir``: one direction for all cells (needed for "rgb").  Returns tensors
+    shaped [res0, res1, res2(, k)]."""
+    handle = tree.handle
+    vals = []
+    for name, v, dt in (("lo", lo, np.float32), ("hi", hi, np.float32), ("res", res, np.int64),
+                        ("dir", dir, np.float32)):
+        if v is None and name == "dir":
+            vals.append(None)
+            continue
+        a = np.asarray(v)
+        if a.shape != (3,) or (name == "res" and not np.issubdtype(a.dtype, np.integer)):
+            raise ValueError(f"{name} must be 3 {'integers' if name == 'res' else 'numbers'}")
+        vals.append(a.astype(dt))
+    lo_a, hi_a, res_a, dir_a = vals
+    if (res_a < 1).any() or (res_a > 2 ** 31 - 1).any() or int(res_a.prod(dtype=object)) > 2 ** 40:
+        raise ValueError(f"res must be positive with at most 2^40 cells in all: {tuple(res_a)}")
+    out_t, out, sp = _query_outputs(tree, check(tree, []), want, tuple(int(r) for r in res_a), dir_a is not None,
+                                    space)
+    c_lo, c_hi = (C.c_float * 3)(*map(float, lo_a)), (C.c_float * 3)(*map(float, hi_a))
+    c_res = (C.c_int32 * 3)(*[int(r) for r in res_a])
+    c_dir = None if dir_a is None else C.byref((C.c_float * 3)(*map(float, dir_a)))
+    _abi.check(_abi.lib().vr_query_grid(handle, C.byref(c_lo), C.byref(c_hi), C.byref(c_res), c_dir,
+                                        sp, C.byref(out), _stream_ptr(stream)))
+    return out_t
+
+
+# ---- per-leaf ray weights (vr_accumulate_weights) -----------------------
+def accumulate_weights(tree, cam: Camera, transforms, options: RenderOptions, *, max_weight=None, hits=None,
+                       want=("max_weight",), fp_mode: int = _abi.FP_STRICT, stream=None) -> dict:
+    """Per leaf slot, over every pixel of every pose of ``transforms`` (12 floats each, as
+    ``launch_renderer_batch`` takes them): the largest compositing weight a sample in the slot received
+    ("max_weight", float32) and the number of hit samples in it ("hits", a uint32 count held in an int32
+    tensor) -- vr_accumulate_weights, enqueued on ``stream``, one launch per 512 poses.
+
+    Returns a dict of torch tensors shaped [capacity, N, N, N], indexed like the file's ``child`` /
+    ``data`` arrays.  ``want`` names the outputs; a buffer passed as ``max_weight`` / ``hits`` is wanted
+    too and is ACCUMULATED INTO (it must be contiguous, on the tree's device, and -- max_weight -- hold
+    non-negative, non-NaN floats); the others are allocated zeroed.  Any split of a pose set into calls
+    gives the same bits.  Of ``options`` only step_size, sigma_thresh, stop_thresh and render_bbox are
+    read.  No poses: only the tree's file-order table is put on the device (the warm-up call)."""
+    handle = tree.handle
+    want = parse_want(want, ("max_weight", "hits"))
+    c, res = outputs(tree, [], _leaf_specs(tree), {"max_weight": max_weight, "hits": hits}, want, zeros=True)
+    L, o, out = _abi.lib(), options.to_c(), _leaf_weights_c(c)
+    for _, m, cams in _pose_chunks(cam, transforms):
+        _abi.check(L.vr_accumulate_weights(handle, m, cams, C.byref(o), int(fp_mode), C.byref(out),
+                                           _stream_ptr(stream)))
+    return res
+
+
+# ---- gradients of a rendered batch (vr_render_backward) ----------------
+def touched_words(tree) -> int:
+    """Words of a ``touched`` bitmap of this tree: ceil(capacity * N^3 / 32)."""
+    _ = tree.handle  # (a tree that is not on the device is refused, as by every operation)
+    return (tree.capacity * tree.N ** 3 + 31) // 32
+
+
+def render_backward(tree, cam: Camera, transforms, options: RenderOptions, grad_accum, *, grad_data=None,
+                    fp_mode: int = _abi.FP_STRICT, stream=None, touched=None):
+    """The derivative of a rendered batch with respect to the tree's values -- vr_render_backward,
+    enqueued on ``stream``, one launch per 512 poses.
+
+    ``grad_accum``: float32 [len(transforms), height, width, 4], contiguous, on the tree's device:
+    dL/d of the four numbers ``accums`` of ``launch_renderer_batch`` receive per pixel.  Returns the
+    float32 buffer [capacity, N, N, N, data_dim], indexed like the file's ``data`` array, that the
+    contributions were ADDED into: ``grad_data`` when given (contiguous, float32), else one allocated
+    zeroed.  The sum uses float atomics: two runs may differ in the last bits.  The march is that of
+    ``accumulate_weights`` (offscreen, no mesh depth); render_depth, enable_probe, rot_dirs, a narrowed
+    basis_minmax and SG / ASG trees are refused.
+
+    ``touched``: an int32 buffer of ``touched_words()`` words selects the marked call
+    (vr_render_backward_touched): the bit of every slot the call adds into is ORed into it -- bit s & 31 of
+    word s >> 5, s = file node * N^3 + child slot; zero it once.  The marks are bit-reproducible; ``step``
+    consumes them."""
+    handle = tree.handle
+    shape_d = (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim)
+    bufs = [Buf("grad_accum", grad_accum, (F32,), (len(transforms), cam.height, cam.width, 4))]
+    c, res = outputs(tree, bufs + _marks(tree, touched), {"grad_data": (F32, shape_d)},
+                     {"grad_data": grad_data}, ("grad_data",), zeros=True)
+    L, o, g, d = _abi.lib(), options.to_c(), c.ptr["grad_accum"], c.ptr["grad_data"]
+    frame_bytes = cam.height * cam.width * 16
+    for first, m, cams in _pose_chunks(cam, transforms):
+        _marked_call(L.vr_render_backward, L.vr_render_backward_touched, c.ptr.get("touched"), handle, m, cams,
+                     C.byref(o), int(fp_mode), g + first * frame_bytes if m else placeholder(g, d), d, stream=stream)
+    return res["grad_data"]
+
+
+# ---- ray lists (vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays) ----
+def render_rays(tree, origins, dirs, options: RenderOptions, *, want=("accum",), rgba=None, accum=None,
+                fp_mode: int = _abi.FP_STRICT, stream=None, n=None) -> dict:
+    """Colour along caller-supplied rays -- vr_render_rays, one launch, enqueued on ``stream``.
+
+    ``origins`` / ``dirs``: float32 [n, 3], contiguous, on the tree's device, world space; a direction may have
+    any finite non-zero length (or raw device pointers with ``n``).  Ray i is the ray of a pixel entered
+    behind screen2worlddir's matrix product: the direction is normalised, then everything an offscreen frame
+    does follows, so a list built from a camera gives that frame's bits.  ``want``: "accum" (float32 [n, 4]:
+    trace_ray's output before the composite) and / or "rgba" (uint8 [n, 4]: composited over
+    background_brightness); a buffer passed as ``rgba`` / ``accum`` is wanted too and is written.  Returns a
+    dict of torch tensors.  64 consecutive rays share a wave; the library does not reorder them.
+    render_depth and enable_probe are refused."""
+    handle = tree.handle
+    want = parse_want(want, ("rgba", "accum"))
+    c, res = outputs(tree, _ray_bufs(origins, dirs), {"rgba": (U8, ("n", 4)), "accum": (F32, ("n", 4))},
+                     {"rgba": rgba, "accum": accum}, want, zeros=False, n=n)
+    if not res:
+        raise ValueError("no output is wanted: name 'rgba' and / or 'accum'")
+    if c.n == 0:  # (empty tensors have no address to pass, and nothing would be launched)
+        return res
+    out, rays, o = _abi.VrRayOut(), _rays_c(c), options.to_c()
+    out.rgba, out.accum = c.ptr.get("rgba"), c.ptr.get("accum")
+    _abi.check(_abi.lib().vr_render_rays(handle, c.n, C.byref(rays), C.byref(o), int(fp_mode), C.byref(out),
+                                         _stream_ptr(stream)))
+    return res
+
+
+def accumulate_weights_rays(tree, origins, dirs, options: RenderOptions, *, max_weight=None, hits=None,
+                            want=("max_weight",), fp_mode: int = _abi.FP_STRICT, stream=None, n=None) -> dict:
+    """``accumulate_weights`` over the rays of a list (as ``render_rays`` takes them) --
+    vr_accumulate_weights_rays, one launch.  No rays: only the file-order table is put on the device."""
+    handle = tree.handle
+    want = parse_want(want, ("max_weight", "hits"))
+    c, res = outputs(tree, _ray_bufs(origins, dirs), _leaf_specs(tree), {"max_weight": max_weight, "hits": hits},
+                     want, zeros=True, n=n)
+    out, rays, o = _leaf_weights_c(c), _rays_c(c), options.to_c()
+    if c.n == 0:
+        rays.origins = rays.dirs = placeholder(out.max_weight, out.hits)
+    _abi.check(_abi.lib().vr_accumulate_weights_rays(handle, c.n, C.byref(rays), C.byref(o), int(fp_mode),
+                                                     C.byref(out), _stream_ptr(stream)))
+    return res
+
+
+def render_backward_rays(tree, origins, dirs, options: RenderOptions, grad_accum, *, grad_data=None,
+                         fp_mode: int = _abi.FP_STRICT, stream=None, n=None, touched=None):
+    """``render_backward`` over the rays of a list (as ``render_rays`` takes them) -- vr_render_backward_rays,
+    one launch.  ``grad_accum``: float32 [n, 4], row i for ray i: dL/d of the four numbers ``render_rays``
+    returns as "accum".  Returns the float32 buffer [capacity, N, N, N, data_dim] added into.  ``touched``: as
+    ``render_backward`` takes it (vr_render_backward_rays_touched)."""
+    handle = tree.handle
+    bufs = _ray_bufs(origins, dirs) + [Buf("grad_accum", grad_accum, (F32,), ("n", 4))]
+    c, res = outputs(tree, bufs + _marks(tree, touched),
+                     {"grad_data": (F32, (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim))},
+                     {"grad_data": grad_data}, ("grad_data",), zeros=True, n=n)
+    rays, o, g, d = _rays_c(c), options.to_c(), c.ptr["grad_accum"], c.ptr["grad_data"]
+    if c.n == 0:
+        rays.origins = rays.dirs = g = d
+    L = _abi.lib()
+    _marked_call(L.vr_render_backward_rays, L.vr_render_backward_rays_touched, c.ptr.get("touched"), handle, c.n,
+                 C.byref(rays), C.byref(o), int(fp_mode), g, d, stream=stream)
+    return res["grad_data"]
+
+
+# ---- the values of the device copy, in place (vr_tree_update_data / vr_tree_read_data) ----
+def _data_dtype(dtype) -> str:
+    """torch.float16 / torch.float32 (or their names, or a __cuda_array_interface__ typestr) -> the name."""
+    name = _TYPESTR.get(dtype) if isinstance(dtype, str) and dtype in _TYPESTR else str(dtype).replace("torch.", "")
+    if name not in _DATA_DTYPES:
+        raise ValueError(f"the tree's data must be float16 or float32, not {dtype}")
+    return name
+
+
+def update_data(tree, data, stream=None) -> None:
+    """Overwrites the values of the DEVICE copy with ``data`` -- vr_tree_update_data, enqueued on ``stream``:
+    the step after ``render_backward`` once the optimiser has moved its master parameters.
+
+    ``data``: a torch CUDA tensor (or any object with ``__cuda_array_interface__``) of dtype float16 or
+    float32 with capacity * N^3 * data_dim elements, contiguous, on the tree's device, indexed like the
+    file's ``data`` array ([capacity, N, N, N, data_dim], record [R.., G.., B.., sigma]); a raw device pointer
+    is taken to hold float16.  float32 is rounded to float16 to nearest even, as ``numpy.astype(float16)``
+    rounds.  Afterwards the device copy is bit for bit what a fresh upload of this array would be; the sigma of
+    internal slots is ignored.
+
+    The update WRITES the tree: launches and queries enqueued later on the same stream see the new values,
+    work on other streams has to be ordered with events, and nothing may read the tree while it runs.  The
+    host arrays of the tree object are NOT touched: ``data_`` goes stale, and ``load_device()`` from it would
+    undo the update (``read_data`` returns what the device holds)."""
+    handle = tree.handle
+    c = check(tree, [_data_buf(tree, "data", data)])
+    _abi.check(_abi.lib().vr_tree_update_data(handle, c.ptr["data"], _DATA_DTYPES[c.dtype["data"] or F16],
+                                              _stream_ptr(stream)))
+
+
+def read_data(tree, dtype=None, out=None, stream=None):
+    """The current values of the DEVICE copy in file order -- vr_tree_read_data, enqueued on ``stream``: a
+    torch tensor [capacity, N, N, N, data_dim] of ``dtype`` (torch.float16, the default, or torch.float32:
+    the exact widening) on the tree's device; ``out`` when given (contiguous, that many elements; its dtype
+    decides, ``dtype`` for a raw pointer).  The bits are those uploaded or last written, the sigma of internal
+    slots +0.  Works where the host arrays are gone (``clear_cpu_memory``, a quantised upload, a clone)."""
+    handle = tree.handle
+    name = None if dtype is None else _data_dtype(dtype)
+    if out is None:
+        shape = (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim)
+        c, res = outputs(tree, [], {"out": (name or F16, shape)}, {}, ("out",), zeros=False)
+        out = res["out"]
+    else:
+        c = check(tree, [_data_buf(tree, "out", out)])
+        if name not in (None, c.dtype["out"] or name):
+            raise ValueError(f"out is not of dtype {dtype}")
+    _abi.check(_abi.lib().vr_tree_read_data(handle, c.ptr["out"], _DATA_DTYPES[c.dtype.get("out") or name or F16],
+                                            _stream_ptr(stream)))
+    return out
+
+
+# ---- a sparse optimiser step, in place (vr_tree_step) ----
+def tree_step(tree, master, grad, touched, *, kind="sgd", lr, lr_sigma=None, m=None, v=None, betas=(0.9, 0.999),
+              eps: float = 1e-8, step: int = 1, stream=None) -> None:
+    """An optimiser step over ONLY the slots marked in ``touched``, written into the DEVICE copy in place --
+    vr_tree_step, enqueued on ``stream``.
+
+    ``master`` / ``grad`` (and ``m`` / ``v`` for kind="adam"): float32 buffers of capacity * N^3 * data_dim
+    elements, contiguous, on the tree's device, indexed like the file's ``data`` array; ``touched``: the int32
+    bitmap a marked ``render_backward`` / ``render_backward_rays`` filled.  In every marked slot ``master``
+    moves by the rule of include/volrend_hip.h (``lr_sigma``: the rate of the sigma entry, default ``lr``;
+    Adam's moments of unmarked slots stand still), the tree takes float16(master), ``grad`` becomes +0; then
+    the bitmap is zero.  Unmarked slots are neither read nor written.  WRITES the tree, ordered as
+    ``update_data`` is; the host arrays of the tree object go stale."""
+    handle = tree.handle
+    if kind not in _abi.STEP_KINDS:
+        raise ValueError(f"kind names 'sgd' or 'adam', not {kind!r}")
+    bufs = []
+    for name, x in (("master", master), ("grad", grad), ("m", m), ("v", v)):
+        if x is not None:
+            bufs.append(_data_buf(tree, name, x, (F32,)))
+        elif name in ("master", "grad") or kind != "sgd":
+            raise ValueError(f"{name} is missing" + (" (kind='adam' needs both moments)" if name in ("m", "v") else ""))
+    s = _abi.VrStep()
+    for name, ptr in check(tree, bufs + [_touched_buf(tree, touched)]).ptr.items():
+        setattr(s, name, ptr)
+    s.kind = _abi.STEP_KINDS[kind]
+    s.lr, s.lr_sigma = float(lr), float(lr if lr_sigma is None else lr_sigma)
+    s.beta1, s.beta2, s.eps, s.step = float(betas[0]), float(betas[1]), float(eps), int(step)
+    _abi.check(_abi.lib().vr_tree_step(handle, C.byref(s), _stream_ptr(stream)))
