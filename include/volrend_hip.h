@@ -426,8 +426,15 @@ int vr_accumulate_weights(vr_tree_t tree, int n_frames, const VrCamera* cams,
  * summed over all rays of all frames, in binary32 (the running sum behind R_i in binary64) with float
  * atomic adds: THE ORDER OF THE SUM IS NOT DEFINED, so two runs may differ in the last bits.  This is the
  * library's one output that is not bit-reproducible; every other output stays bit-exact.
- * A ray that meets non-finite records or gradients leaves unspecified values in the elements it touches;
- * nothing faults, and elements no ray touches keep their bits.
+ * Non-finite values.  A ray is outside the formulas if a slot one of its hit samples falls into holds a
+ * non-finite value (any entry of the record, sigma included), if its grad_accum pixel holds one, or if its
+ * binary32 forward output -- out[0..3] or the transmittance T_{K+1} as the colour kernels compute them -- is
+ * itself non-finite, even when every record it meets is finite (a_i = inf from a large negative sigma under a
+ * negative sigma_thresh; s = 1 / 0 when stop_thresh >= 1 meets an a_K that rounds to 1).  Such a ray leaves
+ * unspecified values in every element of the slots its hit samples fall into, and only there: the call
+ * returns, nothing faults, every other ray's contribution to every other slot is what the formulas say, and
+ * elements no ray touches keep their bits.  Which samples are hits depends on sigma_i > sigma_thresh alone (a
+ * NaN sigma is never a hit, +inf is one), for these rays as for all others.
  * Contract: that of vr_accumulate_weights -- enqueue only, on a launch slot (vr_reserve of the same shape
  * covers it), <= VR_MAX_BATCH frames of one size and one set of intrinsics, step_size <= 0 / NaN refused,
  * the sample guard reports through vr_tree_status, n_frames == 0 uploads the file-order table and launches

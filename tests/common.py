@@ -287,12 +287,13 @@ EDGE_COEFF = [0x7E00, 0x7C00, 0xFC00, 0x7BFF, 0xFBFF] + [
 EDGE_RGBA = [0xB800, 0xC200, 0x3E00, 0x4700, 0x7BFF, 0x7C00, 0xFC00, 0x7E00]
 
 
-def apply_value_edges(tree, seed, frac=0.08):
+def apply_value_edges(tree, seed, frac=0.08, coeff=None, rgba_colours=None, sigmas=None):
     """Overwrites a seeded fraction ``frac`` of the leaf records of ``tree`` (occupied and empty
     alike) with special values: in each chosen record 1-3 colour entries from EDGE_COEFF / EDGE_RGBA
     (for SH / SG / ASG basis 0 of a channel half the time, whose basis value is the constant 0.2821)
     and, in half of them, sigma from EDGE_SIGMA.  SG / ASG lobes get special parameters too: lambda
-    NaN, inf, 0 and 1e30 in lobes 0-3 and a mu of length 2 in lobe 4.  Returns a new tree."""
+    NaN, inf, 0 and 1e30 in lobes 0-3 and a mu of length 2 in lobe 4.  ``coeff``, ``rgba_colours`` and
+    ``sigmas`` replace the three catalogues (binary16 bit patterns).  Returns a new tree."""
     import dataclasses
     rng = np.random.default_rng(seed)
     dd = tree.data_dim
@@ -301,14 +302,17 @@ def apply_value_edges(tree, seed, frac=0.08):
     pick = leaf[rng.random(leaf.size) < frac]
     rgba = tree.format_name == "RGBA"
     bd = max(tree.basis_dim, 1)
-    cat = np.array(EDGE_RGBA if rgba else EDGE_COEFF, np.uint16)
+    coeff = EDGE_COEFF if coeff is None else coeff
+    rgba_colours = EDGE_RGBA if rgba_colours is None else rgba_colours
+    sigmas = EDGE_SIGMA if sigmas is None else sigmas
+    cat = np.array(rgba_colours if rgba else coeff, np.uint16)
     for r in pick:
         for _ in range(int(rng.integers(1, 4))):
             ch = int(rng.integers(3))
             j = ch if rgba else ch * bd + (0 if rng.random() < 0.5 else int(rng.integers(bd)))
             data[r, j] = cat[rng.integers(cat.size)]
         if rng.random() < 0.5:
-            data[r, dd - 1] = EDGE_SIGMA[int(rng.integers(len(EDGE_SIGMA)))]
+            data[r, dd - 1] = sigmas[int(rng.integers(len(sigmas)))]
     extra = tree.extra
     if extra is not None:
         extra = extra.copy()
@@ -321,9 +325,10 @@ def apply_value_edges(tree, seed, frac=0.08):
     return dataclasses.replace(tree, data=data.view(np.float16).reshape(tree.data.shape), extra=extra)
 
 
-def value_edge_tree(fmt="SH", basis_dim=16, seed=0, depth=5, frac=0.08):
+def value_edge_tree(fmt="SH", basis_dim=16, seed=0, depth=5, frac=0.08, **catalogues):
     """A seeded small_scene with special values in a fraction of its leaf records (apply_value_edges)."""
-    return apply_value_edges(small_scene(depth=depth, basis_dim=basis_dim, fmt=fmt, seed=seed), seed + 1, frac)
+    return apply_value_edges(small_scene(depth=depth, basis_dim=basis_dim, fmt=fmt, seed=seed), seed + 1, frac,
+                             **catalogues)
 
 
 def axis_camera(size=63, focal=70.0, dist=4.0):

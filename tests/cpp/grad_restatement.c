@@ -20,8 +20,21 @@
  *                      that much (a light that decays to 1e-60 sticks at a subnormal), which no bound relative
  *                      to M covers; 2^-126 U does.  U also carries eight smallest subnormals per contribution
  *                      (SUBNORMAL_UNITS): a product that comes out below 2^-149 is zero in binary32.
+ *                      Two more magnitudes, for records whose sigmoid argument u is large (optional outputs):
+ *                      M_c is M with every colour-dependent factor of sample i, channel ch -- the c (1 + c) of
+ *                      the coefficient terms, the |g_ch c_ch| inside G_abs, R_abs and C^_abs -- multiplied by
+ *                      1 + A_{i,ch}, A_{i,ch} = sum_b |B_b| |k_{i,ch,b}| (0 for RGBA): the binary32 dot product
+ *                      u carries an absolute error of about 2^-24 A, which is the RELATIVE error of exp(-u)
+ *                      and so of 1 - c or c, whichever is small.  U_c is U with every colour factor replaced
+ *                      by 1 as well (the coefficient term 2 |g_ch s B_b|, the sigma term with |g_ch| for
+ *                      |g_ch c_ch|): binary32 gives c = 1 / (1 + inf) = 0 where binary64 gives 1e-48.
  *       grad_eval32    the same formulas in binary32, rays taken in a caller-given order and every
- *                      contribution added into a binary32 array as it comes.
+ *                      contribution added into a binary32 array as it comes.  -DGRAD_MUTANT=n (1..3) builds
+ *                      this entry point -- and only this one -- with one deliberate mistake, for the tests
+ *                      that show the error unit still sees it:
+ *                        1  dc formed without the (1 - c) factor
+ *                        2  R_i formed in binary32 as total minus running prefix
+ *                        3  the not-stopped tail g_3 T_{K+1} used for stopped rays
  *
  * Build: gcc -O2 -std=c11 -ffp-contract=off -mfma -fPIC -shared -I oracle (the oracle's flags).
  */
@@ -44,6 +57,10 @@
 /* A contribution is a chain of binary32 products; one whose result is subnormal carries an absolute error of half
  * the smallest subnormal, 2^-150.  Per contribution U gets 2^-20: 2^-126 * 2^-20 = eight smallest subnormals. */
 #define SUBNORMAL_UNITS 0x1p-20
+
+#ifndef GRAD_MUTANT
+#define GRAD_MUTANT 0
+#endif
 
 static inline float madd_strict(float a, float b, float c) { return a * b + c; }
 static inline float madd_fma(float a, float b, float c) { return fmaf(a, b, c); }
@@ -194,15 +211,29 @@ void grad_trace_slots(const GradTrace* tr, int64_t r, int64_t* out) {
     for (int64_t i = 0; i < ray->n; ++i) out[i] = tr->hits[ray->first + i].slot;
 }
 
-/* Colour of one sample in binary64; dc = d colour / d (record entry of basis function b) without B_b. */
-static void colour64(const GradTrace* tr, const GradRay* ray, const double* v, double* c, double* dc) {
+/* The slots of every ray's hits, ray after ray (out: the sum of grad_trace_rays' n_hits entries). */
+void grad_trace_all_slots(const GradTrace* tr, int64_t* out) {
+    for (int64_t r = 0; r < tr->n_rays; ++r) {
+        const GradRay* ray = tr->rays + r;
+        for (int64_t i = 0; i < ray->n; ++i) *out++ = tr->hits[ray->first + i].slot;
+    }
+}
+
+/* Colour of one sample in binary64; dc = d colour / d (record entry of basis function b) without B_b;
+ * amp = 1 + A, A = sum_b |B_b| |k_b| (the size of the terms of u; 1 for RGBA). */
+static void colour64(const GradTrace* tr, const GradRay* ray, const double* v, double* c, double* dc, double* amp) {
     for (int ch = 0; ch < 3; ++ch) {
         if (tr->n_basis == 0) {
             c[ch] = v[ch];
             dc[ch] = 1.0;
+            amp[ch] = 1.0;
         } else {
-            double u = 0.0;
-            for (int b = 0; b < tr->n_basis; ++b) u += (double)ray->basis[b] * v[ch * tr->basis_dim + b];
+            double u = 0.0, A = 0.0;
+            for (int b = 0; b < tr->n_basis; ++b) {
+                u += (double)ray->basis[b] * v[ch * tr->basis_dim + b];
+                A += fabs((double)ray->basis[b] * v[ch * tr->basis_dim + b]);
+            }
+            amp[ch] = 1.0 + A;
             c[ch] = 1.0 / (1.0 + exp(-u));
             dc[ch] = c[ch] * (1.0 - c[ch]);
         }
@@ -231,8 +262,8 @@ int grad_eval64(const GradTrace* tr, const double* data, const double* g_all, do
             const double* v = data + h[i].slot * dd;
             const double a = exp(-(double)h[i].delta * v[dd - 1]);
             const double w = T - T * a;
-            double c[3], dc[3];
-            colour64(tr, ray, v, c, dc);
+            double c[3], dc[3], amp[3];
+            colour64(tr, ray, v, c, dc, amp);
             for (int ch = 0; ch < 3; ++ch) C[ch] += w * c[ch];
             if (g) {
                 Chat += w * (g[0] * c[0] + g[1] * c[1] + g[2] * c[2]);
@@ -265,8 +296,8 @@ int grad_eval64(const GradTrace* tr, const double* data, const double* g_all, do
             const double* v = data + h[i].slot * dd;
             const double a = exp(-(double)h[i].delta * v[dd - 1]);
             const double w = T - T * a;
-            double c[3], dc[3];
-            colour64(tr, ray, v, c, dc);
+            double c[3], dc[3], amp[3];
+            colour64(tr, ray, v, c, dc, amp);
             const double G_abs = fabs(g[0] * c[0]) + fabs(g[1] * c[1]) + fabs(g[2] * c[2]);
             suf[3 * i + 0] = w * (g[0] * c[0] + g[1] * c[1] + g[2] * c[2]);
             suf[3 * i + 1] = (T + T * a) * G_abs;
@@ -289,8 +320,8 @@ int grad_eval64(const GradTrace* tr, const double* data, const double* g_all, do
             const double delta = (double)h[i].delta;
             const double a = exp(-delta * v[dd - 1]);
             const double w = T - T * a, Tn = T * a;
-            double c[3], dc[3];
-            colour64(tr, ray, v, c, dc);
+            double c[3], dc[3], amp[3];
+            colour64(tr, ray, v, c, dc, amp);
             const double G = g[0] * c[0] + g[1] * c[1] + g[2] * c[2];
             const double G_abs = fabs(g[0] * c[0]) + fabs(g[1] * c[1]) + fabs(g[2] * c[2]);
             const double R = suf[3 * i + 0], R_abs = suf[3 * i + 1], R_one = suf[3 * i + 2];
@@ -317,6 +348,85 @@ int grad_eval64(const GradTrace* tr, const double* data, const double* g_all, do
                 grad[base + dd - 1] += delta * (s * (Tn * G - R) - s * s * Tend * Chat);
                 mag[base + dd - 1] += fabs(delta) * (fabs(s) * (fabs(Tn) * G_abs + R_abs) + s * s * fabs(Tend) * Chat_abs);
                 under[base + dd - 1] += fabs(delta) * (fabs(s) * (G_abs + R_one) + s * s * Gsum_abs) + SUBNORMAL_UNITS;
+            }
+            T = Tn;
+        }
+    }
+    free(suf);
+    return 0;
+}
+
+/*
+ * The edge-aware magnitudes M_c and U_c (the comment at the top) of the same record, ADDED INTO mag_c and under_c
+ * ([n_slots * data_dim]).  A sibling of grad_eval64 so that grad, M and U keep the bits they had.
+ */
+int grad_edge64(const GradTrace* tr, const double* data, const double* g_all, double* mag_c, double* under_c) {
+    if (!tr || !data || !g_all || !mag_c || !under_c) return 1;
+    const int dd = tr->data_dim, nb = tr->n_basis, bd = tr->basis_dim;
+    double* suf = NULL; /* per hit, behind it: the sums of (T_j + T_{j+1}) G_c,j and of 2 G_one */
+    int64_t suf_cap = 0;
+    for (int64_t r = 0; r < tr->n_rays; ++r) {
+        const GradRay* ray = tr->rays + r;
+        const GradHit* h = tr->hits + ray->first;
+        const int64_t K = ray->n;
+        const double* g = g_all + 4 * (int64_t)ray->pixel;
+        const double G_one = fabs(g[0]) + fabs(g[1]) + fabs(g[2]);
+        if (K > suf_cap) {
+            free(suf);
+            suf_cap = 2 * K;
+            suf = (double*)malloc((size_t)suf_cap * 2 * sizeof(double));
+            if (!suf) return 1;
+        }
+        double T = 1.0;
+        for (int64_t i = 0; i < K; ++i) {
+            const double* v = data + h[i].slot * dd;
+            const double a = exp(-(double)h[i].delta * v[dd - 1]);
+            double c[3], dc[3], amp[3];
+            colour64(tr, ray, v, c, dc, amp);
+            const double G_c = fabs(g[0] * c[0]) * amp[0] + fabs(g[1] * c[1]) * amp[1] + fabs(g[2] * c[2]) * amp[2];
+            suf[2 * i + 0] = (T + T * a) * G_c;
+            suf[2 * i + 1] = 2.0 * G_one;
+            T *= a;
+        }
+        const double Tend = T;
+        const double s = ray->stopped ? 1.0 / (1.0 - Tend) : 1.0;
+        double acc[2] = {0, 0};
+        for (int64_t i = K - 1; i >= 0; --i)
+            for (int q = 0; q < 2; ++q) {
+                const double term = suf[2 * i + q];
+                suf[2 * i + q] = acc[q];
+                acc[q] += term;
+            }
+        const double Chat_c = acc[0], Gsum_one = acc[1];
+        T = 1.0;
+        for (int64_t i = 0; i < K; ++i) {
+            const int64_t base = h[i].slot * dd;
+            const double* v = data + base;
+            const double delta = (double)h[i].delta;
+            const double a = exp(-delta * v[dd - 1]);
+            const double Tn = T * a;
+            double c[3], dc[3], amp[3];
+            colour64(tr, ray, v, c, dc, amp);
+            const double G_c = fabs(g[0] * c[0]) * amp[0] + fabs(g[1] * c[1]) * amp[1] + fabs(g[2] * c[2]) * amp[2];
+            const double R_c = suf[2 * i + 0], R_one = suf[2 * i + 1];
+            for (int ch = 0; ch < 3; ++ch) {
+                if (nb == 0) {
+                    mag_c[base + ch] += fabs(g[ch] * s) * (T + Tn);
+                    under_c[base + ch] += 2.0 * fabs(g[ch] * s) + SUBNORMAL_UNITS;
+                } else {
+                    for (int b = 0; b < nb; ++b) {
+                        const double gsb = fabs(g[ch] * s * (double)ray->basis[b]);
+                        mag_c[base + ch * bd + b] += gsb * c[ch] * (1.0 + c[ch]) * amp[ch] * (T + Tn);
+                        under_c[base + ch * bd + b] += 2.0 * gsb + SUBNORMAL_UNITS;
+                    }
+                }
+            }
+            if (!ray->stopped) {
+                mag_c[base + dd - 1] += fabs(delta) * (fabs(Tn) * G_c + R_c + fabs(g[3] * Tend));
+                under_c[base + dd - 1] += fabs(delta) * (G_one + R_one + fabs(g[3])) + SUBNORMAL_UNITS;
+            } else {
+                mag_c[base + dd - 1] += fabs(delta) * (fabs(s) * (fabs(Tn) * G_c + R_c) + s * s * fabs(Tend) * Chat_c);
+                under_c[base + dd - 1] += fabs(delta) * (fabs(s) * (G_one + R_one) + s * s * Gsum_one) + SUBNORMAL_UNITS;
             }
             T = Tn;
         }
@@ -362,7 +472,11 @@ int grad_eval32(const GradTrace* tr, const float* data, const float* g_all, cons
                     float u = 0.f;
                     for (int b = 0; b < nb; ++b) u += ray->basis[b] * v[ch * bd + b];
                     c[ch] = 1.f / (1.f + expf(-u));
+#if GRAD_MUTANT == 1
+                    e[4 + ch] = c[ch];
+#else
                     e[4 + ch] = c[ch] * (1.f - c[ch]);
+#endif
                 }
             }
             e[0] = T * (1.f - a);
@@ -377,6 +491,15 @@ int grad_eval32(const GradTrace* tr, const float* data, const float* g_all, cons
             R += buf[7 * i + 0] * buf[7 * i + 2];
         }
         const float Chat = R;
+#if GRAD_MUTANT == 2
+        {
+            float prefix = 0.f;
+            for (int64_t i = 0; i < K; ++i) {
+                prefix += buf[7 * i + 0] * buf[7 * i + 2];
+                buf[7 * i + 3] = Chat - prefix;
+            }
+        }
+#endif
         const float s = ray->stopped ? 1.f / (1.f - Tend) : 1.f;
         for (int64_t i = 0; i < K; ++i) {
             const int64_t base = h[i].slot * dd;
@@ -390,7 +513,11 @@ int grad_eval32(const GradTrace* tr, const float* data, const float* g_all, cons
                 }
             }
             if (!ray->stopped) grad[base + dd - 1] += h[i].delta * (e[1] * e[2] - e[3] + g[3] * Tend);
+#if GRAD_MUTANT == 3
+            else grad[base + dd - 1] += h[i].delta * (s * (e[1] * e[2] - e[3]) + g[3] * Tend);
+#else
             else grad[base + dd - 1] += h[i].delta * (s * (e[1] * e[2] - e[3]) - s * s * Tend * Chat);
+#endif
         }
     }
     free(buf);

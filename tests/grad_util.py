@@ -20,6 +20,7 @@ from tests.common import ob
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "grad_restatement.c")
 _lib = None
+_mutants = {}
 
 EPS32 = 2.0 ** -24
 TINY32 = 2.0 ** -126
@@ -34,29 +35,44 @@ K = 4.0 * K32
 OPTION_SETS = au.OPTION_SETS
 
 
-def lib():
+def lib(mutant=0):
+    """The restatement; mutant = 1..3 builds it with -DGRAD_MUTANT (one deliberate mistake in grad_eval32, see the
+    source), for the tests that show the error unit sees the mistake."""
     global _lib
+    if mutant:
+        if mutant not in _mutants:
+            _mutants[mutant] = _build(mutant)
+        return _mutants[mutant]
     if _lib is None:
-        td = tempfile.mkdtemp(prefix="vr_grad_restate_")
-        atexit.register(shutil.rmtree, td, ignore_errors=True)
-        so = os.path.join(td, "libgrad_restatement.so")
-        subprocess.check_call(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-mfma", "-fPIC", "-shared",
-                               "-Wno-unused-function", "-I", os.path.join(ROOT, "oracle"), SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.grad_trace_frame.restype = C.c_void_p
-        L.grad_trace_frame.argtypes = [C.POINTER(ob.OrTree), C.POINTER(ob.OrCamera), C.POINTER(ob.OrOptions), C.c_int]
-        L.grad_trace_free.restype = None
-        L.grad_trace_free.argtypes = [C.c_void_p]
-        L.grad_trace_rays.restype = None
-        L.grad_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.grad_trace_slots.restype = None
-        L.grad_trace_slots.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
-        L.grad_eval64.restype = C.c_int
-        L.grad_eval64.argtypes = [C.c_void_p] + [C.c_void_p] * 7
-        L.grad_eval32.restype = C.c_int
-        L.grad_eval32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        _lib = L
+        _lib = _build(0)
     return _lib
+
+
+def _build(mutant):
+    td = tempfile.mkdtemp(prefix="vr_grad_restate_")
+    atexit.register(shutil.rmtree, td, ignore_errors=True)
+    so = os.path.join(td, "libgrad_restatement.so")
+    subprocess.check_call(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-mfma", "-fPIC", "-shared",
+                           "-Wno-unused-function", f"-DGRAD_MUTANT={mutant}", "-I", os.path.join(ROOT, "oracle"),
+                           SRC, "-o", so, "-lm"])
+    L = C.CDLL(so)
+    L.grad_trace_frame.restype = C.c_void_p
+    L.grad_trace_frame.argtypes = [C.POINTER(ob.OrTree), C.POINTER(ob.OrCamera), C.POINTER(ob.OrOptions), C.c_int]
+    L.grad_trace_free.restype = None
+    L.grad_trace_free.argtypes = [C.c_void_p]
+    L.grad_trace_rays.restype = None
+    L.grad_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.grad_trace_slots.restype = None
+    L.grad_trace_slots.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.grad_trace_all_slots.restype = None
+    L.grad_trace_all_slots.argtypes = [C.c_void_p, C.c_void_p]
+    L.grad_eval64.restype = C.c_int
+    L.grad_eval64.argtypes = [C.c_void_p] + [C.c_void_p] * 7
+    L.grad_edge64.restype = C.c_int
+    L.grad_edge64.argtypes = [C.c_void_p] * 5
+    L.grad_eval32.restype = C.c_int
+    L.grad_eval32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    return L
 
 
 def _p(a):
@@ -108,15 +124,29 @@ class Trace:
         assert lib().grad_eval64(self.ptr, _p(data64), _p(g64), None, None, _p(grad), _p(mag), _p(under)) == 0
         return grad, mag, under
 
+    def all_slots(self):
+        """-> (slot of every hit, ray after ray; the ray of every hit), int64."""
+        out = np.zeros(int(self.n_hits.sum()), np.int64)
+        lib().grad_trace_all_slots(self.ptr, _p(out))
+        return out, np.repeat(np.arange(self.n_hits.size), self.n_hits)
+
+    def edge64(self, data64, g64, mag_c, under_c):
+        """Adds the frame's edge-aware magnitudes M_c and U_c into mag_c / under_c (float64, the shape of data)."""
+        g64 = np.ascontiguousarray(g64, np.float64)
+        assert g64.shape == (self.h, self.w, 4) and data64.dtype == np.float64 and data64.flags.c_contiguous
+        assert mag_c.shape == self.shape and under_c.shape == self.shape
+        assert lib().grad_edge64(self.ptr, _p(data64), _p(g64), _p(mag_c), _p(under_c)) == 0
+        return mag_c, under_c
+
     def loss64(self, data64, g64):
         """sum(g * out): the scalar whose derivative backward64 claims to be."""
         return float((self.forward64(data64)[0] * g64).sum())
 
-    def backward32(self, data32, g32, order, grad32):
+    def backward32(self, data32, g32, order, grad32, mutant=0):
         g32 = np.ascontiguousarray(g32, np.float32)
         order = np.ascontiguousarray(order, np.int64)
         assert data32.dtype == np.float32 and grad32.dtype == np.float32 and grad32.shape == self.shape
-        assert lib().grad_eval32(self.ptr, _p(data32), _p(g32), _p(order), order.size, _p(grad32)) == 0
+        assert lib(mutant).grad_eval32(self.ptr, _p(data32), _p(g32), _p(order), order.size, _p(grad32)) == 0
         return grad32
 
 
@@ -224,3 +254,155 @@ def worst_ratio(got, ref):
     pos = mag > 0
     ratio = float((diff[pos] / unit(ref)[pos]).max()) if pos.any() else 0.0
     return ratio, bool((diff[~pos] == 0).all())
+
+
+# ---- the value domain: saturated colours, edge densities, non-finite rays -----------------------------------------
+# unit() cannot judge a record whose sigmoid argument u is tens of units: the binary32 dot product u carries an
+# absolute error of ~2^-24 sum_b |B_b k_b|, which is the relative error of exp(-u), and binary32 flushes a colour to
+# 0 where binary64 keeps 1e-48.  unit_edge() covers both (M_c, U_c: tests/cpp/grad_restatement.c).
+# The edge summation constant (tests/test_grad_restatement.py::test_edge_summation_constant measures it): the
+# largest |binary32 - binary64| / unit_edge() of the restatement's binary32 entry point over the clean elements of
+# every edge case below, both catalogues, in scanline and in shuffled ray order: 28.996 (rgba_never_stop, finite
+# catalogue; the SH cases come to 1.3-3.8 with the default options and to 16.4 with stop_thresh = 0), rounded up.
+# K_EDGE = 4 * K32_EDGE by the rule of K.  If the GPU exceeds K_EDGE, that is a finding about the kernel: K_EDGE
+# does not move.
+K32_EDGE = 29.0
+K_EDGE = 4.0 * K32_EDGE
+
+
+def _finite_bits(cat):
+    return [b for b in cat if (b & 0x7C00) != 0x7C00]
+
+
+def _half_bits(v):
+    return int(np.float16(v).view(np.uint16))
+
+
+# finite: the three catalogues of tests/common.py without NaN and +-inf, plus coefficients +-40 (|u| ~ 11 through
+# basis 0) and +-200; full: the catalogues as they are (and grad_accum non-finite in about 1 % of the pixels)
+CATALOGUES = {
+    "finite": dict(coeff=_finite_bits(common.EDGE_COEFF) + [_half_bits(v) for v in (40, -40, 200, -200)],
+                   rgba_colours=_finite_bits(common.EDGE_RGBA), sigmas=_finite_bits(common.EDGE_SIGMA)),
+    "full": {},
+}
+
+# name -> dict(fmt, basis_dim, opt, fp_modes, frac (finite, full): the share of the leaf records that get special
+# values, chosen per case so that the cap of tests/test_grad_restatement.py::test_edge_cap holds; camera "orbit" |
+# "axis"; tree "edge" (a depth-`depth` value_edge_tree) | "n4" (the generic descent))
+EDGE_CASES = {
+    "sh16": dict(fmt="SH", basis_dim=16, opt={}, fp_modes=(0, 1), frac=(0.08, 0.08)),
+    "sh16_no_stop": dict(fmt="SH", basis_dim=16, opt=dict(stop_thresh=0.0), fp_modes=(0, 1), frac=(0.08, 0.02)),
+    "sh16_stop_ge_1": dict(fmt="SH", basis_dim=16, opt=dict(stop_thresh=1.5), fp_modes=(0, 1), frac=(0.08, 0.08)),
+    "sh25": dict(fmt="SH", basis_dim=25, opt={}, fp_modes=(0,), frac=(0.08, 0.08)),
+    "sh9_thresh_edge": dict(fmt="SH", basis_dim=9, opt=dict(sigma_thresh=0.5), fp_modes=(0,), frac=(0.08, 0.08)),
+    "sh4_negative_thresh": dict(fmt="SH", basis_dim=4, opt=dict(sigma_thresh=-1.0), fp_modes=(0,), frac=(0.08, 0.04)),
+    "basis1": dict(fmt="SH", basis_dim=3, opt={}, fp_modes=(0,), frac=(0.08, 0.08)),
+    "rgba": dict(fmt="RGBA", basis_dim=-1, opt={}, fp_modes=(0,), frac=(0.08, 0.08)),
+    "rgba_never_stop": dict(fmt="RGBA", basis_dim=-1, opt=dict(stop_thresh=-0.5), fp_modes=(0,), frac=(0.08, 0.01)),
+    "rgba_stop_ge_1": dict(fmt="RGBA", basis_dim=-1, opt=dict(stop_thresh=1.0), fp_modes=(0,), frac=(0.08, 0.08),
+                           camera="axis"),
+    "n4": dict(tree="n4", opt={}, fp_modes=(0,), frac=(0.08, 0.08), size=40),
+    "blocked": dict(fmt="SH", basis_dim=4, depth=7, opt={}, fp_modes=(0,), frac=(0.08, 0.08), blocked=True),
+}
+EDGE_RUNS = [(n, fp) for n, c in EDGE_CASES.items() for fp in c["fp_modes"]]
+EDGE_IDS = [f"{n}-fp{fp}" for n, fp in EDGE_RUNS]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_tree(name, catalogue):
+    c = EDGE_CASES[name]
+    seed = 7100 + sum(map(ord, name))
+    frac = c["frac"][0 if catalogue == "finite" else 1]
+    if c.get("tree") == "n4":
+        return common.apply_value_edges(common.random_tree_general_n(), seed + 1, frac, **CATALOGUES[catalogue])
+    return common.value_edge_tree(c["fmt"], c["basis_dim"], seed=seed, depth=c.get("depth", 5), frac=frac,
+                                  **CATALOGUES[catalogue])
+
+
+def edge_view(name):
+    """-> (transform, w, h, focal): one pose, 56 x 56 (57 x 57 for the axis camera, whose centre row and column
+    need an odd size; 40 x 40 for the generic descent)."""
+    c = EDGE_CASES[name]
+    size = c.get("size", 56)
+    if c.get("camera") == "axis":
+        return common.axis_camera(size | 1)
+    return common.camera_for(pose_idx=(7100 + sum(map(ord, name))) % 8, size=size)
+
+
+def edge_upstream(catalogue, h, w, seed=7):
+    """grad_accum [1, h, w, 4]: upstream("normal"); in the full catalogue about 1 % of the pixels hold NaN, +inf or
+    -inf in one of their four entries."""
+    g = upstream("normal", 1, h, w, seed=seed).copy()
+    if catalogue == "full":
+        rng = np.random.default_rng(seed + 1)
+        ys, xs = np.nonzero(rng.random((h, w)) < 0.01)
+        for y, x in zip(ys, xs):
+            g[0, y, x, int(rng.integers(4))] = (np.nan, np.inf, -np.inf)[int(rng.integers(3))]
+    return g
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(name, catalogue, fp_mode):
+    """The float64 gradient of one edge case, its magnitudes and its clean mask, once per session and read-only.
+    -> the dict of reference() plus mag_c, under_c and, per slot (bool [n_slots]): hit (a hit sample fell into it),
+    dirty (a dirty ray hit it), clean (hit and not dirty).  A ray is dirty if a slot it hits holds a non-finite
+    value, if its grad_accum pixel is non-finite, or if the oracle's binary32 forward of its pixel (accumulators,
+    transmittance) is non-finite -- finite records that overflow in binary32: att = inf from sigma = -65504,
+    s = 1 / 0 when stop_thresh >= 1 meets an att that rounds to 1."""
+    c = EDGE_CASES[name]
+    tree = edge_tree(name, catalogue)
+    tr, w, h, f = edge_view(name)
+    kw = dict(c["opt"])
+    g = edge_upstream(catalogue, h, w)
+    d64 = data64_of(tree)
+    grad, mag, under, mag_c, under_c = (np.zeros(d64.shape, np.float64) for _ in range(5))
+    t = Trace(tree, tr, w, h, f, fp_mode, **kw)
+    g64 = g[0].astype(np.float64)
+    t.backward64(d64, g64, grad, mag, under)
+    t.edge64(d64, g64, mag_c, under_c)
+    # the clean mask
+    dd = tree.data_dim
+    n_slots = d64.size // dd
+    slots, ray_of_hit = t.all_slots()
+    bad_record = ~np.isfinite(d64.reshape(n_slots, dd)).all(1)
+    _, acc, _ = common.oracle_frame(tree, tr, w, h, f, fp_mode, **kw)
+    _, T, _, _ = au.restate(tree, tr, w, h, f, fp_mode, **kw)
+    dirty_ray = ~np.isfinite(g[0]).all(-1).reshape(-1) | ~np.isfinite(acc).all(-1).reshape(-1) | \
+        ~np.isfinite(T).reshape(-1)
+    dirty_ray[ray_of_hit[bad_record[slots]]] = True
+    hit, dirty = np.zeros(n_slots, bool), np.zeros(n_slots, bool)
+    hit[slots] = True
+    dirty[slots[dirty_ray[ray_of_hit]]] = True
+    clean = hit & ~dirty
+    for a in (g, grad, mag, under, mag_c, under_c, hit, dirty, clean):
+        a.setflags(write=False)
+    return dict(tree=tree, ndc=None, trs=[tr], w=w, h=h, f=f, g=g, grad=grad, mag=mag, under=under, mag_c=mag_c,
+                under_c=under_c, traces=[t], opt=kw, hit=hit, dirty=dirty, clean=clean,
+                dirty_rays=int((dirty_ray & (t.n_hits > 0)).sum()), blocked=bool(c.get("blocked")))
+
+
+def unit_edge(ref):
+    """The edge-aware error unit per element: 2^-24 M_c + 2^-126 U_c."""
+    return EPS32 * ref["mag_c"] + TINY32 * ref["under_c"]
+
+
+def clean_elements(ref):
+    """bool, the shape of data: the elements of the clean slots."""
+    dd = ref["grad"].shape[-1]
+    return np.broadcast_to(ref["clean"][:, None], (ref["clean"].size, dd)).reshape(ref["grad"].shape)
+
+
+def worst_edge_ratio(got, ref, start=None, slack=None):
+    """max (|got - start - grad| - slack) / unit_edge over the clean elements with M > 0, their number, and whether
+    the clean elements with M == 0 hold the bits of `start` (zeros when None)."""
+    start = np.zeros(ref["grad"].shape, np.float32) if start is None else start
+    clean = clean_elements(ref)
+    pos = clean & (np.nan_to_num(ref["mag"], nan=0.0) > 0)
+    with np.errstate(invalid="ignore"):
+        diff = np.abs(np.asarray(got, np.float64) - start.astype(np.float64) - ref["grad"])
+        if slack is not None:
+            diff = np.maximum(diff - slack, 0.0)
+    ratio = float((diff[pos] / unit_edge(ref)[pos]).max()) if pos.any() else 0.0
+    zero = clean & ~pos
+    same = np.asarray(got, np.float32).view(np.uint32)[zero] == start.view(np.uint32)[zero]
+    return ratio, int(pos.sum()), bool(same.all())

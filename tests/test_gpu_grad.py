@@ -3,7 +3,11 @@ tied to the oracle and to central differences by tests/test_grad_restatement.py)
 
 Per element of grad_data: |gpu - f64| <= K * unit, unit = 2^-24 M (+ 2^-126 U where binary32 underflows:
 tests/grad_util.py unit()), K = 4 * K32 = 148 -- no element is left out.  The buffers start from a sentinel
-pattern, so an element no hit sample touches must still hold the caller's bits."""
+pattern, so an element no hit sample touches must still hold the caller's bits.
+
+The value domain (section 8): saturated colours, edge densities and non-finite records and gradients, judged
+with the edge-aware unit (tests/grad_util.py unit_edge(), K_EDGE = 4 * K32_EDGE = 116) on the clean elements --
+those of the slots that no ray outside the formulas hits."""
 import numpy as np
 import pytest
 
@@ -223,6 +227,76 @@ def test_fog_below_the_threshold_and_zero_gradient(torch_cuda):
 
 def start_for(ref):
     return sentinel(ref["grad"].shape).copy()
+
+
+# ---- 8. the value domain ---------------------------------------------------------------------------------
+def upload_edge(ref):
+    return upload(ref, "blocked" if ref["blocked"] else None)
+
+
+def assert_edge_parity(got, ref, start=None, what=""):
+    """An edge case of tests/grad_util.py: clean elements with M > 0 within K_EDGE * unit_edge (plus the slack of
+    assert_parity for a buffer that starts from `start`), clean elements with M == 0 and every slot no ray hits
+    -- interior slots included -- bit-identical to `start`.  Dirty slots are not looked at."""
+    start = np.zeros(ref["grad"].shape, np.float32) if start is None else start
+    with np.errstate(invalid="ignore"):
+        slack = ref["under"] * 2.0 ** 20 * gu.EPS32 * np.abs(start.astype(np.float64))
+    worst, n, zeros_same = gu.worst_edge_ratio(got, ref, start, slack)
+    print(f"{what}: worst |gpu - f64| / unit_edge = {worst:.3f} of {gu.K_EDGE} over {n} clean elements; "
+          f"{int(ref['dirty'].sum())} of {int(ref['hit'].sum())} hit slots dirty")
+    assert n >= 200, "the case shows nothing"
+    assert worst <= gu.K_EDGE, what
+    assert zeros_same, f"{what}: a clean element with M == 0 was written"
+    dd = ref["grad"].shape[-1]
+    same = (got.view(np.uint32) == start.view(np.uint32)).reshape(-1, dd)
+    assert same[~ref["hit"]].all(), f"{what}: {int((~same[~ref['hit']]).any(1).sum())} slots no ray hits were written"
+    interior = np.asarray(ref["tree"].child).reshape(-1) != 0
+    assert interior.any() and not ref["hit"][interior].any()
+    return worst
+
+
+def assert_contained(got, ref, start, what=""):
+    """assert_edge_parity, and the case shows something: a dirty slot holds a non-finite value afterwards."""
+    assert_edge_parity(got, ref, start, what)
+    dd = ref["grad"].shape[-1]
+    assert ref["dirty"].any() and not np.isfinite(got.reshape(-1, dd)[ref["dirty"]]).all(), \
+        f"{what}: no dirty slot holds a non-finite value"
+
+
+@pytest.mark.parametrize("name,fp_mode", gu.EDGE_RUNS, ids=gu.EDGE_IDS)
+def test_finite_edge_values_match_the_float64_formulas(torch_cuda, name, fp_mode):
+    """Saturated colours and edge densities, all finite (the finite catalogue of tests/grad_util.py), into a
+    zeroed buffer."""
+    torch = torch_cuda
+    ref = gu.edge_reference(name, "finite", fp_mode)
+    t = upload_edge(ref)
+    try:
+        got = backward(torch, t, ref, fp_mode)
+        torch.cuda.synchronize()
+        assert t.status() == 0
+        got = got.cpu().numpy()
+    finally:
+        t.free_device()
+    assert_edge_parity(got, ref, what=f"finite {name} fp{fp_mode}")
+
+
+@pytest.mark.parametrize("name,fp_mode", gu.EDGE_RUNS, ids=gu.EDGE_IDS)
+def test_non_finite_rays_are_contained(torch_cuda, name, fp_mode):
+    """NaN and +-inf in records and in grad_accum (the full catalogue), into the sentinel: the call returns, a ray
+    that meets none of them and whose binary32 forward is finite leaves what the formulas say, and what no ray
+    hits keeps its bits."""
+    torch = torch_cuda
+    ref = gu.edge_reference(name, "full", fp_mode)
+    start = sentinel(ref["grad"].shape)
+    t = upload_edge(ref)
+    try:
+        got = backward(torch, t, ref, fp_mode, grad_data=torch.from_numpy(start.copy()).cuda())
+        torch.cuda.synchronize()
+        assert t.status() == 0
+        got = got.cpu().numpy()
+    finally:
+        t.free_device()
+    assert_contained(got, ref, start, what=f"full {name} fp{fp_mode}")
 
 
 # ---- 9. the sample guard --------------------------------------------------------------------------------

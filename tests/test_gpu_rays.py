@@ -19,7 +19,7 @@ from tests import common
 from tests import grad_util as gu
 from tests import rays_util as ru
 from tests import weights_util as wu
-from tests.test_gpu_grad import assert_parity, sentinel
+from tests.test_gpu_grad import assert_contained, assert_parity, sentinel, upload_edge
 from tests.test_gpu_weights import SENT_W, expected
 
 pytestmark = pytest.mark.gpu
@@ -279,6 +279,26 @@ def test_backward_of_shuffled_camera_lists(torch_cuda, name, size, n, optset, gk
         t.free_device()
     assert (ref["mag"] > 0).sum() > 200, "the case shows nothing"
     assert_parity(got, ref, start=start, what=f"rays {name} {optset} {gkind}")
+
+
+@pytest.mark.parametrize("name", ["sh16", "sh4_negative_thresh", "rgba"])
+def test_backward_of_shuffled_lists_contains_non_finite_rays(torch_cuda, name):
+    """The full-catalogue edge cases of tests/grad_util.py as shuffled lists: dirty and clean rays share a wave,
+    and for SH4 and RGBA one packed scatter instruction.  The assertions of
+    tests/test_gpu_grad.py::test_non_finite_rays_are_contained."""
+    torch = torch_cuda
+    ref = gu.edge_reference(name, "full", 0)
+    idx = np.random.default_rng(9).permutation(ref["w"] * ref["h"])
+    start = sentinel(ref["grad"].shape)
+    t = upload_edge(ref)
+    try:
+        got = backward_list(torch, t, ref, 0, idx, start=start)
+        torch.cuda.synchronize()
+        assert t.status() == 0
+        got = got.cpu().numpy()
+    finally:
+        t.free_device()
+    assert_contained(got, ref, start, what=f"rays full {name}")
 
 
 def fma_reference(name):

@@ -82,7 +82,21 @@ def marked_rays(torch, t, name, fp_mode=0, touched=None, grad_data=None):
 
 
 # ---- 1. the marks are the hit set --------------------------------------------------------------------------------
-MARK_CASES = [("sh16", 0), ("sh16", 1), ("sh25", 0), ("sh9_near", 0), ("rgba", 0), ("basis1", 0), ("n3", 0), ("chain", 0)]
+# (edge_*: the full-catalogue value-domain trees of tests/grad_util.py -- NaN and +-inf in records.  A mark depends
+# on sigma > sigma_thresh alone: NaN sigma never marks, +inf sigma does, dirty or clean makes no difference.)
+MARK_CASES = [("sh16", 0), ("sh16", 1), ("sh25", 0), ("sh9_near", 0), ("rgba", 0), ("basis1", 0), ("n3", 0), ("chain", 0),
+              ("edge_sh16", 0), ("edge_rgba", 0)]
+
+
+def cpu_hit_set(name):
+    """The slots with a hit sample in the scene's two poses, marched by the restatement (strict model), and the
+    float32 sigma of every slot."""
+    c = uu.case(name)
+    tree = c["tree"]
+    hit = np.zeros(n_slots(tree), bool)
+    for tr in c["trs"]:
+        hit[gu.Trace(tree, tr, c["w"], c["h"], c["f"], 0).all_slots()[0]] = True
+    return hit, np.asarray(tree.data, np.float32).reshape(-1, tree.data_dim)[:, -1]
 
 
 @pytest.mark.parametrize("name,fp_mode", MARK_CASES, ids=[f"{n}-fp{f}" for n, f in MARK_CASES])
@@ -92,7 +106,8 @@ def test_marks_are_the_hit_set(torch_cuda, name, fp_mode):
     c = uu.case(name)
     tree = c["tree"]
     o, d, g = rays_of(name)
-    ref = reference(name, fp_mode)
+    edge = name.startswith("edge_")
+    ref = None if edge else reference(name, fp_mode)     # (the gradient of the edge trees: tests/test_gpu_grad.py)
     slots = n_slots(tree)
     # bits set beforehand, on slots of internal nodes (no sample ever falls into one): the call ORs
     interior = np.flatnonzero(np.asarray(tree.child).reshape(-1) != 0)
@@ -130,6 +145,13 @@ def test_marks_are_the_hit_set(torch_cuda, name, fp_mode):
     for what, gd, mk in (("rays", grad, marks), ("frames", grad_f, marks_f)):
         touched_elems = (gd.reshape(-1, dd) != 0).any(1)
         assert not (touched_elems & ~mk).any(), f"{what}: a non-zero gradient in an unmarked slot"
+    if edge:
+        cpu_hit, sigma = cpu_hit_set(name)
+        assert np.array_equal(marks_f, cpu_hit), f"{int((marks_f != cpu_hit).sum())} marks differ from the hit set"
+        assert np.isnan(sigma).any() and not marks_f[np.isnan(sigma)].any(), "a NaN sigma was marked"
+        assert marks_f[sigma == np.inf].any(), "no +inf sigma was marked: the case shows nothing"
+        assert not np.isfinite(grad_f).all(), "no non-finite record was met: the case shows nothing"
+        return
     assert_parity(grad_f, ref, what=f"marked frames {name} fp{fp_mode}")
     if fp_mode == 0:
         assert_parity(grad, ref, what=f"marked rays {name}")

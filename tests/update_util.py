@@ -18,7 +18,7 @@ def case(name):
     """-> dict(tree, ndc, trs (two poses), w, h, f, tuning): the grad tests' small scenes, the 28-level chain (float
     descent), `mixed` -- depth 5 under top_levels = 2, brick_levels = 1, so that most leaves lie below top grid and
     bricks and their sigma exists in node words only -- and `n3`, whose file-side runs (27 * 13 elements) are not
-    whole 16-byte pieces."""
+    whole 16-byte pieces.  `edge_<case>`: the full-catalogue tree of grad_util.EDGE_CASES[case]."""
     tuning = None
     if name == "chain":
         tree, target = common.deep_chain_tree_n2()
@@ -29,6 +29,8 @@ def case(name):
         tree, ndc, tuning = common.small_scene(depth=5, basis_dim=4, seed=77), None, dict(top_levels=2, brick_levels=1)
     elif name == "n3":
         tree, ndc = common.random_tree_general_n(N=3, depth=3, basis_dim=4, seed=5), None
+    elif name.startswith("edge_"):   # the full-catalogue value-domain trees of tests/grad_util.py: NaN, +-inf
+        tree, ndc = gu.edge_tree(name[5:], "full"), None
     else:
         tree, _, ndc = gu.tree_of(name)
         if name == "blocked":
