@@ -553,6 +553,13 @@ int vr_tree_set_tuning(vr_tree_t tree, const char* key, int value);
  * [4] distinct leaves summed over shade rounds [5] retire rounds [6] rays retired in them [7] scheduler iterations.
  * Synchronous (copies from the device); reset != 0 clears them. */
 int vr_sched_stats(vr_tree_t tree, uint64_t out[8], int reset);
+/* Block cull (tuning key "block_cull", default 1): in colour and AOV frame launches of a tree on the N == 2
+ * lookup path, ray generation skips the 8x8 pixel blocks whose rays provably meet no cell with sigma > 0 -- they
+ * get the pixel of a ray without a hit sample, which is the pixel they would have got.  Not with sigma_thresh < 0,
+ * NDC trees, a render_bbox outside the unit cube, counters / render_depth / SG / ASG, or a camera whose plane cuts an
+ * occupied cell.  out[0] = blocks that launches with the cull on have generated or skipped, out[1] = the skipped
+ * ones among them.  Synchronous (copies from the device); reset != 0 clears them. */
+int vr_tree_cull_stats(vr_tree_t tree, uint64_t out[2], int reset);
 /* Distinct-line meter (SURVEY.md 8(d) "B_unique", the compulsory-traffic lower bound): with
  * enable != 0 the tree gets one bit per 128-byte line of its device arrays, and every
  * INSTRUMENTED launch (frames with counters) sets the bits of the lines its accesses touch.

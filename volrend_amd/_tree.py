@@ -232,6 +232,13 @@ class N3Tree:
                  "retire_rounds", "retired", "iterations")
         return dict(zip(names, [int(v) for v in out]))
 
+    def cull_stats(self, reset: bool = True) -> dict:
+        """8x8 pixel blocks that launches with the block cull on have seen, and those among them that ray
+        generation skipped (vr_tree_cull_stats)."""
+        out = (C.c_uint64 * 2)()
+        _abi.check(_abi.lib().vr_tree_cull_stats(self.handle, C.byref(out), 1 if reset else 0))
+        return {"blocks": int(out[0]), "culled": int(out[1])}
+
     def touch_enable(self, enable: bool = True) -> None:
         """Distinct-line meter of instrumented launches on / off (vr_touch_enable)."""
         _abi.check(_abi.lib().vr_touch_enable(self.handle, 1 if enable else 0))

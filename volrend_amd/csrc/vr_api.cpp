@@ -41,6 +41,7 @@ const Knob kKnobs[] = {
     {"brick_blocked", "VR_BRICK_BLOCKED", &Tuning::brick_blocked, kAutoFlag, 0, 0, true},
     {"max_iter", "VR_MAX_ITER", &Tuning::max_iter, kClamp, 1, INT_MAX, false},
     {"weights_check", "VR_WEIGHTS_CHECK", &Tuning::weights_check, kFlag, 0, 0, false},
+    {"block_cull", "VR_BLOCK_CULL", &Tuning::block_cull, kFlag, 0, 0, false},
 };
 
 const Knob* find_knob(const char* key) {
@@ -212,6 +213,20 @@ int vr_sched_stats(vr_tree_t t, uint64_t out[vr::kSchedStats], int reset) {
     DeviceGuard guard(t->device);
     HIP_TRY(hipMemcpy(out, t->sched_stats.get(), vr::kSchedStats * sizeof(uint64_t), hipMemcpyDeviceToHost));
     if (reset) HIP_TRY(hipMemset(t->sched_stats.get(), 0, vr::kSchedStats * sizeof(uint64_t)));
+    return VR_OK;
+}
+
+int vr_tree_cull_stats(vr_tree_t t, uint64_t out[2], int reset) {
+    if (!t || !out) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard guard(t->device);
+    uint64_t lines[vr::kCullStatLines * vr::kCullStatStride];
+    HIP_TRY(hipMemcpy(lines, t->cull_stats.get(), sizeof(lines), hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(t->cull_stats.get(), 0, sizeof(lines)));
+    out[0] = out[1] = 0;
+    for (int i = 0; i < vr::kCullStatLines; ++i) {
+        out[0] += lines[i * vr::kCullStatStride];
+        out[1] += lines[i * vr::kCullStatStride + 1];
+    }
     return VR_OK;
 }
 

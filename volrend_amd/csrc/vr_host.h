@@ -65,6 +65,7 @@ struct TreeShape {
     int leaf_stride_h = 0;
     int top_levels = 0, brick_levels = 0, n_bricks = 0;  // lookup structure (N == 2), see vr_dev_layout.h
     int brick_blocked = 0;  // entry order of the bricks (vr_dev_layout.h), fixed at upload
+    int occ_levels = -1;    // g of the block cull's occupancy (vr_internal.h "Block cull"); -1: the tree has none
     uint64_t device_bytes = 0;
 };
 
@@ -72,6 +73,8 @@ struct VrTreeOpaque : TreeShape {
     int device = 0;
     DeviceBuffer arrays[4];      // TreeArray: leaves (uint16_t), nodes (uint32_t), top (uint2), bricks (uint32_t)
     DeviceBuffer extra, status, sched_stats;  // float, uint32_t, vr::kSchedStats x u64 (vr_sched_stats)
+    DeviceBuffer occ;            // vr::occ_words(occ_levels) uint32_t: length, bitmap and boundary list of the block cull
+    DeviceBuffer cull_stats;     // vr::kCullStatLines x vr::kCullStatStride u64 (vr_tree_cull_stats)
     DeviceBuffer touch[4];       // distinct-line bitmaps of the arrays (vr_touch_enable)
     DeviceBuffer touch_out;      // 4 x u64
     DeviceBuffer probe_buf;      // kLaunchSlots x data_dim floats: the lumisphere at opt.probe
@@ -108,6 +111,18 @@ inline size_t ray_buffer_bytes(uint32_t total_rays, int words_per_ray) {
     return vr::ray_slots(total_rays) * (size_t)words_per_ray * sizeof(uint32_t);
 }
 inline size_t list_pixel_bytes(uint32_t total_rays) { return (size_t)total_rays * 4; }
+// The block masks of a frame launch (vr_internal.h "Block cull"), behind the ray records of its slot: one bit per
+// 8x8 block of the frame's tile grid (`k`: tile_geometry), whole groups of four words per frame.
+inline uint32_t block_mask_words(const vr::KParams& k) {
+    const uint64_t blocks = (uint64_t)k.tiles_x * (uint64_t)(k.tile_w / 8) * (uint64_t)k.tiles_y * (uint64_t)(k.tile_h / 8);
+    return (uint32_t)(((blocks + 127) / 128) * 4);
+}
+inline size_t block_mask_bytes(const vr::KParams& k, int n_frames) {
+    return (size_t)block_mask_words(k) * sizeof(uint32_t) * (size_t)n_frames;
+}
+// Rebuilds the tree's occupancy from its node words, on `hs` (a tree without one: nothing).  Behind every call
+// that writes node words, before it returns.  (vr_upload.cpp)
+hipError_t refresh_occupancy(const VrTreeOpaque* t, hipStream_t hs);
 
 // Launch slot: per-launch scratch in device memory (ring, see LaunchSlot).  Picks the slot of this
 // launch, points `k` at its scratch and makes its ray buffer large enough (`need` bytes).  `guard` holds the

@@ -191,6 +191,11 @@ struct KParams {
 // The tree takes the N == 2 lookup (top grid + bricks, built at upload when the tree qualifies) and not
 // the literal descent: the launchers of vr_render.hip, vr_weights.hip and vr_query.hip pick their flavour by it.
 inline bool uses_lookup(const KParams& p) { return p.N == 2 && p.top_levels > 0; }
+// Which launches leave FAST for the FULL flavour (render_kernel MODE_FULL, raygen_kernel FULL): SG / ASG
+// lobes, the access counters, and the depth visualisation.
+inline bool needs_full(const KParams& p) {
+    return p.format == VR_FORMAT_SG || p.format == VR_FORMAT_ASG || p.instrumented || p.render_depth;
+}
 
 // The grid of a persistent march kernel (render_kernel, weights_kernel, grad_kernel; one wave per workgroup) over
 // total_blocks blocks of 64 rays: enough waves to fill the chip -- waves_per_cu of the flavour on each of
@@ -223,6 +228,49 @@ struct AovTable {
     int32_t n;
     AovDesc f[kTableChunk];
 };
+
+// ---------------------------------------------------------------------------
+// Block cull (colour and AOV frame launches of trees on the N == 2 lookup path): ray generation sends the 64 rays
+// of an 8x8 pixel block that provably meets no density down the path of a ray that misses the volume -- a ray
+// without a hit sample leaves trace_ray with the same values (out = 0, light = 1).
+//   * Occupancy, built at upload and rebuilt behind every call that writes node words (vr_tree_kernels.hip): a
+//     bitmap of 2^g cells per axis, g = min(kOccMaxLevels, depth of the deepest leaf), cell index x << 2g | y << g | z;
+//     a cell is set when a leaf that overlaps it has sigma > 0.  From it the list of the set cells with an unset or
+//     out-of-grid face neighbour: a line that meets a set cell runs through the closure of a listed one.
+//     One buffer (VrTreeOpaque.occ): kOccHeaderWords words (word 0 = the length of the list), the bitmap, the list
+//     (sized for every cell).
+//   * Per launch, block_mask_kernel (vr_render.hip) splats every listed cell into every frame: one bit per 8x8
+//     block of the FRAME (block (bx, by) = bit by * nbx + bx of the frame's words, whatever the tile shard), in the
+//     launch slot behind the ray records, zeroed by prepare_launch_kernel.
+//   * The FAST flavours of raygen_kernel / raygen_aov_kernel read their block's bit (CullParams, their last
+//     argument; mask = NULL: no cull) and count blocks seen / culled.
+// KParams does not change: the march kernels keep their kernel descriptors (tools/kernel_digest.py).
+// ---------------------------------------------------------------------------
+constexpr int kOccMaxLevels = 7;
+constexpr int kOccHeaderWords = 4;
+constexpr int kCullStatLines = 16;        // the counters are spread over this many 64-byte lines (by workgroup)
+constexpr int kCullStatStride = 8;        // u64 words per line: [0] = blocks seen, [1] = blocks culled
+constexpr int kMaskMaxWords = 4096;       // words of one frame's mask that block_mask_kernel holds in LDS: larger frames
+                                          // (> 131072 blocks) are not culled
+__host__ __device__ inline size_t occ_bitmap_words(int g) { return g >= 2 ? ((size_t)1 << (3 * g)) / 32 : 1; }
+__host__ __device__ inline size_t occ_words(int g) { return kOccHeaderWords + occ_bitmap_words(g) + ((size_t)1 << (3 * g)); }
+struct CullParams {
+    const uint32_t* mask;            // n_frames x words_per_frame; NULL = no cull
+    uint32_t words_per_frame;        // (a multiple of 4)
+    uint32_t nbx;                    // 8x8 blocks per row of the frame
+    unsigned long long* stats;       // kCullStatLines x kCullStatStride
+};
+// What block_mask_kernel reads beside KParams (frames, n_frames, offset, scale, width, height, fx, fy).
+struct MaskParams {
+    uint32_t* mask;
+    uint32_t words_per_frame, nbx, nby;
+    const uint32_t* occ;             // VrTreeOpaque.occ
+    int32_t levels;                  // g
+    int32_t groups_per_frame;        // workgroups that share the list for one frame
+};
+hipError_t launch_block_mask(const KParams& p, const MaskParams& m, hipStream_t stream);
+// the occupancy bitmap and boundary list of a tree from its node words (vr_tree_kernels.hip)
+hipError_t launch_build_occupancy(const uint32_t* nodes, int levels, uint32_t* occ, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
 // Leaf-weight launches (vr_accumulate_weights): the march without records or shading.  The kernels of
@@ -330,12 +378,15 @@ hipError_t launch_step_values(const StepArgs& a, int n_cus, hipStream_t stream);
 
 // vr_render.hip: the kernels of a launch
 hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream);
-hipError_t launch_render_aov(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
-                             int gen_waves, hipStream_t stream);
-hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream);
+// (cull: the block masks of the launch, CullParams{} = none; a ray list never has one)
+hipError_t launch_render_aov(const KParams& p, const AovParams& a, const CullParams& cull, int fp_mode, int n_cus,
+                             int waves_override, int gen_waves, hipStream_t stream);
+// (mask: the block masks of the launch, which the kernel clears for its frames; NULL = none)
+hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream, uint32_t* mask = nullptr,
+                          uint32_t words_per_frame = 0);
 // (rays: as launch_weights; the frame table then holds the list's one pseudo-frame)
-hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
-                         hipStream_t stream, const RayList* rays = nullptr);
+hipError_t launch_render(const KParams& p, const CullParams& cull, int fp_mode, int n_cus, int waves_override,
+                         int gen_waves, hipStream_t stream, const RayList* rays = nullptr);
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
                         hipStream_t stream);
 

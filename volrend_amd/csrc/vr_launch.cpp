@@ -261,11 +261,12 @@ bool needs_file_order(LaunchKind kind) { return kind == LaunchKind::kWeights || 
 
 // What the enqueue step of a launch finds ready: the finished KParams, the knobs the launch goes by, the waves
 // of a ray-generation workgroup, its slot, its stream, and the pixel words it asked for (else NULL).
-struct Turn { const vr::KParams& k; const Tuning& tn; int gen_waves; unsigned slot; hipStream_t hs; void* pixel_words; };
+struct Turn { const vr::KParams& k; const Tuning& tn; int gen_waves; unsigned slot; hipStream_t hs; void* extra; };
 
 // THE launch sequence; every march launch goes through it.  `k` holds what the entry point checked and filled
-// (geometry, caller's part); pixel_words: 4 more bytes per ray behind the records (vr_render_rays without an
-// rgba array: the march stores a pixel word per ray anyway); enqueue(Turn) puts tables and kernels into the
+// (geometry, caller's part); extra_bytes: that much more of the slot's buffer behind the records, Turn.extra
+// (vr_render_rays without an rgba array: 4 bytes per ray, the march stores a pixel word per ray anyway; a frame
+// launch of a tree with occupancy: its block masks); enqueue(Turn) puts tables and kernels into the
 // stream, behind the slot's previous launch.  The device guard comes before the mutex.
 //   * The launch mutex covers slot bookkeeping and the enqueue order of one launch, and everything that other
 //     calls change under it: the knobs (vr_tree_set_tuning), the touch bitmaps (vr_touch_enable / vr_touch_count
@@ -275,7 +276,7 @@ struct Turn { const vr::KParams& k; const Tuning& tn; int gen_waves; unsigned sl
 //   * The file-order table is made before anything else (the call's one host-blocking step), also by a warm-up
 //     call -- no frames, or an empty list -- which launches nothing.
 template <typename Enqueue>
-int run_launch(VrTreeOpaque* t, LaunchKind kind, const Views& v, bool pixel_words, vr::KParams& k, void* stream,
+int run_launch(VrTreeOpaque* t, LaunchKind kind, const Views& v, size_t extra_bytes, vr::KParams& k, void* stream,
                Enqueue&& enqueue) {
     DeviceGuard device_guard(t->device);
     hipStream_t hs = static_cast<hipStream_t>(stream);
@@ -289,13 +290,12 @@ int run_launch(VrTreeOpaque* t, LaunchKind kind, const Views& v, bool pixel_word
     fill_tuning_params(k, t, tn, plan);
     const size_t records = ray_buffer_bytes(k.total_rays, record_words(kind, k.ray_tail_words));
     unsigned slot;
-    if (int rc = acquire_slot(t, guard, hs, k, records + (pixel_words ? list_pixel_bytes(k.total_rays) : 0), slot))
-        return rc;
+    if (int rc = acquire_slot(t, guard, hs, k, records + extra_bytes, slot)) return rc;
     fill_tree_params(k, t);
     SlotTurn turn;
     if (int rc = turn.begin(t->slots[slot], hs)) return rc;
-    void* const pixels = pixel_words ? t->slots[slot].rays.get<char>() + records : nullptr;
-    return enqueue(Turn{k, tn, plan.raygen_waves, slot, hs, pixels});  // (`turn` records the slot's event)
+    void* const extra = extra_bytes ? t->slots[slot].rays.get<char>() + records : nullptr;
+    return enqueue(Turn{k, tn, plan.raygen_waves, slot, hs, extra});  // (`turn` records the slot's event)
 }
 
 // What vr_render_aov adds to the checks of a batch; leaves pitch and depth_world in `a`.
@@ -331,7 +331,8 @@ int validate_aov(int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
 // has its one pseudo-frame and no pose.  frames = NULL: no buffers (a leaf-weight or backward launch, which
 // only needs the poses and the queue reset); aovs: also the plane table of an AOV launch, through `a`.
 int enqueue_tables(const vr::KParams& k, const Views& v, hipStream_t hs, const VrFrame* frames = nullptr,
-                   const VrAov* aovs = nullptr, const vr::AovParams& a = vr::AovParams{}) {
+                   const VrAov* aovs = nullptr, const vr::AovParams& a = vr::AovParams{},
+                   const vr::MaskParams& m = vr::MaskParams{}) {
     for (int first = 0; first < k.n_frames; first += vr::kTableChunk) {
         vr::FrameTable tbl;
         memset(&tbl, 0, sizeof(tbl));
@@ -345,7 +346,7 @@ int enqueue_tables(const vr::KParams& k, const Views& v, hipStream_t hs, const V
             tbl.f[i].depth = frames[first + i].depth;
             tbl.f[i].counters = reinterpret_cast<VrCounters*>(frames[first + i].counters);
         }
-        HIP_TRY(vr::launch_prepare(k, tbl, hs));
+        HIP_TRY(vr::launch_prepare(k, tbl, hs, m.mask, m.words_per_frame));  // (also clears the frames' block masks)
         if (aovs) {
             vr::AovTable at;
             memset(&at, 0, sizeof(at));
@@ -361,8 +362,21 @@ int enqueue_tables(const vr::KParams& k, const Views& v, hipStream_t hs, const V
     return VR_OK;
 }
 
+// Whether the launch culls blocks (vr_internal.h "Block cull"), from the finished KParams, the knobs it goes by
+// and its options.  Off: the knob; a tree without occupancy (not on the N == 2 lookup path); the FULL flavours
+// (their counters equal the oracle's); sigma_thresh < 0 (a sample of sigma 0 is a hit then); an NDC tree (its rays
+// are warped); a render_bbox that leaves the unit cube (samples outside it are clamped into the border leaves); a
+// frame of more blocks than block_mask_kernel holds.
+bool culls_blocks(const VrTreeOpaque* t, const vr::KParams& k, const Tuning& tn, const VrRenderOptions* opt) {
+    if (!tn.block_cull || !t->occ || !vr::uses_lookup(k) || vr::needs_full(k)) return false;
+    if (opt->sigma_thresh < 0.f || k.ndc_width > 0) return false;
+    for (int i = 0; i < 3; ++i)
+        if (!(opt->render_bbox[i] >= 0.f) || !(opt->render_bbox[i + 3] <= 1.f)) return false;
+    return block_mask_words(k) <= (uint32_t)vr::kMaskMaxWords;
+}
+
 // vr_render_batch (aovs = NULL) and vr_render_aov.  Into the stream go the probe pre-kernel, the frame table
-// (for an AOV launch also the plane table, in the launch's slot), ray generation + render.
+// (for an AOV launch also the plane table, in the launch's slot), the block masks, ray generation + render.
 int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
                   const VrFrame* frames, const VrAov* aovs, int depth_units, bool want_aov, void* stream) {
     vr::KParams k;
@@ -374,15 +388,30 @@ int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRende
         if (int rc = validate_aov(n_frames, cams, opt, frames, aovs, depth_units, a)) return rc;
     fill_caller_params(k, opt, &frames[0]);
     const Views v{cams, n_frames};
-    return run_launch(t, want_aov ? LaunchKind::kAov : LaunchKind::kColour, v, false, k, stream, [&](const Turn& u) -> int {
+    const size_t mask_bytes = t->occ ? block_mask_bytes(k, n_frames) : 0;  // (room for them, whatever the knob says)
+    return run_launch(t, want_aov ? LaunchKind::kAov : LaunchKind::kColour, v, mask_bytes, k, stream, [&](const Turn& u) -> int {
         a.planes = t->slot_aovs.get<vr::AovDesc>() + (size_t)u.slot * vr::kMaxBatch;
         if (u.k.enable_probe)  // launch_renderer's pre-kernel, volrend.cu:202-209
             HIP_TRY(vr::launch_probe(u.k, opt->probe, const_cast<float*>(u.k.probe_coeffs), u.hs));
-        if (int rc = enqueue_tables(u.k, v, u.hs, frames, want_aov ? aovs : nullptr, a)) return rc;
+        vr::MaskParams m{};
+        vr::CullParams cull{};
+        if (u.extra && culls_blocks(t, u.k, u.tn, opt)) {
+            m.mask = static_cast<uint32_t*>(u.extra);
+            m.words_per_frame = block_mask_words(u.k);
+            m.nbx = (uint32_t)(u.k.tiles_x * (u.k.tile_w / 8));
+            m.nby = (uint32_t)(u.k.tiles_y * (u.k.tile_h / 8));
+            m.occ = t->occ.get<uint32_t>();
+            m.levels = t->occ_levels;
+            const int groups = 2048 / n_frames;  // workgroups that share the cell list for one frame
+            m.groups_per_frame = groups < 4 ? 4 : (groups > 128 ? 128 : groups);
+            cull = vr::CullParams{m.mask, m.words_per_frame, m.nbx, t->cull_stats.get<unsigned long long>()};
+        }
+        if (int rc = enqueue_tables(u.k, v, u.hs, frames, want_aov ? aovs : nullptr, a, m)) return rc;
+        if (m.mask) HIP_TRY(vr::launch_block_mask(u.k, m, u.hs));
         if (want_aov)
-            HIP_TRY(vr::launch_render_aov(u.k, a, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
+            HIP_TRY(vr::launch_render_aov(u.k, a, cull, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
         else
-            HIP_TRY(vr::launch_render(u.k, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
+            HIP_TRY(vr::launch_render(u.k, cull, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
         return VR_OK;
     });
 }
@@ -437,7 +466,7 @@ int march_launch(vr_tree_t t, LaunchKind kind, const Views& v, const VrRenderOpt
     k.offscreen = 1;
     k.layout = VR_LAYOUT_FRAME;
     k.pitch = (int64_t)k.width * 4;
-    return run_launch(t, kind, v, false, k, stream, [&](const Turn& u) -> int {
+    return run_launch(t, kind, v, 0, k, stream, [&](const Turn& u) -> int {
         if (int rc = enqueue_tables(u.k, v, u.hs)) return rc;
         HIP_TRY(launch(u));
         return VR_OK;
@@ -595,10 +624,11 @@ int vr_render_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOpt
     f.accum = out->accum;
     fill_caller_params(k, opt, &f);
     k.any_accum = out->accum ? 1 : 0;
-    return run_launch(t, LaunchKind::kColour, v, !out->rgba, k, stream, [&](const Turn& u) -> int {
-        f.rgba = out->rgba ? out->rgba : u.pixel_words;
+    const size_t pixel_bytes = out->rgba ? 0 : list_pixel_bytes(k.total_rays);
+    return run_launch(t, LaunchKind::kColour, v, pixel_bytes, k, stream, [&](const Turn& u) -> int {
+        f.rgba = out->rgba ? out->rgba : u.extra;
         if (int rc = enqueue_tables(u.k, v, u.hs, &f)) return rc;
-        HIP_TRY(vr::launch_render(u.k, fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs, v.rays()));
+        HIP_TRY(vr::launch_render(u.k, vr::CullParams{}, fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs, v.rays()));
         return VR_OK;
     });
 }

@@ -33,6 +33,8 @@ struct Tuning {
                              // a launch that trips it reports through vr_tree_status (tests lower it)
     int weights_check = 1;   // vr_accumulate_weights: read max_weight[slot] first and issue the atomic max only
                              // for a larger weight (0: one atomic per positive weight; vr_weights.hip, EXPERIMENTS.md)
+    int block_cull = 1;      // colour / AOV frame launches: ray generation culls the 8x8 pixel blocks that meet no
+                             // occupied cell (vr_internal.h "Block cull"; 0: every block generates its rays)
 };
 
 // The march kernel of a launch, and what its rays come from: the pixels of n_frames poses, or a list of rays

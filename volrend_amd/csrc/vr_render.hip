@@ -209,6 +209,7 @@ __device__ __forceinline__ void store_colour_ray(const KParams& p, uint32_t slot
 #define VR_RENDER_KERNEL render_kernel
 #define VR_RAYGEN_KERNEL raygen_kernel
 #define VR_KERNEL_ARGS const KParams p
+#define VR_RAYGEN_ARGS const KParams p, const CullParams cull
 #define VR_KERNEL_AOV false
 #define VR_KERNEL_AOV_LOCAL const AovParams aov{};  // (never read)
 #endif  // VR_KERNEL_PASS_AOV
@@ -693,7 +694,7 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void VR_R
 // atomics: at 4 waves a 64-frame launch is 4 % slower, at 1 wave 35 % (profiles/r06_raygen_waves.jsonl).
 
 template <int FMA, bool FULL, int GW>
-__global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
+__global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_RAYGEN_ARGS) {
     constexpr bool AOV = VR_KERNEL_AOV;
     VR_KERNEL_AOV_LOCAL
     const int lane = threadIdx.x & (kWave - 1);
@@ -701,6 +702,10 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
     const uint32_t id =
         (uint32_t)(((int64_t)blockIdx.x * GW + wave) * kWave + lane);
     bool valid = false;
+    // Block cull (vr_internal.h; FAST flavours, cull.mask != NULL): the 64 lanes of a wave hold the pixels of ONE
+    // 8x8 block of one frame.  When the block's bit of the launch's mask is clear, no ray of the block meets a
+    // cell with density: all of them take the path of a ray that misses the volume, which leaves the same pixel.
+    bool culled = false;
     Ray nr;
     uint8_t* px = nullptr;
     uint32_t xy = 0;
@@ -708,11 +713,19 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
     float vdir[3] = {0.f, 0.f, 1.f};
     if (id < p.total_rays) {
         const PixelRef r = locate(p, id);
+        if constexpr (!FULL) {
+            if (cull.mask) {
+                const uint32_t b = (uint32_t)(r.y >> 3) * cull.nbx + (uint32_t)(r.x >> 3);
+                const uint32_t w = cull.mask[(size_t)r.frame * cull.words_per_frame + (b >> 5)];
+                culled = __builtin_amdgcn_readfirstlane((int)((w >> (b & 31u)) & 1u)) == 0;  // (wave-uniform)
+            }
+        }
         if (r.in_image) {
             frame = r.frame;
             xy = (uint32_t)r.x | ((uint32_t)r.y << 16);
             px = pixel_ptr(p, p.frames[r.frame], r);
-            setup_ray<FMA>(p, r, nr, vdir);
+            if (culled) reset_ray(nr);
+            else setup_ray<FMA>(p, r, nr, vdir);
             if (nr.alive) {
                 valid = true;
             } else {
@@ -724,7 +737,31 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
     }
     // compaction into the queue that owns the workgroup's blocks (vr_dev_rays.h)
     const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
+    __shared__ uint32_t wave_culled[GW];  // (read behind the barriers of reserve_ray_slots)
+    if constexpr (!FULL && GW > 1) {
+        if (cull.mask && lane == 0) wave_culled[wave] = culled ? 1u : 0u;
+    }
     const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
+    if constexpr (!FULL) {
+        // the observable (vr_tree_cull_stats): blocks seen and blocks culled by this workgroup, one atomic
+        // instruction (two lanes, two words of one line; the lines are dealt over the workgroups)
+        if (cull.mask && threadIdx.x < 2u) {
+            const int64_t left = (int64_t)(p.total_rays >> 6) - (int64_t)blockIdx.x * GW;
+            uint32_t n = (uint32_t)(left < 0 ? 0 : (left < GW ? left : GW));
+            if (threadIdx.x == 1u) {
+                if constexpr (GW > 1) {
+                    n = 0;
+#pragma unroll
+                    for (int w = 0; w < GW; ++w) n += wave_culled[w];
+                } else {
+                    n = culled ? 1u : 0u;
+                }
+            }
+            if (n)
+                atomicAdd(cull.stats + (blockIdx.x & (uint32_t)(kCullStatLines - 1)) * kCullStatStride + threadIdx.x,
+                          (unsigned long long)n);
+        }
+    }
     if (!valid) return;
     const uint32_t slot = my_base + lane_rank(m_valid);
     uint32_t* rb = ray_slot(p.ray_buf_rw, kRayWords + p.ray_tail_words, slot);
@@ -763,6 +800,7 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
 #undef VR_RENDER_KERNEL
 #undef VR_RAYGEN_KERNEL
 #undef VR_KERNEL_ARGS
+#undef VR_RAYGEN_ARGS
 #undef VR_KERNEL_AOV
 #undef VR_KERNEL_AOV_LOCAL
 // the AOV pair (vr_render_aov): the same text once more
@@ -770,6 +808,7 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
 #define VR_RENDER_KERNEL render_aov_kernel
 #define VR_RAYGEN_KERNEL raygen_aov_kernel
 #define VR_KERNEL_ARGS const KParams p, const AovParams aov
+#define VR_RAYGEN_ARGS const KParams p, const AovParams aov, const CullParams cull
 #define VR_KERNEL_AOV true
 #define VR_KERNEL_AOV_LOCAL
 #include "vr_render.hip"
@@ -777,6 +816,7 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_KERNEL_ARGS) {
 #undef VR_RENDER_KERNEL
 #undef VR_RAYGEN_KERNEL
 #undef VR_KERNEL_ARGS
+#undef VR_RAYGEN_ARGS
 #undef VR_KERNEL_AOV
 #undef VR_KERNEL_AOV_LOCAL
 
@@ -817,12 +857,119 @@ __global__ __launch_bounds__(kWave* GW) void raygen_rays_kernel(const KParams p,
 
 // Writes the per-launch frame table into device memory and resets the ray queue.
 // (Stream-ordered replacement for a pinned-memory H2D copy + memset.)
-__global__ void prepare_launch_kernel(FrameTable tbl, FrameDesc* frames, uint32_t* queue_head) {
+// mask != NULL: also clears the block masks of its frames (words_per_frame, a multiple of 4, each) for
+// block_mask_kernel.
+__global__ void prepare_launch_kernel(FrameTable tbl, FrameDesc* frames, uint32_t* queue_head, uint32_t* mask,
+                                      uint32_t words_per_frame) {
     const int i = threadIdx.x;
     if (i < tbl.n) frames[tbl.first + i] = tbl.f[i];
     if (tbl.first == 0 && i < kMaxQueues) {
         queue_head[i * kQueueStride + kQueueHead] = 0u;
         queue_head[i * kQueueStride + kQueueCount] = 0u;
+    }
+    if (mask) {
+        uint4* const q = reinterpret_cast<uint4*>(mask + (size_t)tbl.first * words_per_frame);
+        const uint32_t n = (uint32_t)tbl.n * (words_per_frame >> 2);
+        for (uint32_t j = threadIdx.x; j < n; j += blockDim.x) q[j] = make_uint4(0u, 0u, 0u, 0u);
+    }
+}
+
+// ---------------------------------------------------------------------------
+// block_mask_kernel: the block masks of a launch (vr_internal.h "Block cull").  Workgroup (x, f) takes the x-th
+// part of the tree's boundary-cell list for frame f: every cell is projected as its bounding sphere, the blocks
+// the projection can touch are marked in an LDS copy of the frame's mask, and the copy's non-zero words are ORed
+// into the mask of the launch slot.
+//   Cell centre c (tree space) -> world (c - offset) / scale -> camera (X, Y, depth) by the frame's pose; the
+//   sphere has the half-diagonal r of the cell's box in world space.  A point of the sphere, (X + a, Y + b,
+//   depth + e) with a^2 + b^2 + e^2 <= r^2, lies on the ray of pixel x = w/2 + fx (X + a) / (depth + e), and
+//   |(X + a) / (depth + e) - X / depth| = |a depth - X e| / (depth (depth + e)) <= r sqrt(depth^2 + X^2) /
+//   (depth (depth - r)); likewise for y.  That half-width, times 1.05 plus one pixel for the rounding of ray
+//   generation and of this kernel, gives the rectangle of pixels whose blocks are marked.
+//   The whole frame is marked when a sphere comes within r / 100 of the camera plane (depth - r <= r / 100), when the
+//   pose is not a rotation (to 1e-4) or anything here is not finite: such a frame is not culled.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void block_mask_kernel(const KParams p, const MaskParams m) {
+    __shared__ uint32_t bits[kMaskMaxWords];
+    __shared__ uint32_t whole;
+    const uint32_t wpf = m.words_per_frame;
+    for (uint32_t i = threadIdx.x; i < wpf; i += blockDim.x) bits[i] = 0u;
+    if (threadIdx.x == 0) whole = 0u;
+    __syncthreads();
+    const int frame = blockIdx.y;
+    const int g = m.levels;
+    const uint32_t count = m.occ[0];
+    const uint32_t* const list = m.occ + kOccHeaderWords + occ_bitmap_words(g);
+    const uint32_t per = (count + (uint32_t)m.groups_per_frame - 1u) / (uint32_t)m.groups_per_frame;
+    const uint32_t lo = blockIdx.x * per;
+    const uint32_t hi = lo + per < count ? lo + per : count;
+    float xf[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) xf[i] = p.frames[frame].xf[i];
+    const float cell = u2f((uint32_t)(127 - g) << 23);  // 2^-g
+    float inv_scale[3], r2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        inv_scale[i] = 1.f / p.scale[i];
+        const float h = 0.5f * cell * inv_scale[i];
+        r2 += h * h;
+    }
+    const float r = __builtin_sqrtf(r2) * 1.0001f;
+    // the pose must be a rotation for the sphere to stay one in camera space
+    bool ok = r > 0.f && r < 1e30f;
+#pragma unroll
+    for (int a = 0; a < 3; ++a)
+#pragma unroll
+        for (int b = a; b < 3; ++b) {
+            const float d = xf[3 * a] * xf[3 * b] + xf[3 * a + 1] * xf[3 * b + 1] + xf[3 * a + 2] * xf[3 * b + 2];
+            if (!(__builtin_fabsf(d - (a == b ? 1.f : 0.f)) <= 1e-4f)) ok = false;
+        }
+    const float afx = __builtin_fabsf(p.fx), afy = __builtin_fabsf(p.fy);
+    const uint32_t n_mask = (1u << g) - 1u;
+    const float fnbx = (float)m.nbx, fnby = (float)m.nby;
+    if (!ok && lo < hi) whole = 1u;
+    for (uint32_t idx = lo + threadIdx.x; ok && idx < hi; idx += blockDim.x) {
+        const uint32_t c = list[idx];
+        const float tc[3] = {((float)((c >> (2 * g)) & n_mask) + 0.5f) * cell, ((float)((c >> g) & n_mask) + 0.5f) * cell,
+                             ((float)(c & n_mask) + 0.5f) * cell};
+        float d[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) d[i] = (tc[i] - p.offset[i]) * inv_scale[i] - xf[9 + i];
+        const float X = xf[0] * d[0] + xf[1] * d[1] + xf[2] * d[2];
+        const float Y = xf[3] * d[0] + xf[4] * d[1] + xf[5] * d[2];
+        const float depth = -(xf[6] * d[0] + xf[7] * d[1] + xf[8] * d[2]);
+        if (!(depth - r > 0.01f * r)) {
+            // in front of the camera plane or through it -- or behind it: then no ray of the frame reaches the cell
+            if (!(depth + r < 0.f)) whole = 1u;
+            continue;
+        }
+        const float inv = 1.f / (depth * (depth - r));
+        const float rx = afx * r * __builtin_sqrtf(depth * depth + X * X) * inv * 1.05f + 1.f;
+        const float ry = afy * r * __builtin_sqrtf(depth * depth + Y * Y) * inv * 1.05f + 1.f;
+        const float px = 0.5f * (float)p.width + p.fx * X / depth;
+        const float py = 0.5f * (float)p.height - p.fy * Y / depth;
+        // blocks [bx0, bx1] x [by0, by1], clamped in float (a NaN takes the whole row / column)
+        const float fx0 = __builtin_floorf(__builtin_fmaxf((px - rx) * 0.125f, 0.f));
+        const float fx1 = __builtin_floorf(__builtin_fminf((px + rx) * 0.125f, fnbx - 1.f));
+        const float fy0 = __builtin_floorf(__builtin_fmaxf((py - ry) * 0.125f, 0.f));
+        const float fy1 = __builtin_floorf(__builtin_fminf((py + ry) * 0.125f, fnby - 1.f));
+        if (!(fx0 <= fx1) || !(fy0 <= fy1)) continue;  // beside the frame
+        const uint32_t bx0 = (uint32_t)fx0, bx1 = (uint32_t)fx1, by0 = (uint32_t)fy0, by1 = (uint32_t)fy1;
+        for (uint32_t by = by0; by <= by1; ++by) {
+            const uint32_t first = by * m.nbx + bx0, last = by * m.nbx + bx1;
+            for (uint32_t w = first >> 5; w <= (last >> 5); ++w) {
+                const uint32_t from = w == (first >> 5) ? (first & 31u) : 0u;
+                const uint32_t to = w == (last >> 5) ? (last & 31u) : 31u;
+                const uint32_t mask = (0xFFFFFFFFu >> (31u - to)) & (0xFFFFFFFFu << from);
+                if ((bits[w] & mask) != mask) atomicOr(&bits[w], mask);
+            }
+        }
+    }
+    __syncthreads();
+    uint32_t* const out = m.mask + (size_t)frame * wpf;
+    const bool all = whole != 0u;
+    for (uint32_t i = threadIdx.x; i < wpf; i += blockDim.x) {
+        const uint32_t v = all ? 0xFFFFFFFFu : bits[i];
+        if (v != 0u && (out[i] & v) != v) atomicOr(&out[i], v);  // (a stale read only costs the atomic)
     }
 }
 
@@ -902,12 +1049,6 @@ __global__ void probe_kernel(const KParams p, float probe0, float probe1, float 
     for (int i = threadIdx.x; i < p.data_dim - 1; i += blockDim.x) out[i] = h2f(v[i]);
 }
 
-// Which launches leave FAST for the FULL flavour (render_kernel MODE_FULL, raygen_kernel FULL): SG / ASG
-// lobes, the access counters, and the depth visualisation.
-bool needs_full(const KParams& p) {
-    return p.format == VR_FORMAT_SG || p.format == VR_FORMAT_ASG || p.instrumented || p.render_depth;
-}
-
 // grid = the persistent waves (persistent_grid, vr_internal.h): as many as the chip holds of this flavour
 // (or the tuning override)
 template <int FMA, int MODE, bool AOV>
@@ -952,19 +1093,19 @@ hipError_t launch_fp(const KParams& p, const AovParams& a, int64_t total_blocks,
 // Ray generation + the persistent march of one launch (the probe overlay is launch_render's own).
 // rays: a ray list takes the place of the frames' pixels (never with AOV planes).
 template <bool AOV>
-hipError_t launch_march(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
-                        int gen_waves, hipStream_t stream, const RayList* rays = nullptr) {
+hipError_t launch_march(const KParams& p, const AovParams& a, const CullParams& cull, int fp_mode, int n_cus,
+                        int waves_override, int gen_waves, hipStream_t stream, const RayList* rays = nullptr) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
     {   // ray generation: gen_waves wave blocks (8x8 pixels each) per workgroup
         const bool full = needs_full(p);
 #define VR_GEN(FMA_, FULL_, GW_)                                                                    \
     do {                                                                                            \
         const dim3 grid_((unsigned)((total_blocks + GW_ - 1) / GW_)), block_(kWave * GW_);          \
-        if constexpr (AOV) hipLaunchKernelGGL((raygen_aov_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, a); \
+        if constexpr (AOV) hipLaunchKernelGGL((raygen_aov_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, a, cull); \
         else if (rays) {                                                                            \
             if constexpr (GW_ >= 4) hipLaunchKernelGGL((raygen_rays_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, *rays); \
         }                                                                                           \
-        else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p);    \
+        else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, cull); \
     } while (0)
 #define VR_GEN_GW(FMA_, FULL_)                                                                      \
     do {                                                                                            \
@@ -987,16 +1128,26 @@ hipError_t launch_march(const KParams& p, const AovParams& a, int fp_mode, int n
 
 }  // namespace
 
-hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream) {
+hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream, uint32_t* mask,
+                          uint32_t words_per_frame) {
     hipLaunchKernelGGL(prepare_launch_kernel, dim3(1), dim3(64), 0, stream, tbl,
-                       const_cast<FrameDesc*>(p.frames), p.queue_head);
+                       const_cast<FrameDesc*>(p.frames), p.queue_head, mask, words_per_frame);
     return hipGetLastError();
 }
 
-hipError_t launch_render(const KParams& p, int fp_mode, int n_cus, int waves_override, int gen_waves,
-                         hipStream_t stream, const RayList* rays) {
+// one workgroup per (part of the list, frame)
+hipError_t launch_block_mask(const KParams& p, const MaskParams& m, hipStream_t stream) {
+    if (p.n_frames <= 0 || m.groups_per_frame <= 0) return hipSuccess;
+    hipLaunchKernelGGL(block_mask_kernel, dim3((unsigned)m.groups_per_frame, (unsigned)p.n_frames), dim3(256), 0, stream,
+                       p, m);
+    return hipGetLastError();
+}
+
+hipError_t launch_render(const KParams& p, const CullParams& cull, int fp_mode, int n_cus, int waves_override,
+                         int gen_waves, hipStream_t stream, const RayList* rays) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    const hipError_t e = launch_march<false>(p, AovParams{}, fp_mode, n_cus, waves_override, gen_waves, stream, rays);
+    const hipError_t e =
+        launch_march<false>(p, AovParams{}, cull, fp_mode, n_cus, waves_override, gen_waves, stream, rays);
     if (e != hipSuccess || !p.enable_probe || p.probe_disp_size <= 0) return e;
     const int side = p.probe_disp_size + 5;
     const dim3 pgrid((unsigned)((side * side + 255) / 256), (unsigned)p.n_frames);
@@ -1013,10 +1164,10 @@ hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream
 }
 
 // (no probe overlay: vr_render_aov refuses enable_probe)
-hipError_t launch_render_aov(const KParams& p, const AovParams& a, int fp_mode, int n_cus, int waves_override,
-                             int gen_waves, hipStream_t stream) {
+hipError_t launch_render_aov(const KParams& p, const AovParams& a, const CullParams& cull, int fp_mode, int n_cus,
+                             int waves_override, int gen_waves, hipStream_t stream) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    return launch_march<true>(p, a, fp_mode, n_cus, waves_override, gen_waves, stream);
+    return launch_march<true>(p, a, cull, fp_mode, n_cus, waves_override, gen_waves, stream);
 }
 
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,

@@ -130,7 +130,8 @@ int vr_reserve_tiles(vr_tree_t t, int width, int height, int n_frames, int tile_
     // exactly the ray count vr_render_batch computes, for rank 0 (which holds the most tiles)
     vr::KParams geo;
     if (int rc = launch_geometry(width, height, tile_w, tile_h, 0, world, n_frames, geo)) return rc;
-    return reserve_slots(t, n_slots, colour_record_bytes(t, geo.total_rays));
+    // (behind the records: the block masks of such a launch, vr_internal.h "Block cull")
+    return reserve_slots(t, n_slots, colour_record_bytes(t, geo.total_rays) + (t->occ ? block_mask_bytes(geo, n_frames) : 0));
 }
 
 // two slots of whole frames: what a render loop on one stream (one slot) or on two alternating

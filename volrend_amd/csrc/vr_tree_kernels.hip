@@ -189,7 +189,111 @@ __global__ void build_bricks_kernel(const uint32_t* nodes, const int32_t* brick_
     bricks[gid] = node;  // internal node of level G0 + BL
 }
 
+// ---------------------------------------------------------------------------
+// Occupancy of the block cull (vr_internal.h "Block cull"): bitmap and boundary list, from the node words.
+// ---------------------------------------------------------------------------
+// sigma of a leaf word as the march reads it: a float compare, so NaN, -0 and negative values do not count
+__device__ __forceinline__ bool leaf_occupied(uint32_t w) {
+    return (float)__builtin_bit_cast(_Float16, (uint16_t)(w & 0xFFFFu)) > 0.f;
+}
+
+// Does the subtree of `node` hold a leaf with sigma > 0?  Depth first with an explicit stack of (node, next
+// child); a leaf sits at most 24 levels deep (lookup_applies), deeper is answered "yes".
+__device__ bool subtree_occupied(const uint32_t* nodes, uint32_t node) {
+    constexpr int kStack = 24;
+    uint32_t st_node[kStack];
+    uint32_t st_next[kStack];
+    int sp = 0;
+    st_node[0] = node;
+    st_next[0] = 0;
+    while (sp >= 0) {
+        if (st_next[sp] == 8u) {
+            --sp;
+            continue;
+        }
+        const uint32_t w = nodes[(uint64_t)st_node[sp] * 8u + st_next[sp]];
+        st_next[sp]++;
+        if (w & kLeafBit) {
+            if (leaf_occupied(w)) return true;
+        } else {
+            if (sp + 1 >= kStack) return true;
+            ++sp;
+            st_node[sp] = w;
+            st_next[sp] = 0;
+        }
+    }
+    return false;
+}
+
+// One thread per cell of the 2^g-per-axis grid, 32 consecutive cells per bitmap word.  Thread 0 clears the
+// length of the list, which occupancy_list_kernel appends to behind this kernel.
+__global__ void occupancy_cells_kernel(const uint32_t* nodes, int g, uint32_t* occ) {
+    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n_cells = 1u << (3 * g);
+    if (cell == 0) occ[0] = 0u;
+    bool set = false;
+    if (cell < n_cells) {
+        const uint32_t mask = (1u << g) - 1u;
+        const uint32_t cx = (cell >> (2 * g)) & mask, cy = (cell >> g) & mask, cz = cell & mask;
+        uint32_t node = 0;
+        bool leaf = false;
+        for (int l = 0; l < g; ++l) {
+            const int sh = g - 1 - l;
+            const uint32_t slot = (((cx >> sh) & 1u) << 2) | (((cy >> sh) & 1u) << 1) | ((cz >> sh) & 1u);
+            const uint32_t w = nodes[(uint64_t)node * 8u + slot];
+            if (w & kLeafBit) {
+                leaf = true;
+                set = leaf_occupied(w);
+                break;
+            }
+            node = w;
+        }
+        if (!leaf) set = subtree_occupied(nodes, node);  // an internal node of level g (g = 0: the root)
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(set);
+    if ((threadIdx.x & 31u) == 0u && cell < (n_cells > 32u ? n_cells : 32u))
+        occ[kOccHeaderWords + (cell >> 5)] = (uint32_t)(m >> (threadIdx.x & 32u));
+}
+
+// The set cells with an unset or out-of-grid face neighbour, appended with one atomic per wave.
+__global__ void occupancy_list_kernel(int g, uint32_t* occ) {
+    const uint32_t cell = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t n_cells = 1u << (3 * g);
+    const uint32_t* bits = occ + kOccHeaderWords;
+    uint32_t* list = occ + kOccHeaderWords + occ_bitmap_words(g);
+    bool keep = false;
+    if (cell < n_cells) {
+        const int n = 1 << g;
+        const int c[3] = {(int)((cell >> (2 * g)) & (uint32_t)(n - 1)), (int)((cell >> g) & (uint32_t)(n - 1)),
+                          (int)(cell & (uint32_t)(n - 1))};
+        auto is_set = [&](int x, int y, int z) -> bool {
+            if (x < 0 || y < 0 || z < 0 || x >= n || y >= n || z >= n) return false;
+            const uint32_t i = ((uint32_t)x << (2 * g)) | ((uint32_t)y << g) | (uint32_t)z;
+            return (bits[i >> 5] >> (i & 31u)) & 1u;
+        };
+        if (is_set(c[0], c[1], c[2]))
+            keep = !(is_set(c[0] - 1, c[1], c[2]) && is_set(c[0] + 1, c[1], c[2]) && is_set(c[0], c[1] - 1, c[2]) &&
+                     is_set(c[0], c[1] + 1, c[2]) && is_set(c[0], c[1], c[2] - 1) && is_set(c[0], c[1], c[2] + 1));
+    }
+    const unsigned long long m = __builtin_amdgcn_ballot_w64(keep);
+    if (m == 0ull) return;
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t base = 0;
+    if (lane == (uint32_t)__builtin_ctzll(m)) base = atomicAdd(&occ[0], (uint32_t)__builtin_popcountll(m));
+    base = (uint32_t)__builtin_amdgcn_readlane((int)base, __builtin_ctzll(m));
+    if (keep)
+        list[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = cell;
+}
+
 }  // namespace
+
+hipError_t launch_build_occupancy(const uint32_t* nodes, int levels, uint32_t* occ, hipStream_t stream) {
+    const uint32_t n_cells = 1u << (3 * levels);
+    const dim3 grid((n_cells + 255u) / 256u), block(256);
+    hipLaunchKernelGGL(occupancy_cells_kernel, grid, block, 0, stream, nodes, levels, occ);
+    hipLaunchKernelGGL(occupancy_list_kernel, grid, block, 0, stream, levels, occ);
+    return hipGetLastError();
+}
 
 hipError_t launch_assemble(uint8_t* frame, int64_t pitch, const uint8_t* gathered, int width,
                            int height, int tile_w, int tile_h, int world, int n_frames,

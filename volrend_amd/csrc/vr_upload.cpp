@@ -93,6 +93,9 @@ hipError_t alloc_launch_scratch(VrTreeOpaque* t) {
     if (e == hipSuccess) e = hipMemset(t->status.get(), 0, sizeof(uint32_t));
     if (e == hipSuccess) e = t->sched_stats.alloc(vr::kSchedStats * sizeof(unsigned long long));
     if (e == hipSuccess) e = hipMemset(t->sched_stats.get(), 0, vr::kSchedStats * sizeof(unsigned long long));
+    const size_t cull_sz = (size_t)vr::kCullStatLines * vr::kCullStatStride * sizeof(unsigned long long);
+    if (e == hipSuccess) e = t->cull_stats.alloc(cull_sz);
+    if (e == hipSuccess) e = hipMemset(t->cull_stats.get(), 0, cull_sz);
     if (e == hipSuccess) e = t->probe_buf.alloc(sizeof(float) * (size_t)t->desc.data_dim * kLaunchSlots);
     for (unsigned i = 0; i < kLaunchSlots && e == hipSuccess; ++i) e = t->slots[i].done.create();
     if (e == hipSuccess) e = t->slot_frames.alloc(sizeof(vr::FrameDesc) * vr::kMaxBatch * kLaunchSlots);
@@ -273,6 +276,19 @@ hipError_t build_lookup(const LookupPlan& plan, const std::vector<int32_t>& bric
     return e;
 }
 
+// Step: the occupancy of the block cull (vr_internal.h "Block cull") for a tree that has its lookup structure:
+// allocated for the worst case -- every cell in the list -- and built from the node words.
+hipError_t build_occupancy(VrTreeOpaque* t) {
+    if (t->top_levels <= 0) return hipSuccess;
+    const int deepest = t->max_depth + 1;  // depth of the deepest leaf
+    t->occ_levels = deepest < vr::kOccMaxLevels ? deepest : vr::kOccMaxLevels;
+    const size_t bytes = vr::occ_words(t->occ_levels) * sizeof(uint32_t);
+    hipError_t e = t->occ.alloc(bytes);
+    if (e == hipSuccess) e = refresh_occupancy(t, nullptr);
+    t->device_bytes += bytes;
+    return e;
+}
+
 // Step: the extra array (SG / ASG lobes), from wherever the caller's arrays are.
 hipError_t upload_extra(const UploadJob& j, VrTreeOpaque* t) {
     if (!j.d->extra || !j.d->extra_count) return hipSuccess;
@@ -331,6 +347,7 @@ int upload_steps(const UploadJob& j, vr_tree_t* out) {
     if (e == hipSuccess && plan.G0 > 0) e = build_lookup(plan, brick_roots, t.get(), d_roots, flag);
     if (e == hipSuccess && flag != 0)
         return fail(VR_ERR_BAD_TREE, "lookup structure build failed (flag %u)", flag);
+    if (e == hipSuccess) e = build_occupancy(t.get());
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = upload_extra(j, t.get());
     if (e != hipSuccess) return fail(hip_code(e), "tree upload failed: %s", hipGetErrorString(e));
@@ -366,6 +383,11 @@ int upload_impl(const VrTreeDesc* d, const VrQuantDesc* q, vr_tree_t* out) {
 }
 
 }  // namespace
+
+hipError_t refresh_occupancy(const VrTreeOpaque* t, hipStream_t hs) {
+    if (!t->occ) return hipSuccess;
+    return vr::launch_build_occupancy(t->arrays[kNodes].get<uint32_t>(), t->occ_levels, t->occ.get<uint32_t>(), hs);
+}
 
 extern "C" {
 
@@ -443,6 +465,7 @@ int vr_tree_clone(vr_tree_t src, int device, vr_tree_t* out) {
     hipError_t e = hipSuccess;
     for (int i = 0; i < 4 && e == hipSuccess; ++i) e = copy(t->arrays[i], src->arrays[i]);
     if (e == hipSuccess) e = copy(t->extra, src->extra);
+    if (e == hipSuccess) e = copy(t->occ, src->occ);  // (bitmap and list travel with the arrays they were built from)
     if (e == hipSuccess) e = alloc_launch_scratch(t.get());
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess)

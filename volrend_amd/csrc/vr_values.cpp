@@ -66,6 +66,7 @@ int tree_data_pass(vr_tree_t t, void* data_dev, int dtype, void* stream, bool up
         HIP_TRY(vr::launch_refresh_lookup(a.nodes, t->brick_root_dev.get<int32_t>(), t->n_bricks,
                                           t->arrays[kTop].get<uint2>(), t->arrays[kBricks].get<uint32_t>(),
                                           t->top_levels, t->brick_levels, hs));
+    HIP_TRY(refresh_occupancy(t, hs));
     return VR_OK;
 }
 
@@ -141,6 +142,7 @@ int vr_tree_step(vr_tree_t t, const VrStep* s, void* stream) {
         HIP_TRY(vr::launch_refresh_lookup(a.nodes, t->brick_root_dev.get<int32_t>(), t->n_bricks,
                                           t->arrays[kTop].get<uint2>(), t->arrays[kBricks].get<uint32_t>(),
                                           t->top_levels, t->brick_levels, hs));
+    HIP_TRY(refresh_occupancy(t, hs));
     return VR_OK;
 }
 
