@@ -557,3 +557,57 @@ class FakeCudaTensor:
 
     def dim(self):
         return len(self.shape)
+
+
+# ---- child arrays for the host walks (tests/test_tree_walk.py, tests/test_weights_file_order.py) ------------------
+def rows_of(tree):
+    return tree.child.reshape(tree.capacity, -1).astype(np.int64)
+
+
+def scrambled(child, seed=7):
+    """The construction of tests/test_gpu_chain.py::test_tree_with_backward_links on the child array:
+    the nodes in a random order, root first.  -> (new child array, new index of every old node)."""
+    cap = child.shape[0]
+    new_of = np.concatenate([[0], 1 + np.random.default_rng(seed).permutation(cap - 1)])
+    tgt = np.where(child != 0, np.arange(cap)[:, None] + child, -1)
+    out = np.zeros_like(child)
+    out[new_of] = np.where(tgt >= 0, new_of[np.maximum(tgt, 0)] - new_of[:, None], 0)
+    return out, new_of
+
+
+def with_unreachable(child):
+    """Five nodes behind the tree that nothing links to: one links on to the next, one back into the tree."""
+    extra = np.zeros((5, child.shape[1]), np.int64)
+    extra[1, 2] = 1
+    extra[3, 0] = -(child.shape[0] + 2)       # -> node 1 of the tree
+    return np.concatenate([child, extra])
+
+
+# ---- one frame on the GPU against the oracle (torch is handed in) --------------------------------------------------
+def gpu_frame(torch, tree, transform, w, h, focal, fp_mode=0, ndc=None, offscreen=True,
+              rgba_init=None, depth_init=None, shard=None, fy=None, **opt_kw):
+    from volrend_amd import api
+    t = api.N3Tree.from_synth(tree, ndc=ndc)
+    cam = api.Camera(w, h, focal, focal if fy is None else fy)
+    cam.transform = np.asarray(transform, dtype=np.float32)
+    opts = api.RenderOptions(**opt_kw)
+    if rgba_init is not None:
+        img = torch.from_numpy(rgba_init.copy()).cuda()
+    else:
+        img = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
+    acc = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
+    dep = torch.from_numpy(depth_init).cuda() if depth_init is not None else None
+    api.launch_renderer(t, cam, opts, img, dep, torch.cuda.current_stream(), offscreen,
+                        accum=acc, shard=shard, fp_mode=fp_mode)
+    torch.cuda.synchronize()
+    out = img.cpu().numpy(), acc.cpu().numpy()
+    t.free_device()
+    return out
+
+
+def assert_parity(rgba_g, acc_g, rgba_o, acc_o):
+    ulp = ulp_diff(acc_g, acc_o)
+    bad_px = int((rgba_g != rgba_o).any(-1).sum())
+    assert ulp.max() <= 1, f"accumulators differ by up to {ulp.max()} ulp"
+    assert bad_px == 0, f"{bad_px} RGBA8 pixels differ"
+    assert np.array_equal(acc_g.view(np.uint32), acc_o.view(np.uint32)), "accumulators not bit-equal"

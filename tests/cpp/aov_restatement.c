@@ -1,99 +1,12 @@
 /*
  * aov_restatement.c -- the yardstick of the vr_render_aov tests (TEST INFRASTRUCTURE).
  *
- * The oracle has no depth sum D and no final transmittance T of their own: its depth mode only
- * shows min(0.3 * D, 1), rescaled at an early stop.  This file restates the loop of trace_ray
- * (oracle/vr_oracle_core.inc, rt_core.cuh:108-175) WITHOUT the colour and hands out, per pixel,
- *   D      = sum of weight * t over the hit samples, in order (D = weight * t + D: two roundings in
- *            the strict model, one fused operation in the FMA model),
- *   T      = light_intensity when the ray leaves the loop,
- *   ds     = delta_scale of the ray (1 for a tree with N <= 0),
- *   stop   = 1 where stop_thresh ended the ray.
- * Everything around the loop -- ray generation, NDC warp, the ray/box test, the tree query, the
- * step -- is the oracle's own code, included and called.  tests/test_aov_restatement.py ties D, T
- * and stop back to or_render on every pixel.
- *
- * Build: gcc -O2 -std=c11 -ffp-contract=off -mfma -fPIC -shared -I oracle (the oracle's flags).
+ * The oracle has no depth sum D and no final transmittance T of their own: its depth mode only shows
+ * min(0.3 * D, 1), rescaled at an early stop.  This file hands out, per pixel, what the one restatement of
+ * the march (march_restatement.h) gives of a ray: D, T, ds = delta_scale and stop.
+ * tests/test_aov_restatement.py ties D, T and stop back to or_render on every pixel.
  */
-#define _GNU_SOURCE
-#include <math.h>
-#include <stdint.h>
-#include <string.h>
-
-#include "vr_oracle.h"
-#include "vr_detmath.h"
-
-#define VR_FMA 0
-#include "vr_oracle_core.inc"
-#undef VR_FMA
-#define VR_FMA 1
-#include "vr_oracle_core.inc"
-#undef VR_FMA
-
-static inline float madd_strict(float a, float b, float c) { return a * b + c; }
-static inline float madd_fma(float a, float b, float c) { return fmaf(a, b, c); }
-
-#define DEFINE_AOV_PIXEL(M)                                                                          \
-    static void aov_pixel_##M(const OrTree* tree, const OrCamera* cam, const OrOptions* opt,          \
-                              int offscreen, const float* depth_init, int x, int y, float* D_out,     \
-                              float* T_out, float* ds_out, uint8_t* stop_out) {                       \
-        float D = 0.f, light = 1.f, dir[3], cen[3];                                                   \
-        *D_out = 0.f;                                                                                 \
-        *T_out = 1.f;                                                                                 \
-        *ds_out = 1.f;                                                                                \
-        *stop_out = 0;                                                                                \
-        if (!(tree->N > 0)) return;                                                                   \
-        /* render_pixel, volrend.cu:135-148 */                                                        \
-        screen2worlddir_##M(x, y, cam, dir, cen);                                                     \
-        maybe_world2ndc_##M(tree, dir, cen);                                                          \
-        for (int i = 0; i < 3; ++i) cen[i] = madd_##M(tree->scale[i], cen[i], tree->offset[i]);       \
-        float tmax_bg = 1e9f;                                                                         \
-        if (!offscreen && depth_init) tmax_bg = depth_init[(size_t)y * (size_t)cam->width + x];       \
-        /* trace_ray up to the ray/box test, rt_core.cuh:52-92 */                                     \
-        dir[0] *= tree->scale[0];                                                                     \
-        dir[1] *= tree->scale[1];                                                                     \
-        dir[2] *= tree->scale[2];                                                                     \
-        const float delta_scale = 1.f / norm3_##M(dir);                                               \
-        dir[0] *= delta_scale;                                                                        \
-        dir[1] *= delta_scale;                                                                        \
-        dir[2] *= delta_scale;                                                                        \
-        tmax_bg /= delta_scale;                                                                       \
-        *ds_out = delta_scale;                                                                        \
-        float tmin, tmax, invdir[3];                                                                  \
-        for (int i = 0; i < 3; ++i) invdir[i] = (float)(1.0 / ((double)dir[i] + 1e-9));               \
-        dda_world_##M(cen, invdir, &tmin, &tmax, opt->render_bbox);                                   \
-        tmax = vr_minf(tmax, tmax_bg);                                                                \
-        if (tmax < 0 || tmin > tmax) return;                                                          \
-        /* the loop, rt_core.cuh:108-175, without the colour */                                       \
-        float t = tmin, cube_sz, pos[3];                                                              \
-        while (t < tmax) {                                                                            \
-            pos[0] = madd_##M(t, dir[0], cen[0]);                                                     \
-            pos[1] = madd_##M(t, dir[1], cen[1]);                                                     \
-            pos[2] = madd_##M(t, dir[2], cen[2]);                                                     \
-            int levels;                                                                               \
-            const int64_t leaf = query_##M(tree, pos, &cube_sz, &levels);                             \
-            const uint16_t* tree_val = tree->data + leaf * tree->data_dim;                            \
-            const float t_subcube = dda_unit_##M(pos, invdir) / cube_sz;                              \
-            const float delta_t = t_subcube + opt->step_size;                                         \
-            const float sigma = vr_half_bits_to_float(tree_val[tree->data_dim - 1]);                  \
-            if (sigma > opt->sigma_thresh) {                                                          \
-                const float att = vr_det_expf(-delta_t * delta_scale * sigma);                        \
-                const float weight = light * (1.f - att);                                             \
-                D = madd_##M(weight, t, D);                                                           \
-                light *= att;                                                                         \
-                if (light < opt->stop_thresh) {                                                       \
-                    *stop_out = 1;                                                                    \
-                    break;                                                                            \
-                }                                                                                     \
-            }                                                                                         \
-            t += delta_t;                                                                             \
-        }                                                                                             \
-        *D_out = D;                                                                                   \
-        *T_out = light;                                                                               \
-    }
-
-DEFINE_AOV_PIXEL(strict)
-DEFINE_AOV_PIXEL(fma)
+#include "march_restatement.h"
 
 /* All pixels of a frame; D, T, ds: [height][width] floats, stop: [height][width] bytes. */
 int aov_restate(const OrTree* tree, const OrCamera* cam, const OrOptions* opt, int fp_mode, int offscreen,
@@ -102,10 +15,12 @@ int aov_restate(const OrTree* tree, const OrCamera* cam, const OrOptions* opt, i
     for (int y = 0; y < cam->height; ++y)
         for (int x = 0; x < cam->width; ++x) {
             const size_t i = (size_t)y * (size_t)cam->width + (size_t)x;
-            if (fp_mode == OR_FP_FMA)
-                aov_pixel_fma(tree, cam, opt, offscreen, depth_init, x, y, D + i, T + i, ds + i, stop + i);
-            else
-                aov_pixel_strict(tree, cam, opt, offscreen, depth_init, x, y, D + i, T + i, ds + i, stop + i);
+            MarchRay ray;
+            march_pixel(tree, cam, opt, fp_mode, offscreen, depth_init, x, y, &ray, NULL, NULL);
+            D[i] = ray.D;
+            T[i] = ray.T;
+            ds[i] = ray.delta_scale;
+            stop[i] = (uint8_t)ray.stopped;
         }
     return 0;
 }

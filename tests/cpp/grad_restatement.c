@@ -2,11 +2,10 @@
  * grad_restatement.c -- the yardstick of the vr_render_backward tests (TEST INFRASTRUCTURE).
  *
  * Two steps.
- *   grad_trace_frame   marches every pixel of one offscreen frame with the oracle's own binary32 code
- *                      (oracle/vr_oracle_core.inc, either FP model: ray generation, NDC warp, the ray/box test,
- *                      the tree query, the step, the attenuation and the stop test of trace_ray,
- *                      rt_core.cuh:66-196) and RECORDS what the differentiation treats as constants: per ray its
- *                      pixel, its basis values, whether stop_thresh ended it, and per hit sample (sigma >
+ *   grad_trace_frame   marches every pixel of one offscreen frame with the one restatement of the march
+ *                      (march_restatement.h, either FP model) and RECORDS what the differentiation treats as
+ *                      constants: per ray its pixel, its basis values (the oracle's precalc_basis; zero for a ray
+ *                      that misses the box), whether stop_thresh ended it, and per hit sample (sigma >
  *                      sigma_thresh) the leaf slot in the file's numbering and delta = fl(delta_t * delta_scale).
  *   grad_eval64 / grad_eval32   evaluate the formulas of include/volrend_hip.h (vr_render_backward) on such a
  *                      record, with the VALUES (sigma and the record entries) taken from an array the caller
@@ -35,24 +34,8 @@
  *                        1  dc formed without the (1 - c) factor
  *                        2  R_i formed in binary32 as total minus running prefix
  *                        3  the not-stopped tail g_3 T_{K+1} used for stopped rays
- *
- * Build: gcc -O2 -std=c11 -ffp-contract=off -mfma -fPIC -shared -I oracle (the oracle's flags).
  */
-#define _GNU_SOURCE
-#include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include "vr_oracle.h"
-#include "vr_detmath.h"
-
-#define VR_FMA 0
-#include "vr_oracle_core.inc"
-#undef VR_FMA
-#define VR_FMA 1
-#include "vr_oracle_core.inc"
-#undef VR_FMA
+#include "march_restatement.h"
 
 /* A contribution is a chain of binary32 products; one whose result is subnormal carries an absolute error of half
  * the smallest subnormal, 2^-150.  Per contribution U gets 2^-20: 2^-126 * 2^-20 = eight smallest subnormals. */
@@ -61,9 +44,6 @@
 #ifndef GRAD_MUTANT
 #define GRAD_MUTANT 0
 #endif
-
-static inline float madd_strict(float a, float b, float c) { return a * b + c; }
-static inline float madd_fma(float a, float b, float c) { return fmaf(a, b, c); }
 
 typedef struct {
     int64_t slot;  /* node * N^3 + child slot, file numbering */
@@ -86,7 +66,11 @@ typedef struct {
     int32_t data_dim, basis_dim, n_basis; /* n_basis: basis functions the renderer uses; 0 = RGBA */
 } GradTrace;
 
-static int push_hit(GradTrace* tr, int64_t slot, float delta) {
+/* MarchHit: records the sample */
+static int push_hit(void* ctx, int64_t slot, float t, float delta, float weight) {
+    GradTrace* tr = (GradTrace*)ctx;
+    (void)t;
+    (void)weight;
     if (tr->n_hits == tr->cap_hits) {
         const int64_t cap = tr->cap_hits ? tr->cap_hits * 2 : 4096;
         GradHit* h = (GradHit*)realloc(tr->hits, (size_t)cap * sizeof(GradHit));
@@ -99,64 +83,6 @@ static int push_hit(GradTrace* tr, int64_t slot, float delta) {
     tr->n_hits++;
     return 0;
 }
-
-#define DEFINE_TRACE_PIXEL(M)                                                                         \
-    static int trace_pixel_##M(const OrTree* tree, const OrCamera* cam, const OrOptions* opt, int x,  \
-                               int y, GradTrace* tr, GradRay* ray) {                                  \
-        float light = 1.f, dir[3], cen[3];                                                            \
-        ray->pixel = y * cam->width + x;                                                              \
-        ray->stopped = 0;                                                                             \
-        ray->first = tr->n_hits;                                                                      \
-        ray->n = 0;                                                                                   \
-        for (int i = 0; i < 25; ++i) ray->basis[i] = 0.f;                                             \
-        if (!(tree->N > 0)) return 0;                                                                 \
-        screen2worlddir_##M(x, y, cam, dir, cen);                                                     \
-        const float vdir[3] = {dir[0], dir[1], dir[2]};                                               \
-        maybe_world2ndc_##M(tree, dir, cen);                                                          \
-        for (int i = 0; i < 3; ++i) cen[i] = madd_##M(tree->scale[i], cen[i], tree->offset[i]);       \
-        float tmax_bg = 1e9f;                                                                         \
-        dir[0] *= tree->scale[0];                                                                     \
-        dir[1] *= tree->scale[1];                                                                     \
-        dir[2] *= tree->scale[2];                                                                     \
-        const float delta_scale = 1.f / norm3_##M(dir);                                               \
-        dir[0] *= delta_scale;                                                                        \
-        dir[1] *= delta_scale;                                                                        \
-        dir[2] *= delta_scale;                                                                        \
-        tmax_bg /= delta_scale;                                                                       \
-        float tmin, tmax, invdir[3];                                                                  \
-        for (int i = 0; i < 3; ++i) invdir[i] = (float)(1.0 / ((double)dir[i] + 1e-9));               \
-        dda_world_##M(cen, invdir, &tmin, &tmax, opt->render_bbox);                                   \
-        tmax = vr_minf(tmax, tmax_bg);                                                                \
-        if (tmax < 0 || tmin > tmax) return 0;                                                        \
-        if (tr->n_basis > 0) precalc_basis_##M(tree, vdir, ray->basis);                               \
-        float t = tmin, cube_sz, pos[3];                                                              \
-        while (t < tmax) {                                                                            \
-            pos[0] = madd_##M(t, dir[0], cen[0]);                                                     \
-            pos[1] = madd_##M(t, dir[1], cen[1]);                                                     \
-            pos[2] = madd_##M(t, dir[2], cen[2]);                                                     \
-            int levels;                                                                               \
-            const int64_t leaf = query_##M(tree, pos, &cube_sz, &levels);                             \
-            const uint16_t* tree_val = tree->data + leaf * tree->data_dim;                            \
-            const float t_subcube = dda_unit_##M(pos, invdir) / cube_sz;                              \
-            const float delta_t = t_subcube + opt->step_size;                                         \
-            const float sigma = vr_half_bits_to_float(tree_val[tree->data_dim - 1]);                  \
-            if (sigma > opt->sigma_thresh) {                                                          \
-                const float att = vr_det_expf(-delta_t * delta_scale * sigma);                        \
-                if (push_hit(tr, leaf, delta_t * delta_scale)) return 1;                              \
-                ray->n++;                                                                             \
-                light *= att;                                                                         \
-                if (light < opt->stop_thresh) {                                                       \
-                    ray->stopped = 1;                                                                 \
-                    break;                                                                            \
-                }                                                                                     \
-            }                                                                                         \
-            t += delta_t;                                                                             \
-        }                                                                                             \
-        return 0;                                                                                     \
-    }
-
-DEFINE_TRACE_PIXEL(strict)
-DEFINE_TRACE_PIXEL(fma)
 
 void grad_trace_free(GradTrace* tr) {
     if (!tr) return;
@@ -186,12 +112,19 @@ GradTrace* grad_trace_frame(const OrTree* tree, const OrCamera* cam, const OrOpt
     }
     for (int y = 0; y < cam->height; ++y)
         for (int x = 0; x < cam->width; ++x) {
-            GradRay* ray = tr->rays + ((int64_t)y * cam->width + x);
-            const int rc = fp_mode == OR_FP_FMA ? trace_pixel_fma(tree, cam, opt, x, y, tr, ray)
-                                                : trace_pixel_strict(tree, cam, opt, x, y, tr, ray);
-            if (rc) {
+            GradRay* ray = tr->rays + ((int64_t)y * cam->width + x); /* (calloc: basis is zero for a miss) */
+            MarchRay m;
+            ray->pixel = y * cam->width + x;
+            ray->first = tr->n_hits;
+            if (march_pixel(tree, cam, opt, fp_mode, 1, NULL, x, y, &m, push_hit, tr)) {
                 grad_trace_free(tr);
                 return NULL;
+            }
+            ray->n = tr->n_hits - ray->first;
+            ray->stopped = m.stopped;
+            if (m.entered && tr->n_basis > 0) {
+                if (fp_mode == OR_FP_FMA) precalc_basis_fma(tree, m.vdir, ray->basis);
+                else precalc_basis_strict(tree, m.vdir, ray->basis);
             }
         }
     return tr;

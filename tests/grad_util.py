@@ -1,26 +1,16 @@
-"""Helpers of the vr_render_backward tests: the C restatement of trace_ray's loop with the derivative's formulas
-(tests/cpp/grad_restatement.c), compiled on first use with the oracle's flags, and the cases the CPU and GPU
-tests share.  Scenes and option sets are those of tests/aov_util.py."""
+"""Helpers of the vr_render_backward tests: the record of the hits of the C restatement of the march with the
+derivative's formulas on it (tests/cpp/grad_restatement.c over march_restatement.h), and the cases the CPU and
+GPU tests share.  Scenes and option sets are those of tests/aov_util.py."""
 from __future__ import annotations
 
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import aov_util as au
-from tests import common
+from tests import build_util, common
 from tests.common import ob
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "grad_restatement.c")
-_lib = None
-_mutants = {}
 
 EPS32 = 2.0 ** -24
 TINY32 = 2.0 ** -126
@@ -35,27 +25,11 @@ K = 4.0 * K32
 OPTION_SETS = au.OPTION_SETS
 
 
+@functools.lru_cache(maxsize=None)
 def lib(mutant=0):
     """The restatement; mutant = 1..3 builds it with -DGRAD_MUTANT (one deliberate mistake in grad_eval32, see the
     source), for the tests that show the error unit sees the mistake."""
-    global _lib
-    if mutant:
-        if mutant not in _mutants:
-            _mutants[mutant] = _build(mutant)
-        return _mutants[mutant]
-    if _lib is None:
-        _lib = _build(0)
-    return _lib
-
-
-def _build(mutant):
-    td = tempfile.mkdtemp(prefix="vr_grad_restate_")
-    atexit.register(shutil.rmtree, td, ignore_errors=True)
-    so = os.path.join(td, "libgrad_restatement.so")
-    subprocess.check_call(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-mfma", "-fPIC", "-shared",
-                           "-Wno-unused-function", f"-DGRAD_MUTANT={mutant}", "-I", os.path.join(ROOT, "oracle"),
-                           SRC, "-o", so, "-lm"])
-    L = C.CDLL(so)
+    L = build_util.c_library("grad_restatement.c", (f"-DGRAD_MUTANT={mutant}",))
     L.grad_trace_frame.restype = C.c_void_p
     L.grad_trace_frame.argtypes = [C.POINTER(ob.OrTree), C.POINTER(ob.OrCamera), C.POINTER(ob.OrOptions), C.c_int]
     L.grad_trace_free.restype = None
@@ -88,6 +62,7 @@ class Trace:
         opt = ob.default_options(**opt_kw)
         self.w, self.h = w, h
         self.shape = tuple(tree.data.shape)
+        self._free = lib().grad_trace_free      # (kept here: module globals may be gone when __del__ runs)
         self.ptr = lib().grad_trace_frame(C.byref(th.struct), C.byref(cam), C.byref(opt), fp_mode)
         assert self.ptr
         self.n_hits = np.zeros(w * h, np.int64)
@@ -96,8 +71,8 @@ class Trace:
         self.stopped = stopped.astype(bool)
 
     def __del__(self):
-        if getattr(self, "ptr", None) and _lib is not None:
-            _lib.grad_trace_free(self.ptr)
+        if getattr(self, "ptr", None):
+            self._free(self.ptr)
             self.ptr = None
 
     def slots(self, ray):
@@ -406,3 +381,74 @@ def worst_edge_ratio(got, ref, start=None, slack=None):
     zero = clean & ~pos
     same = np.asarray(got, np.float32).view(np.uint32)[zero] == start.view(np.uint32)[zero]
     return ratio, int(pos.sum()), bool(same.all())
+
+
+# ---- shared by the GPU tests (torch is handed in: the module imports without it) -----------------------------------
+def sentinel(shape):
+    """Finite, non-zero, different from element to element: x + 0 == x bit for bit, and a write shows."""
+    n = int(np.prod(shape))
+    return ((np.arange(n, dtype=np.int64) % 251 + 1).astype(np.float32) * np.float32(2.0 ** -40)).reshape(shape)
+
+
+def upload(ref, name=None):
+    from volrend_amd import api
+    blocked = name == "blocked"
+    if blocked:
+        api.set_tuning(top_levels=2, brick_levels=3, brick_blocked=1)
+    try:
+        t = api.N3Tree.from_synth(ref["tree"], ndc=ref["ndc"])
+    finally:
+        if blocked:
+            api.set_tuning(top_levels=0, brick_levels=3, brick_blocked=-1)
+    if blocked:
+        assert t.info()["brick_blocked"] == 1
+    return t
+
+
+def assert_parity(got, ref, start=None, k=K, what=""):
+    """Every element: |got - start - grad| <= k * unit; elements with M == 0 keep the bits of `start`."""
+    start = np.zeros(ref["grad"].shape, np.float32) if start is None else start
+    diff = np.abs(got.astype(np.float64) - start.astype(np.float64) - ref["grad"])
+    u = unit(ref)
+    pos = ref["mag"] > 0
+    # (a buffer that starts from `start` rounds every add relative to a running value that holds it: 2^-24
+    # |start| per contribution at most, and U * 2^20 bounds their number -- every contribution adds 2^-20 to U)
+    slack = ref["under"] * 2.0 ** 20 * EPS32 * np.abs(start.astype(np.float64))
+    worst = float((np.maximum(diff - slack, 0.0)[pos] / u[pos]).max())
+    print(f"{what}: worst |gpu - f64| / unit = {worst:.3f} of {k} over {int(pos.sum())} elements")
+    assert worst <= k, what
+    same = got.view(np.uint32) == start.view(np.uint32)
+    assert same[~pos].all(), f"{what}: {int((~same[~pos]).sum())} elements nothing touches were written"
+
+
+def upload_edge(ref):
+    return upload(ref, "blocked" if ref["blocked"] else None)
+
+
+def assert_edge_parity(got, ref, start=None, what=""):
+    """An edge case (EDGE_CASES): clean elements with M > 0 within K_EDGE * unit_edge (plus the slack of
+    assert_parity for a buffer that starts from `start`), clean elements with M == 0 and every slot no ray hits
+    -- interior slots included -- bit-identical to `start`.  Dirty slots are not looked at."""
+    start = np.zeros(ref["grad"].shape, np.float32) if start is None else start
+    with np.errstate(invalid="ignore"):
+        slack = ref["under"] * 2.0 ** 20 * EPS32 * np.abs(start.astype(np.float64))
+    worst, n, zeros_same = worst_edge_ratio(got, ref, start, slack)
+    print(f"{what}: worst |gpu - f64| / unit_edge = {worst:.3f} of {K_EDGE} over {n} clean elements; "
+          f"{int(ref['dirty'].sum())} of {int(ref['hit'].sum())} hit slots dirty")
+    assert n >= 200, "the case shows nothing"
+    assert worst <= K_EDGE, what
+    assert zeros_same, f"{what}: a clean element with M == 0 was written"
+    dd = ref["grad"].shape[-1]
+    same = (got.view(np.uint32) == start.view(np.uint32)).reshape(-1, dd)
+    assert same[~ref["hit"]].all(), f"{what}: {int((~same[~ref['hit']]).any(1).sum())} slots no ray hits were written"
+    interior = np.asarray(ref["tree"].child).reshape(-1) != 0
+    assert interior.any() and not ref["hit"][interior].any()
+    return worst
+
+
+def assert_contained(got, ref, start, what=""):
+    """assert_edge_parity, and the case shows something: a dirty slot holds a non-finite value afterwards."""
+    assert_edge_parity(got, ref, start, what)
+    dd = ref["grad"].shape[-1]
+    assert ref["dirty"].any() and not np.isfinite(got.reshape(-1, dd)[ref["dirty"]]).all(), \
+        f"{what}: no dirty slot holds a non-finite value"

@@ -4,10 +4,10 @@ import ctypes as C
 import os
 import re
 import subprocess
-import tempfile
 
 import pytest
 
+from tests import build_util
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,24 +52,12 @@ def test_struct_layouts_match_the_c_compiler():
                "VrTreeInfo": _abi.VrTreeInfo,
                "VrCamera": _abi.VrCamera, "VrRenderOptions": _abi.VrRenderOptions,
                "VrFrame": _abi.VrFrame}
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "volrend_hip.h"',
-             'int main(void){']
     for name, st in structs.items():
-        lines.append(f'printf("{name} %zu\\n", sizeof({name}));')
+        got = build_util.c_struct_layout(name, st, [("VrCounters", "sizeof(VrCounters)")])
+        assert got["size"] == C.sizeof(st), name
         for fname, _ in st._fields_:
-            lines.append(f'printf("{name}.{fname} %zu\\n", offsetof({name}, {fname}));')
-    lines.append('printf("VrCounters %zu\\n", sizeof(VrCounters)); return 0;}')
-    with tempfile.TemporaryDirectory() as td:
-        src = os.path.join(td, "layout.c")
-        open(src, "w").write("\n".join(lines))
-        exe = os.path.join(td, "layout")
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = dict(l.split() for l in subprocess.check_output([exe], text=True).splitlines())
-    for name, st in structs.items():
-        assert int(got[name]) == C.sizeof(st), name
-        for fname, _ in st._fields_:
-            assert int(got[f"{name}.{fname}"]) == getattr(st, fname).offset, f"{name}.{fname}"
-    assert int(got["VrCounters"]) == 8 * len(_abi.COUNTER_FIELDS)
+            assert got[fname] == getattr(st, fname).offset, f"{name}.{fname}"
+    assert got["VrCounters"] == 8 * len(_abi.COUNTER_FIELDS)
 
 
 def test_host_only_entry_points(lib_path):

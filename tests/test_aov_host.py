@@ -5,15 +5,13 @@ that is never followed (and device pointers that are never written)."""
 import ctypes as C
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from volrend_amd import _abi, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, UNSUPPORTED = 1, 5
 TREE, IMG, PLANE = 0x1000, 0x2000, 0x3000   # never dereferenced
 
@@ -38,23 +36,13 @@ def test_symbol_prototype_and_constants(L):
 
 def test_vraov_layout_matches_the_c_compiler():
     st = _abi.VrAov
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "volrend_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(VrAov));',
-             'printf("tree %d\\n", (int)VR_DEPTH_TREE); printf("world %d\\n", (int)VR_DEPTH_WORLD);',
-             'printf("abi %d\\n", (int)VR_ABI_VERSION);']
-    for fname, _ in st._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(VrAov, {fname}));')
-    lines.append("return 0;}")
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "layout.c"), os.path.join(td, "layout")
-        open(src, "w").write("\n".join(lines))
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = dict(l.split() for l in subprocess.check_output([exe], text=True).splitlines())
+    got = build_util.c_struct_layout("VrAov", st, [("tree", "VR_DEPTH_TREE"), ("world", "VR_DEPTH_WORLD"),
+                                                   ("abi", "VR_ABI_VERSION")])
     assert [f for f, _ in st._fields_] == ["depth", "transmittance", "pitch"]
-    assert int(got["size"]) == C.sizeof(st) == 24
+    assert got["size"] == C.sizeof(st) == 24
     for fname, _ in st._fields_:
-        assert int(got[fname]) == getattr(st, fname).offset, fname
-    assert (int(got["tree"]), int(got["world"]), int(got["abi"])) == (0, 1, 3)
+        assert got[fname] == getattr(st, fname).offset, fname
+    assert (got["tree"], got["world"], got["abi"]) == (0, 1, 3)
 
 
 def _args(n=1, w=64, h=48):
@@ -161,16 +149,7 @@ def test_refusals_through_python(L):
 
 
 def test_refusals_through_cpp(L, tmp_path):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    exe = str(tmp_path / "aov_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "aov_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip", "-lz",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.check_output([exe], text=True, stderr=subprocess.DEVNULL)
-    got = dict(l.split(" ", 1) for l in out.splitlines() if not l.startswith("INFO:"))
+    got = build_util.run_key_values(build_util.cpp_program("aov_check", tmp_path), refusals=True)
     for case, word in [("both_null", "NULL"), ("units", "depth_units"), ("pitch_small", "pitch"),
                        ("pitch_odd", "pitch"), ("render_depth", "render_depth"), ("probe", "probe"),
                        ("null_image", "rgba"), ("batch_second_null", "frame 1")]:

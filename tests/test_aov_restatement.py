@@ -1,6 +1,7 @@
 """The yardstick of the vr_render_aov tests is tied to the oracle (no GPU needed).
 
-tests/cpp/aov_restatement.c restates trace_ray's loop without the colour and returns, per pixel,
+tests/cpp/march_restatement.h restates trace_ray's loop without the colour -- the one restatement, which
+the leaf-weight and backward yardsticks march with too -- and tests/cpp/aov_restatement.c returns, per pixel,
 the depth sum D, the final transmittance T, delta_scale and "ended by stop_thresh".  The oracle
 shows both only in disguise, and this test compares those disguises on EVERY pixel, bit for bit
 (NaN == NaN):

@@ -7,11 +7,9 @@ import pytest
 
 from tests import aov_util as au
 from tests import common
+from tests.aov_util import SENTINEL, assert_colour_unchanged, check, host_f32, render_both, sentinel_planes
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = 0x7FC12345   # a NaN payload no computation produces: "this word was never written"
-
 
 @pytest.fixture(scope="module")
 def torch_cuda():
@@ -19,76 +17,6 @@ def torch_cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
     return torch
-
-
-def _planes(torch, n, h, w_words):
-    return torch.full((n, h, w_words), SENTINEL, dtype=torch.int32, device="cuda")
-
-
-def _f32(t):
-    return t.cpu().numpy().view(np.float32)
-
-
-def render_both(torch, t, w, h, f, trs, fp_mode=0, units="tree", offscreen=True, rgba_init=None,
-                depth_init=None, shard=None, stream=None, want=("depth", "transmittance"), pad_words=0, fy=None,
-                **opt_kw):
-    """One vr_render_batch launch and one vr_render_aov launch of the same arguments.
-    -> dict(img0, acc0, img1, acc1, depth, trans) as numpy arrays; planes [n, h, w + pad_words] float32
-    (SENTINEL where never written), depth / trans None when not asked for."""
-    from volrend_amd import api
-    n = len(trs)
-    cam = api.Camera(w, h, f, f if fy is None else fy)
-    opts = api.RenderOptions(**opt_kw)
-    out = {}
-    depths = None if depth_init is None else [torch.from_numpy(depth_init).cuda() for _ in range(n)]
-    dp = _planes(torch, n, h, w + pad_words) if "depth" in want else None
-    tp = _planes(torch, n, h, w + pad_words) if "transmittance" in want else None
-    aov = [api.AovPlanes(dp[i] if dp is not None else None, tp[i] if tp is not None else None,
-                         (w + pad_words) * 4 if pad_words else 0) for i in range(n)]
-    for k, kw in (("0", {}), ("1", dict(aov=aov, depth_units=units))):
-        shape = (n, h, w, 4)
-        if shard is not None and shard.compact:
-            shape = (n, api.compact_bytes(w, h, shard))
-        if rgba_init is not None:
-            img = torch.from_numpy(np.broadcast_to(rgba_init, (n,) + rgba_init.shape).copy()).cuda()
-        else:
-            img = torch.zeros(shape, dtype=torch.uint8, device="cuda")
-        acc = torch.zeros((n, h, w, 4), dtype=torch.float32, device="cuda")
-        api.launch_renderer_batch(t, cam, trs, opts, list(img), stream, offscreen, accums=list(acc),
-                                  depths=depths, shard=shard, fp_mode=fp_mode, **kw)
-        torch.cuda.synchronize()
-        out["img" + k], out["acc" + k] = img.cpu().numpy(), acc.cpu().numpy()
-    assert t.status() == 0
-    out["depth"] = None if dp is None else _f32(dp)
-    out["trans"] = None if tp is None else _f32(tp)
-    return out
-
-
-def assert_colour_unchanged(r, what=""):
-    assert np.array_equal(r["img1"], r["img0"]), f"{what}: RGBA8 differs from vr_render_batch"
-    au.assert_same_bits(r["acc1"], r["acc0"], f"{what}: accum vs vr_render_batch")
-
-
-def check(torch, tree, trs, w, h, f, fp_mode=0, ndc=None, units=("tree", "world"), offscreen=True,
-          rgba_init=None, depth_init=None, tree_tuning=None, fy=None, **opt_kw):
-    """Upload, launch per depth unit, compare every pixel of every frame with the restatement."""
-    from volrend_amd import api
-    t = api.N3Tree.from_synth(tree, ndc=ndc)
-    if tree_tuning:
-        t.set_tuning(**tree_tuning)
-    want = [au.restate(tree, tr, w, h, f, fp_mode, ndc=ndc, offscreen=offscreen, depth_init=depth_init, fy=fy,
-                       **opt_kw)
-            for tr in trs]
-    try:
-        for u in units:
-            r = render_both(torch, t, w, h, f, trs, fp_mode, u, offscreen, rgba_init, depth_init, fy=fy, **opt_kw)
-            assert_colour_unchanged(r, u)
-            for i, (D, T, ds, _) in enumerate(want):
-                au.assert_same_bits(r["depth"][i], D if u == "tree" else au.world_depth(D, ds), f"depth[{u}] frame {i}")
-                au.assert_same_bits(r["trans"][i], T, f"transmittance frame {i}")
-    finally:
-        t.free_device()
-    return want
 
 
 FORMATS = [("SH", 1), ("SH", 4), ("SH", 9), ("SH", 16), ("SH", 25), ("RGBA", 0), ("SG", 9), ("ASG", 4)]
@@ -233,7 +161,7 @@ def test_batches_with_a_pose_per_frame_on_two_streams(torch_cuda):
     cam = api.Camera(w, h, f, f)
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     imgs = torch.zeros((6, h, w, 4), dtype=torch.uint8, device="cuda")
-    dp, tp = _planes(torch, 6, h, w), _planes(torch, 6, h, w)
+    dp, tp = sentinel_planes(torch, 6, h, w), sentinel_planes(torch, 6, h, w)
     torch.cuda.synchronize()
     try:
         for rep in range(3):                       # the two streams alternate over the two halves
@@ -249,8 +177,8 @@ def test_batches_with_a_pose_per_frame_on_two_streams(torch_cuda):
         t.free_device()
     for i, (D, T, _, _) in enumerate(want):
         assert np.array_equal(imgs[i].cpu().numpy(), common.oracle_frame(tree, trs[i], w, h, f)[0]), i
-        au.assert_same_bits(_f32(dp[i]), D, f"depth frame {i}")
-        au.assert_same_bits(_f32(tp[i]), T, f"transmittance frame {i}")
+        au.assert_same_bits(host_f32(dp[i]), D, f"depth frame {i}")
+        au.assert_same_bits(host_f32(tp[i]), T, f"transmittance frame {i}")
 
 
 @pytest.mark.parametrize("compact", [False, True], ids=["frame", "compact"])

@@ -19,11 +19,8 @@ import numpy as np
 import pytest
 
 from tests import common
+from tests import aov_util as au
 from tests import query_util as qu
-from tests import test_gpu_aov as ga
-from tests import test_gpu_parity as gp
-from tests import test_gpu_query as gq
-from tests import test_gpu_weights as gw
 from tests import weights_util as wu
 from tests.common import ob
 
@@ -59,11 +56,11 @@ def chain_case():
 def compare(torch, tree, tr, w, h, fx, fy, fp_mode, ndc=None, nan=False, **kw):
     """One frame on the GPU against the oracle: RGBA8 and accumulators bit for bit."""
     rgba_o, acc_o, cnt = common.oracle_frame(tree, tr, w, h, fx, fp_mode, ndc=ndc, fy=fy, **kw)
-    rgba_g, acc_g = gp.gpu_frame(torch, tree, tr, w, h, fx, fp_mode, ndc=ndc, fy=fy, **kw)
+    rgba_g, acc_g = common.gpu_frame(torch, tree, tr, w, h, fx, fp_mode, ndc=ndc, fy=fy, **kw)
     if nan:
         common.assert_same_values(rgba_g, acc_g, rgba_o, acc_o)
     else:
-        gp.assert_parity(rgba_g, acc_g, rgba_o, acc_o)
+        common.assert_parity(rgba_g, acc_g, rgba_o, acc_o)
     return acc_o, cnt
 
 
@@ -146,7 +143,7 @@ def test_compositing_over_a_mesh_depth_plane(torch_cuda, fp_mode):
 def test_aov_batch_with_a_pose_per_frame(torch_cuda, fp_mode):
     """Both depth units and T over a five-pose batch.  VR_DEPTH_WORLD is D * delta_scale of the ray itself."""
     _, w, h, fx, fy = common.asymmetric_camera()
-    want = ga.check(torch_cuda, common.asymmetric_scene("SH", 16), poses(5), w, h, fx, fp_mode, fy=fy)
+    want = au.check(torch_cuda, common.asymmetric_scene("SH", 16), poses(5), w, h, fx, fp_mode, fy=fy)
     for D, T, ds, stop in want:
         assert (D != 0).mean() >= 0.2 and stop.any()
         assert (ds.max() - ds.min()) / ds.min() > 0.10
@@ -155,15 +152,15 @@ def test_aov_batch_with_a_pose_per_frame(torch_cuda, fp_mode):
 @pytest.mark.parametrize("knobs", KNOBS, ids=KNOB_IDS)
 def test_aov_under_many_refills(torch_cuda, knobs):
     _, w, h, fx, fy = common.asymmetric_camera()
-    ga.check(torch_cuda, common.asymmetric_scene("SH", 16), poses(5), w, h, fx, 0, fy=fy, tree_tuning=knobs)
-    ga.check(torch_cuda, common.asymmetric_scene("SH", 9), poses(5), w, h, fx, 1, fy=fy, units=("world",),
+    au.check(torch_cuda, common.asymmetric_scene("SH", 16), poses(5), w, h, fx, 0, fy=fy, tree_tuning=knobs)
+    au.check(torch_cuda, common.asymmetric_scene("SH", 9), poses(5), w, h, fx, 1, fy=fy, units=("world",),
              tree_tuning=knobs)
 
 
 def test_aov_with_a_mesh_depth_plane(torch_cuda):
     tr, w, h, fx, fy = common.asymmetric_camera()
     init, depth = common.mesh_underlay(w, h)
-    ga.check(torch_cuda, common.asymmetric_scene(), [tr], w, h, fx, 0, fy=fy, offscreen=False, rgba_init=init,
+    au.check(torch_cuda, common.asymmetric_scene(), [tr], w, h, fx, 0, fy=fy, offscreen=False, rgba_init=init,
              depth_init=depth)
 
 
@@ -184,10 +181,10 @@ def check_weights(torch, tree, trs, w, h, fx, fy, want_mw, want_hits, fp_mode, n
     try:
         if tuning:
             t.set_tuning(**tuning)
-        mw, hc = gw.accumulate(torch, t, w, h, fx, trs, fp_mode, tree=tree, fy=fy)
+        mw, hc = wu.accumulate(torch, t, w, h, fx, trs, fp_mode, tree=tree, fy=fy)
         torch.cuda.synchronize()
         assert t.status() == 0
-        wu.assert_same_slots(gw.host(mw), gw.host(hc), *gw.expected(want_mw, want_hits))
+        wu.assert_same_slots(wu.host(mw), wu.host(hc), *wu.expected(want_mw, want_hits))
     finally:
         t.free_device()
     assert (want_hits == 0).any() and (want_mw > 0).sum() > 500, "the case shows nothing"
@@ -229,13 +226,13 @@ def test_world_points(torch_cuda, name):
     present = np.unique(qu.leaf_boxes(tree)[2])
     assert set(np.unique(ans["depth"]).tolist()) >= set(present[present <= 24].tolist())
     # the oracle's answer for a world point IS or_probe_coeffs there (pinned to the reference on this geometry)
-    gq.same_words(ans["coeffs"][::16], qu.probe_coeffs(th, tree, world[::16]), f"{name}: or_probe_coeffs")
+    qu.same_words(ans["coeffs"][::16], qu.probe_coeffs(th, tree, world[::16]), f"{name}: or_probe_coeffs")
     t = api.N3Tree.from_synth(tree)
     try:
-        gq.check_against_oracle(torch_cuda, t, tree, th, world, "world", name, ans)
-        dirs = gq.direction_set(n, 130 + len(name))
-        got = gq.gpu_query(torch_cuda, t, world, dirs, want=("rgb",), space="world")
-        gq.same_words(got["rgb"], qu.recompose_rgb(tree, th, ans["coeffs"], dirs), f"{name} rgb")
+        qu.check_against_oracle(torch_cuda, t, tree, th, world, "world", name, ans)
+        dirs = qu.direction_set(n, 130 + len(name))
+        got = qu.gpu_query(torch_cuda, t, world, dirs, want=("rgb",), space="world")
+        qu.same_words(got["rgb"], qu.recompose_rgb(tree, th, ans["coeffs"], dirs), f"{name} rgb")
     finally:
         t.free_device()
 
@@ -247,7 +244,7 @@ def test_world_grid(torch_cuda):
     tree = common.asymmetric_scene("SH", 9)
     th = ob.TreeHandle(tree)
     lo, hi, res, direction = (-1.5, -1.0, -3.5), (2.2, 0.9, 2.3), (37, 5, 64), (0.3, -0.5, 0.8)
-    coords = gq.grid_coords(lo, hi, res).reshape(-1, 3)
+    coords = qu.grid_coords(lo, hi, res).reshape(-1, 3)
     ans = qu.oracle_answers(tree, th, coords, "world")
     assert (ans["sigma"] > 0).any() and np.unique(ans["depth"]).size > 2
     rgb = qu.recompose_rgb(tree, th, ans["coeffs"], np.broadcast_to(np.float32(direction), coords.shape))
@@ -259,7 +256,7 @@ def test_world_grid(torch_cuda):
                         ("coeffs", ans["coeffs"]), ("rgb", rgb)):
             got = g[k].cpu().numpy()
             assert got.shape[:3] == res, (k, got.shape)
-            gq.same_words(got.reshape(want.shape), want, f"grid {k}")
+            qu.same_words(got.reshape(want.shape), want, f"grid {k}")
     finally:
         t.free_device()
 
@@ -296,7 +293,7 @@ def test_ndc_colour_aov_and_weights(torch_cuda, fp_mode):
     assert (acc_o[..., 3] != 0).mean() >= 0.2
     tr2 = tr.copy()
     tr2[9:12] += np.float32(0.05)
-    ga.check(torch_cuda, tree, [tr, tr2], w, h, fx, fp_mode, ndc=ndc, fy=fy)
+    au.check(torch_cuda, tree, [tr, tr2], w, h, fx, fp_mode, ndc=ndc, fy=fy)
     mw, hc, _ = wu.restate(tree, [tr, tr2], w, h, fx, fp_mode, ndc=ndc, fy=fy)
     check_weights(torch_cuda, tree, [tr, tr2], w, h, fx, fy, mw, hc, fp_mode, ndc=ndc)
 

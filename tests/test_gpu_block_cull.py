@@ -17,7 +17,6 @@ from tests import aov_util as au
 from tests import common
 from tests import cull_util as cu
 from tests import query_util as qu
-from tests import test_gpu_aov as ga
 from tests.common import ob
 
 pytestmark = pytest.mark.gpu
@@ -126,14 +125,14 @@ def test_aov_planes(torch_cuda, name, fp_mode):
     restatement, colour equal to vr_render_batch's; and the AOV launch culls."""
     from volrend_amd import api
     tree, trs, f = scene(name), poses(3), SIZE * 1111.111 / 800.0
-    ga.check(torch_cuda, tree, trs, SIZE, SIZE, f, fp_mode)
+    au.check(torch_cuda, tree, trs, SIZE, SIZE, f, fp_mode)
     t = api.N3Tree.from_synth(tree)
     try:
         t.cull_stats(reset=True)
-        r = ga.render_both(torch_cuda, t, SIZE, SIZE, f, trs, fp_mode)
+        r = au.render_both(torch_cuda, t, SIZE, SIZE, f, trs, fp_mode)
         stats = t.cull_stats()
         t.set_tuning(block_cull=0)
-        r0 = ga.render_both(torch_cuda, t, SIZE, SIZE, f, trs, fp_mode)
+        r0 = au.render_both(torch_cuda, t, SIZE, SIZE, f, trs, fp_mode)
     finally:
         t.free_device()
     assert stats["blocks"] == 2 * 3 * (SIZE // 8) ** 2 and stats["culled"] > 0 and stats["culled"] % 2 == 0

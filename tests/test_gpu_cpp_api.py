@@ -3,36 +3,21 @@ launch_renderer_batch (reference include/volrend/cuda/renderer_kernel.hpp:9-12) 
 RenderOptions field (render_options.hpp:11-53) off its default -- against the CPU oracle.
 renderer.cpp maps the 13 option fields to the C ABI by hand: a swapped or dropped field shows
 here (each case moves fields that change the picture on their own)."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from tests.common import ob
 from volrend_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    out = str(tmp_path_factory.mktemp("bin") / "gpu_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                           "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "gpu_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-pthread",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", out])
-    return out
+    return build_util.cpp_program("gpu_check", tmp_path_factory.mktemp("bin"), gpu=True)
 
 
 CASES = {

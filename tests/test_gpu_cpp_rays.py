@@ -2,38 +2,21 @@
 differentiates a shuffled camera-derived list and writes the results out; each is compared with the yardstick of
 its entry point -- the oracle's frames bit for bit, the leaf-weight restatement bit for bit, the float64 gradient
 within the K of tests/test_gpu_grad.py."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from tests import grad_util as gu
 from tests import rays_util as ru
 from tests import weights_util as wu
 from volrend_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    out = str(tmp_path_factory.mktemp("bin") / "rays_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                           "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "rays_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-pthread",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", out])
-    return out
+    return build_util.cpp_program("rays_check", tmp_path_factory.mktemp("bin"), gpu=True)
 
 
 def test_cpp_ray_calls_match_their_yardsticks(exe, tmp_path):
@@ -54,10 +37,7 @@ def test_cpp_ray_calls_match_their_yardsticks(exe, tmp_path):
     o[idx].tofile(o_raw)
     d[idx].tofile(d_raw)
     np.ascontiguousarray(np.asarray(ref["g"]).reshape(-1, 4)[idx], np.float32).tofile(g_raw)
-    r = subprocess.run([exe, npz, o_raw, d_raw, str(len(idx)), "0", g_raw, prefix], capture_output=True, text=True,
-                       timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    got = dict(line.split() for line in r.stdout.splitlines() if len(line.split()) == 2)   # (the loader prints too)
+    got = build_util.run_key_values(exe, npz, o_raw, d_raw, len(idx), 0, g_raw, prefix)
     assert got["throws"] == "2" and int(got["rays"]) == len(idx)
 
     rgba = np.fromfile(prefix + "rgba.raw", np.uint8).reshape(-1, 4)

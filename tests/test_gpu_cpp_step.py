@@ -2,36 +2,20 @@
 and volrend::tree_step (include/volrend/step.hpp) -- on one tree: tests/cpp/step_check.cpp runs a marked backward
 and one SGD step and writes out what it got; the marks are those of the Python call over the same rays, and master,
 gradient, bitmap and tree are compared bit for bit with the restatement (tests/step_util.py) of its own gradient."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from tests import build_util
 from tests import step_util as su
 from tests import update_util as uu
 from volrend_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    out = str(tmp_path_factory.mktemp("bin") / "step_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                           "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "step_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-pthread",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", out])
-    return out
+    return build_util.cpp_program("step_check", tmp_path_factory.mktemp("bin"), gpu=True)
 
 
 def test_cpp_marked_backward_and_step(exe, tmp_path):
@@ -45,10 +29,7 @@ def test_cpp_marked_backward_and_step(exe, tmp_path):
     for what, a in (("o", o), ("d", d), ("g", g)):
         paths.append(str(tmp_path / f"{what}.raw"))
         np.ascontiguousarray(a, np.float32).tofile(paths[-1])
-    r = subprocess.run([exe, npz, *paths, str(o.shape[0]), repr(float(tgs.LR)), repr(float(tgs.LR_SIGMA)), prefix],
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    got = dict(line.split() for line in r.stdout.splitlines() if len(line.split()) == 2)   # (the loader prints too)
+    got = build_util.run_key_values(exe, npz, *paths, o.shape[0], repr(float(tgs.LR)), repr(float(tgs.LR_SIGMA)), prefix)
     slots = tree.capacity * tree.N ** 3
     assert got["throws"] == "2" and int(got["elements"]) == tree.data.size and int(got["words"]) == su.n_words(slots)
 

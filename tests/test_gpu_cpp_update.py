@@ -1,35 +1,19 @@
 """-m gpu: the C++ wrappers volrend::update_data / read_data (include/volrend/update.hpp) on one tree:
 tests/cpp/update_check.cpp reads the uploaded tree back, writes a second data set into it as binary16 and as
 binary32 and reads it back each time; every array it writes out is compared bit for bit with the file's."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
+from tests import build_util
 from tests import update_util as uu
 from volrend_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    out = str(tmp_path_factory.mktemp("bin") / "update_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                           "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "update_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-pthread",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", out])
-    return out
+    return build_util.cpp_program("update_check", tmp_path_factory.mktemp("bin"), gpu=True)
 
 
 def test_cpp_update_and_read_back(exe, tmp_path):
@@ -39,9 +23,7 @@ def test_cpp_update_and_read_back(exe, tmp_path):
     npz, data, before, after32, after16 = (str(tmp_path / n) for n in ("t.npz", "data.raw", "b16.raw", "a32.raw", "a16.raw"))
     synth.save_npz(tree, npz, compressed=False)
     np.ascontiguousarray(v2).tofile(data)
-    r = subprocess.run([exe, npz, data, before, after32, after16], capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stdout + r.stderr
-    got = dict(line.split() for line in r.stdout.splitlines() if len(line.split()) == 2)   # (the loader prints too)
+    got = build_util.run_key_values(exe, npz, data, before, after32, after16)
     assert got["throws"] == "1" and int(got["elements"]) == v2.size
     want_a, want_b = uu.stored(tree, tree.data), uu.stored(tree, v2)
     assert np.array_equal(np.fromfile(before, np.uint16), want_a.view(np.uint16).reshape(-1))

@@ -13,6 +13,7 @@ import pytest
 
 from tests import common
 from tests import grad_util as gu
+from tests.grad_util import assert_contained, assert_edge_parity, assert_parity, sentinel, upload, upload_edge
 
 pytestmark = pytest.mark.gpu
 FP = pytest.mark.parametrize("fp_mode", [0, 1], ids=["strict", "fma"])
@@ -26,27 +27,6 @@ def torch_cuda():
     return torch
 
 
-def sentinel(shape):
-    """Finite, non-zero, different from element to element: x + 0 == x bit for bit, and a write shows."""
-    n = int(np.prod(shape))
-    return ((np.arange(n, dtype=np.int64) % 251 + 1).astype(np.float32) * np.float32(2.0 ** -40)).reshape(shape)
-
-
-def upload(ref, name=None):
-    from volrend_amd import api
-    blocked = name == "blocked"
-    if blocked:
-        api.set_tuning(top_levels=2, brick_levels=3, brick_blocked=1)
-    try:
-        t = api.N3Tree.from_synth(ref["tree"], ndc=ref["ndc"])
-    finally:
-        if blocked:
-            api.set_tuning(top_levels=0, brick_levels=3, brick_blocked=-1)
-    if blocked:
-        assert t.info()["brick_blocked"] == 1
-    return t
-
-
 def backward(torch, t, ref, fp_mode, g=None, trs=None, grad_data=None, stream=None, opt=None):
     from volrend_amd import api
     g = ref["g"] if g is None else g
@@ -54,22 +34,6 @@ def backward(torch, t, ref, fp_mode, g=None, trs=None, grad_data=None, stream=No
     return t.render_backward(api.Camera(ref["w"], ref["h"], ref["f"], ref["f"]), ref["trs"] if trs is None else trs,
                              api.RenderOptions(**(ref["opt"] if opt is None else opt)), g_dev, grad_data=grad_data,
                              fp_mode=fp_mode, stream=stream)
-
-
-def assert_parity(got, ref, start=None, k=gu.K, what=""):
-    """Every element: |got - start - grad| <= k * unit; elements with M == 0 keep the bits of `start`."""
-    start = np.zeros(ref["grad"].shape, np.float32) if start is None else start
-    diff = np.abs(got.astype(np.float64) - start.astype(np.float64) - ref["grad"])
-    unit = gu.unit(ref)
-    pos = ref["mag"] > 0
-    # (a buffer that starts from `start` rounds every add relative to a running value that holds it: 2^-24
-    # |start| per contribution at most, and U * 2^20 bounds their number -- every contribution adds 2^-20 to U)
-    slack = ref["under"] * 2.0 ** 20 * gu.EPS32 * np.abs(start.astype(np.float64))
-    worst = float((np.maximum(diff - slack, 0.0)[pos] / unit[pos]).max())
-    print(f"{what}: worst |gpu - f64| / unit = {worst:.3f} of {k} over {int(pos.sum())} elements")
-    assert worst <= k, what
-    same = got.view(np.uint32) == start.view(np.uint32)
-    assert same[~pos].all(), f"{what}: {int((~same[~pos]).sum())} elements nothing touches were written"
 
 
 # ---- 5. parity ------------------------------------------------------------------------------------------
@@ -230,39 +194,6 @@ def start_for(ref):
 
 
 # ---- 8. the value domain ---------------------------------------------------------------------------------
-def upload_edge(ref):
-    return upload(ref, "blocked" if ref["blocked"] else None)
-
-
-def assert_edge_parity(got, ref, start=None, what=""):
-    """An edge case of tests/grad_util.py: clean elements with M > 0 within K_EDGE * unit_edge (plus the slack of
-    assert_parity for a buffer that starts from `start`), clean elements with M == 0 and every slot no ray hits
-    -- interior slots included -- bit-identical to `start`.  Dirty slots are not looked at."""
-    start = np.zeros(ref["grad"].shape, np.float32) if start is None else start
-    with np.errstate(invalid="ignore"):
-        slack = ref["under"] * 2.0 ** 20 * gu.EPS32 * np.abs(start.astype(np.float64))
-    worst, n, zeros_same = gu.worst_edge_ratio(got, ref, start, slack)
-    print(f"{what}: worst |gpu - f64| / unit_edge = {worst:.3f} of {gu.K_EDGE} over {n} clean elements; "
-          f"{int(ref['dirty'].sum())} of {int(ref['hit'].sum())} hit slots dirty")
-    assert n >= 200, "the case shows nothing"
-    assert worst <= gu.K_EDGE, what
-    assert zeros_same, f"{what}: a clean element with M == 0 was written"
-    dd = ref["grad"].shape[-1]
-    same = (got.view(np.uint32) == start.view(np.uint32)).reshape(-1, dd)
-    assert same[~ref["hit"]].all(), f"{what}: {int((~same[~ref['hit']]).any(1).sum())} slots no ray hits were written"
-    interior = np.asarray(ref["tree"].child).reshape(-1) != 0
-    assert interior.any() and not ref["hit"][interior].any()
-    return worst
-
-
-def assert_contained(got, ref, start, what=""):
-    """assert_edge_parity, and the case shows something: a dirty slot holds a non-finite value afterwards."""
-    assert_edge_parity(got, ref, start, what)
-    dd = ref["grad"].shape[-1]
-    assert ref["dirty"].any() and not np.isfinite(got.reshape(-1, dd)[ref["dirty"]]).all(), \
-        f"{what}: no dirty slot holds a non-finite value"
-
-
 @pytest.mark.parametrize("name,fp_mode", gu.EDGE_RUNS, ids=gu.EDGE_IDS)
 def test_finite_edge_values_match_the_float64_formulas(torch_cuda, name, fp_mode):
     """Saturated colours and edge densities, all finite (the finite catalogue of tests/grad_util.py), into a

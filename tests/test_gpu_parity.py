@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from tests import common
-from tests.common import ob
+from tests.common import assert_parity, gpu_frame, ob
 
 pytestmark = pytest.mark.gpu
 
@@ -20,35 +20,6 @@ def torch_cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
     return torch
-
-
-def gpu_frame(torch, tree, transform, w, h, focal, fp_mode=0, ndc=None, offscreen=True,
-              rgba_init=None, depth_init=None, shard=None, fy=None, **opt_kw):
-    from volrend_amd import api
-    t = api.N3Tree.from_synth(tree, ndc=ndc)
-    cam = api.Camera(w, h, focal, focal if fy is None else fy)
-    cam.transform = np.asarray(transform, dtype=np.float32)
-    opts = api.RenderOptions(**opt_kw)
-    if rgba_init is not None:
-        img = torch.from_numpy(rgba_init.copy()).cuda()
-    else:
-        img = torch.zeros((h, w, 4), dtype=torch.uint8, device="cuda")
-    acc = torch.zeros((h, w, 4), dtype=torch.float32, device="cuda")
-    dep = torch.from_numpy(depth_init).cuda() if depth_init is not None else None
-    api.launch_renderer(t, cam, opts, img, dep, torch.cuda.current_stream(), offscreen,
-                        accum=acc, shard=shard, fp_mode=fp_mode)
-    torch.cuda.synchronize()
-    out = img.cpu().numpy(), acc.cpu().numpy()
-    t.free_device()
-    return out
-
-
-def assert_parity(rgba_g, acc_g, rgba_o, acc_o):
-    ulp = common.ulp_diff(acc_g, acc_o)
-    bad_px = int((rgba_g != rgba_o).any(-1).sum())
-    assert ulp.max() <= 1, f"accumulators differ by up to {ulp.max()} ulp"
-    assert bad_px == 0, f"{bad_px} RGBA8 pixels differ"
-    assert np.array_equal(acc_g.view(np.uint32), acc_o.view(np.uint32)), "accumulators not bit-equal"
 
 
 @pytest.mark.parametrize("fp_mode", [0, 1])

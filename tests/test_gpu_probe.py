@@ -30,7 +30,7 @@ def _oracle(tree, tr, w, h, f, fp_mode, offscreen=True, rgba_init=None, depth_in
 
 
 def _gpu(torch, tree, tr, w, h, f, fp_mode, **kw):
-    from tests.test_gpu_parity import gpu_frame
+    from tests.common import gpu_frame
     return gpu_frame(torch, tree, tr, w, h, f, fp_mode, **kw)
 
 

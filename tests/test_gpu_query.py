@@ -14,6 +14,8 @@ import pytest
 
 from tests import common, query_util as qu
 from tests.common import ob
+from tests.query_util import (POINT_TREES, check_against_oracle, direction_set,
+                              gpu_query, grid_coords, make_point_tree, same_words)
 
 pytestmark = pytest.mark.gpu
 
@@ -24,61 +26,6 @@ def torch_cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
     return torch
-
-
-# name -> (tree factory, seed of the point set, points by depth); the seeds were chosen on the CPU so
-# that the oracle alone meets the conditions of query_util.check_point_set
-# (tests/test_query_host.py::test_point_sets_meet_their_conditions_on_the_oracle)
-POINT_TREES = {
-    "SH4_d5": (lambda: common.small_scene(depth=5, basis_dim=4, seed=11), 101, False),
-    "SH16_d6": (lambda: common.small_scene(depth=6, basis_dim=16, seed=12), 102, False),
-    "SH1": (lambda: common.small_scene(depth=5, basis_dim=1, seed=13), 103, False),
-    "SH9": (lambda: common.small_scene(depth=5, basis_dim=9, seed=14), 104, False),
-    "SH25": (lambda: common.small_scene(depth=5, basis_dim=25, seed=15), 105, False),
-    "RGBA": (lambda: common.small_scene(depth=5, basis_dim=0, fmt="RGBA", seed=16), 106, False),
-    "SG7": (lambda: common.small_scene(depth=5, basis_dim=7, fmt="SG", seed=17), 107, False),
-    "ASG4": (lambda: common.small_scene(depth=5, basis_dim=4, fmt="ASG", seed=18), 108, False),
-    "edge_SH9": (lambda: common.value_edge_tree("SH", 9, seed=3), 109, False),
-    "fog_SH16": (lambda: common.fog_tree("SH", 16, seed=5, depth=5), 110, False),
-    "N3": (lambda: common.random_tree_general_n(N=3, depth=4, basis_dim=4, seed=21), 111, False),
-    "N4": (lambda: common.random_tree_general_n(N=4, depth=3, basis_dim=9, seed=22), 112, False),
-    "chain28": (lambda: common.deep_chain_tree_n2(28, basis_dim=4, seed=2)[0], 113, True),
-}
-
-
-def make_point_tree(name, n=100_000):
-    factory, seed, by_depth = POINT_TREES[name]
-    tree = factory()
-    return tree, qu.point_set(tree, n, seed, by_depth=by_depth)
-
-
-def same_words(got, want, what):
-    """Bit equality of 32-bit words; a NaN must meet a NaN (any payload)."""
-    got, want = np.ascontiguousarray(got), np.ascontiguousarray(want)
-    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {got.shape} {got.dtype} vs {want.shape}"
-    if got.dtype == np.float32:
-        ng, nw = np.isnan(got), np.isnan(want)
-        assert np.array_equal(ng, nw), f"{what}: NaN in {int((ng & ~nw).sum())} kernel / {int((nw & ~ng).sum())} oracle words only"
-        diff = (got.view(np.uint32) != want.view(np.uint32)) & ~nw
-    else:
-        diff = got != want
-    assert not diff.any(), f"{what}: {int(diff.sum())} of {diff.size} words differ (first at {np.argwhere(diff)[0].tolist()})"
-
-
-def gpu_query(torch, t, pts, dirs=None, want=("sigma", "depth", "local", "coeffs"), space="tree", stream=None):
-    p = torch.from_numpy(np.ascontiguousarray(pts, np.float32)).cuda()
-    d = None if dirs is None else torch.from_numpy(np.ascontiguousarray(dirs, np.float32)).cuda()
-    out = t.query(p, d, want=want, space=space, stream=stream)
-    torch.cuda.synchronize()
-    return {k: v.cpu().numpy() for k, v in out.items()}
-
-
-def check_against_oracle(torch, t, tree, th, pts, space, what, ans=None):
-    ans = ans or qu.oracle_answers(tree, th, pts, space)
-    got = gpu_query(torch, t, pts, space=space)
-    for k in ("sigma", "depth", "local", "coeffs"):
-        same_words(got[k], ans[k], f"{what} {space} {k}")
-    return ans
 
 
 # ---- sigma / depth / local / coeffs ------------------------------------------------------------
@@ -171,19 +118,6 @@ def test_special_coordinates(torch_cuda, name):
 
 
 # ---- colour ---------------------------------------------------------------------------------------
-def direction_set(n, seed):
-    """Unit vectors, un-normalised ones (x 0.3, x 3), exact axes and zero directions."""
-    rng = np.random.default_rng(seed)
-    d = rng.standard_normal((n, 3))
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    d[1::4] *= 0.3
-    d[2::4] *= 3.0
-    d[3::64] = 0.0
-    d[5::64] = (0.0, 0.0, -1.0)
-    d[7::64] = (1.0, 0.0, 0.0)
-    return d.astype(np.float32)
-
-
 RGB_TREES = ["SH1", "SH4_d5", "SH9", "SH16_d6", "SH25", "RGBA", "edge_SH9", "edge_SH16", "edge_RGBA", "N3"]
 
 
@@ -235,19 +169,6 @@ def test_rgb_equals_or_render_on_one_sample_scenes(torch_cuda, fmt, basis_dim):
 
 
 # ---- grid ------------------------------------------------------------------------------------------
-def grid_coords(lo, hi, res):
-    """lo + ((float)i + 0.5f) * ((hi - lo) / (float)res) per axis in float32 -> [r0, r1, r2, 3]."""
-    f32 = np.float32
-    lo, hi = np.asarray(lo, f32), np.asarray(hi, f32)
-    ax = []
-    for a in range(3):
-        cell = (hi[a] - lo[a]) / f32(res[a])
-        ax.append(lo[a] + (np.arange(res[a]).astype(f32) + f32(0.5)) * cell)
-    g = np.stack(np.meshgrid(*ax, indexing="ij"), -1)
-    assert g.dtype == f32
-    return np.ascontiguousarray(g)
-
-
 GRID_CASES = [
     ((0.1, 0.2, 0.15), (0.8, 0.9, 0.7), (37, 5, 64), "tree"),        # inside
     ((-0.3, 0.4, -0.2), (0.6, 1.4, 1.3), (37, 5, 64), "tree"),       # straddling

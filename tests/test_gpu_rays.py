@@ -19,8 +19,8 @@ from tests import common
 from tests import grad_util as gu
 from tests import rays_util as ru
 from tests import weights_util as wu
-from tests.test_gpu_grad import assert_contained, assert_parity, sentinel, upload_edge
-from tests.test_gpu_weights import SENT_W, expected
+from tests.grad_util import assert_contained, assert_parity, sentinel, upload_edge
+from tests.weights_util import SENT_W, expected
 
 pytestmark = pytest.mark.gpu
 FP = pytest.mark.parametrize("fp_mode", [0, 1], ids=["strict", "fma"])

@@ -3,35 +3,20 @@
 render() / set() / clear() / resize() / get_backend(), public camera / options -- against the CPU
 oracle's compositing path (offscreen = 0: the ray march composited over the RGBA8 already in the
 frame, rays ended by the R32F depth image; volrend.cu:142-147,152-165)."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from volrend_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    out = str(tmp_path_factory.mktemp("bin") / "renderer_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                           "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "renderer_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-pthread",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", out])
-    return out
+    return build_util.cpp_program("renderer_check", tmp_path_factory.mktemp("bin"), gpu=True)
 
 
 CAMS = [(-3.0, 0.4, 2.2, -0.75, 0.1, 0.55), (2.5, -2.5, 1.0, 0.66, -0.66, 0.26), (0.3, 3.6, 0.8, 0.05, 0.97, 0.2)]

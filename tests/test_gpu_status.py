@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from volrend_amd import synth
 
 pytestmark = pytest.mark.gpu
@@ -89,16 +89,7 @@ def test_headless_cli_fails_loudly_on_a_guard_trip(torch_cuda, tmp_path, gpus):
 
 
 def test_volume_renderer_fails_loudly_on_a_guard_trip(torch_cuda, tmp_path):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    exe = str(tmp_path / "renderer_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-D__HIP_PLATFORM_AMD__",
-                           "-I", os.path.join(ROOT, "include"), "-I", "/opt/rocm/include",
-                           os.path.join(ROOT, "tests", "cpp", "renderer_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip",
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lz", "-pthread",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
+    exe = build_util.cpp_program("renderer_check", tmp_path, gpu=True)
     npz, _, w, h = _scene_files(tmp_path, 1)
     f = w * 1111.111 / 800.0
     sp = str(tmp_path / "spec.txt")

@@ -16,8 +16,8 @@ from tests import query_util as qu
 from tests import rays_util as ru
 from tests import step_util as su
 from tests import update_util as uu
-from tests.test_gpu_grad import assert_parity
-from tests.test_gpu_update import dev, upload
+from tests.grad_util import assert_parity
+from tests.update_util import dev, upload
 
 pytestmark = pytest.mark.gpu
 LR, LR_SIGMA = 0.5, 3.0      # (both exact in binary32; large enough to move binary16 values)

@@ -12,6 +12,7 @@ import pytest
 
 from tests import common
 from tests import update_util as uu
+from tests.update_util import dev, upload
 
 pytestmark = pytest.mark.gpu
 FP_MODES = (0, 1)
@@ -23,29 +24,6 @@ def torch_cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
     return torch
-
-
-def upload(name, data=None):
-    """The scene with `data` (None: its own), under the scene's upload-time tuning."""
-    from volrend_amd import api
-    c = uu.case(name)
-    tree = c["tree"] if data is None else uu.with_data(c["tree"], data)
-    if c["tuning"]:
-        api.set_tuning(**c["tuning"])
-    try:
-        t = api.N3Tree.from_synth(tree, ndc=c["ndc"])
-    finally:
-        if c["tuning"]:
-            api.set_tuning(top_levels=0, brick_levels=3, brick_blocked=-1)
-    if c["tuning"]:
-        info = t.info()
-        assert all(info[k] == v for k, v in c["tuning"].items()), info
-    return t
-
-
-def dev(torch, a, dtype=None):
-    x = torch.from_numpy(np.array(a, copy=True)).cuda()
-    return x if dtype is None else x.to(dtype)
 
 
 def bits16(x):

@@ -7,7 +7,7 @@ import pytest
 
 from tests import common, query_util as qu
 from tests.common import ob
-from tests.test_gpu_query import gpu_query, same_words
+from tests.query_util import gpu_query, same_words
 
 pytestmark = pytest.mark.gpu
 

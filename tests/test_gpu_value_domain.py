@@ -14,8 +14,7 @@ import numpy as np
 import pytest
 
 from tests import common
-from tests.common import assert_same_values, ob
-from tests.test_gpu_parity import gpu_frame
+from tests.common import assert_same_values, gpu_frame, ob
 
 pytestmark = pytest.mark.gpu
 

@@ -9,11 +9,10 @@ import pytest
 from tests import aov_util as au
 from tests import common
 from tests import weights_util as wu
+from tests.weights_util import accumulate, buffers, expected, host
 
 pytestmark = pytest.mark.gpu
 
-SENT_W = np.float32(2.0 ** -100)          # a known non-negative float: a reached slot holds max(weight, this)
-SENT_H = np.uint32(0xFFFFFFF0)            # sixteen short of the wrap: busy slots count through 2^32
 FP = pytest.mark.parametrize("fp_mode", [0, 1], ids=["strict", "fma"])
 
 
@@ -23,34 +22,6 @@ def torch_cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
     return torch
-
-
-def buffers(torch, tree, want=("max_weight", "hits")):
-    shape = wu.slots_shape(tree)
-    mw = torch.full(shape, float(SENT_W), dtype=torch.float32, device="cuda") if "max_weight" in want else None
-    hc = torch.full(shape, -16, dtype=torch.int32, device="cuda") if "hits" in want else None   # SENT_H
-    return mw, hc
-
-
-def expected(want_mw, want_hits):
-    """What sentinel-initialised buffers hold after accumulating a reference that started from zero."""
-    with np.errstate(over="ignore"):
-        return np.maximum(want_mw, SENT_W), (want_hits + SENT_H).astype(np.uint32)
-
-
-def host(t):
-    return None if t is None else t.cpu().numpy()
-
-
-def accumulate(torch, t, w, h, f, trs, fp_mode=0, want=("max_weight", "hits"), stream=None, mw=None, hc=None,
-               tree=None, fy=None, **opt_kw):
-    from volrend_amd import api
-    if mw is None and hc is None:
-        mw, hc = buffers(torch, tree, want)
-    cam = api.Camera(w, h, f, f if fy is None else fy)
-    t.accumulate_weights(cam, trs, api.RenderOptions(**opt_kw), max_weight=mw, hits=hc,
-                         want=(), fp_mode=fp_mode, stream=stream)
-    return mw, hc
 
 
 def check_reference(torch, ref, fp_mode, ndc=None, tuning=None, **opt_kw):

@@ -8,7 +8,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -134,15 +134,7 @@ def test_refusals_through_python(L):
 
 
 def test_refusals_through_cpp(L, tmp_path):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    exe = str(tmp_path / "grad_refusals")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "grad_refusals.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip", "-lz",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.check_output([exe], text=True, stderr=subprocess.DEVNULL)
-    got = dict(l.split(" ", 1) for l in out.splitlines() if not l.startswith("INFO:"))
+    got = build_util.run_key_values(build_util.cpp_program("grad_refusals", tmp_path), refusals=True)
     for case, word in [("null_grad_accum", "NULL"), ("null_grad_data", "NULL"), ("fp_mode", "fp_mode"),
                        ("step_size", "step_size"), ("render_depth", "render_depth"), ("rot_dirs", "rot_dirs")]:
         assert got[case].startswith("runtime_error: vr_render_backward:") and word in got[case], (case, got[case])

@@ -7,7 +7,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 
 from volrend_amd import synth
 
@@ -28,16 +28,8 @@ def fnv_np(a: np.ndarray) -> int:
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    out = str(tmp_path_factory.mktemp("bin") / "host_check")
-    # the loader references vr_tree_upload & co: link the real library (never called here)
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "host_check.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip", "-lz",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", out])
-    return out
+    # the loader references vr_tree_upload & co: the real library is linked (never called here)
+    return build_util.cpp_program("host_check", tmp_path_factory.mktemp("bin"))
 
 
 def run(exe, *args):

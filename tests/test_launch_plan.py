@@ -3,13 +3,11 @@ chunk cap, block order, ray-generation workgroup, record hint, frame group and q
 size gets.  None of them changes a pixel or a gradient, so no parity test sees one move.
 tests/cpp/launch_plan_check.cpp is built with plain g++ against that one source -- no HIP, no library -- and
 answers every query of this module in one run."""
-import os
 import subprocess
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "volrend_amd", "csrc")
+from tests import build_util
 
 KINDS = ("colour", "aov", "weights", "backward")
 COLOUR, GUIDED = ("colour", "aov"), ("weights", "backward")
@@ -19,11 +17,7 @@ FIELDS = ("chunk_max", "super_block", "raygen_waves", "records_nt", "frame_group
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("bin") / "launch_plan_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", CSRC,
-                           os.path.join(ROOT, "tests", "cpp", "launch_plan_check.cpp"),
-                           os.path.join(CSRC, "vr_launch_plan.cpp"), "-o", out])
-    return out
+    return build_util.csrc_program("launch_plan_check", "vr_launch_plan", tmp_path_factory.mktemp("bin"))
 
 
 def plans(exe, queries):

@@ -8,16 +8,13 @@
 import ctypes as C
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from tests import common, query_util as qu
+from tests import build_util, common, query_util as qu
 from tests.common import ob
 from volrend_amd import _abi, build
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -42,22 +39,12 @@ def test_query_symbols_and_prototypes(L):
 
 def test_query_out_layout_matches_the_c_compiler():
     st = _abi.VrQueryOut
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "volrend_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(VrQueryOut));',
-             'printf("world %d\\n", (int)VR_SPACE_WORLD); printf("tree %d\\n", (int)VR_SPACE_TREE);']
-    for fname, _ in st._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(VrQueryOut, {fname}));')
-    lines.append("return 0;}")
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "layout.c"), os.path.join(td, "layout")
-        open(src, "w").write("\n".join(lines))
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = dict(l.split() for l in subprocess.check_output([exe], text=True).splitlines())
+    got = build_util.c_struct_layout("VrQueryOut", st, [("world", "VR_SPACE_WORLD"), ("tree", "VR_SPACE_TREE")])
     assert [f for f, _ in st._fields_] == ["sigma", "depth", "local", "coeffs", "rgb"]
-    assert int(got["size"]) == C.sizeof(st)
+    assert got["size"] == C.sizeof(st)
     for fname, _ in st._fields_:
-        assert int(got[fname]) == getattr(st, fname).offset, fname
-    assert (int(got["world"]), int(got["tree"])) == (_abi.SPACE_WORLD, _abi.SPACE_TREE)
+        assert got[fname] == getattr(st, fname).offset, fname
+    assert (got["world"], got["tree"]) == (_abi.SPACE_WORLD, _abi.SPACE_TREE)
 
 
 def test_query_argument_checks_need_no_device(L):
@@ -102,11 +89,10 @@ def test_recomposed_colour_equals_or_render_on_one_sample_scenes(fmt, basis_dim)
 
 
 def test_point_sets_meet_their_conditions_on_the_oracle():
-    """The seeds the GPU tests use, checked where no GPU is needed (tests/test_gpu_query.POINT_TREES
+    """The seeds the GPU tests use, checked where no GPU is needed (tests/query_util.POINT_TREES; tests/test_gpu_query.py
     repeats the check on the oracle's answers before it looks at the kernel)."""
-    from tests.test_gpu_query import POINT_TREES, make_point_tree
-    for name in POINT_TREES:
-        tree, pts = make_point_tree(name, n=20000)
+    for name in qu.POINT_TREES:
+        tree, pts = qu.make_point_tree(name, n=20000)
         th = ob.TreeHandle(tree)
         ans = qu.oracle_answers(tree, th, pts, "tree")
         qu.check_point_set(tree, ans, name)

@@ -8,7 +8,7 @@ import subprocess
 
 import pytest
 
-from tests import common
+from tests import build_util, common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -186,16 +186,7 @@ def test_refusals_through_python(L):
 
 
 def test_refusals_through_cpp(L, tmp_path):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    exe = str(tmp_path / "rays_refusals")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "rays_refusals.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip", "-lz",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.check_output([exe], text=True, stderr=subprocess.DEVNULL)
-    got = dict(l.split(" ", 1) for l in out.splitlines() if not l.startswith("INFO:"))
+    got = build_util.run_key_values(build_util.cpp_program("rays_refusals", tmp_path), refusals=True)
     fn = {"render": "vr_render_rays", "weights": "vr_accumulate_weights_rays", "backward": "vr_render_backward_rays",
           "reserve": "vr_reserve_rays"}
     words = {"null_origins": "NULL", "null_dirs": "NULL", "no_output": "both outputs", "fp_mode": "fp_mode",

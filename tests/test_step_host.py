@@ -10,10 +10,9 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common, step_util as su
+from tests import build_util, common, step_util as su
 from volrend_amd import _abi, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 1
 TREE, D, BITS = 0x1000, 0x5000, 0x6000   # never dereferenced
 NEW_CALLS = ("vr_tree_step", "vr_render_backward_touched", "vr_render_backward_rays_touched")
@@ -36,17 +35,10 @@ def test_symbols_prototypes_and_struct_layout(L, tmp_path):
     assert len(_abi.PROTOTYPES["vr_render_backward_rays_touched"][1]) == \
         len(_abi.PROTOTYPES["vr_render_backward_rays"][1]) + 1
     assert (_abi.STEP_SGD, _abi.STEP_ADAM) == (0, 1)
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "volrend_hip.h"', 'int main(void){',
-             'printf("VrStep %zu\\n", sizeof(VrStep));', 'printf("sgd %d\\nadam %d\\n", VR_STEP_SGD, VR_STEP_ADAM);']
-    lines += [f'printf("{n} %zu\\n", offsetof(VrStep, {n}));' for n, _ in _abi.VrStep._fields_]
-    lines.append("return 0;}")
-    src, exe = str(tmp_path / "layout.c"), str(tmp_path / "layout")
-    open(src, "w").write("\n".join(lines))
-    subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-    got = dict(l.split() for l in subprocess.check_output([exe], text=True).splitlines())
-    assert int(got["VrStep"]) == C.sizeof(_abi.VrStep) and (got["sgd"], got["adam"]) == ("0", "1")
+    got = build_util.c_struct_layout("VrStep", _abi.VrStep, [("sgd", "VR_STEP_SGD"), ("adam", "VR_STEP_ADAM")])
+    assert got["size"] == C.sizeof(_abi.VrStep) and (got["sgd"], got["adam"]) == (0, 1)
     for n, _ in _abi.VrStep._fields_:
-        assert int(got[n]) == getattr(_abi.VrStep, n).offset, n
+        assert got[n] == getattr(_abi.VrStep, n).offset, n
 
 
 def make_step(**kw):
@@ -181,16 +173,7 @@ def test_refusals_through_python(L):
 
 
 def test_refusals_through_cpp(L, tmp_path):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    exe = str(tmp_path / "step_refusals")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "step_refusals.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip", "-lz",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.check_output([exe], text=True, stderr=subprocess.DEVNULL)
-    got = dict(l.split(" ", 1) for l in out.splitlines() if not l.startswith("INFO:"))
+    got = build_util.run_key_values(build_util.cpp_program("step_refusals", tmp_path), refusals=True)
     step_cases = [("null_tree", "NULL"), ("null_master", "NULL"), ("null_grad", "NULL"), ("null_touched", "NULL"),
                   ("kind", "kind"), ("lr_nan", "finite"), ("lr_sigma_inf", "finite"), ("eps_nan", "finite"),
                   ("adam_null_m", "moments"), ("adam_null_v", "moments"), ("adam_step0", "step"),

@@ -2,25 +2,18 @@
 numbering, the shape of the lookup structure.  tests/cpp/walk_check.cpp is built with plain g++ against
 that one source -- no HIP, no library -- and its output is checked against walks written here in
 numpy / Python."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import common
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "volrend_amd", "csrc")
+from tests import build_util, common
+from tests.common import rows_of, scrambled, with_unreachable
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("bin") / "walk_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", CSRC,
-                           os.path.join(ROOT, "tests", "cpp", "walk_check.cpp"),
-                           os.path.join(CSRC, "vr_tree_walk.cpp"), "-o", out])
-    return out
+    return build_util.csrc_program("walk_check", "vr_tree_walk", tmp_path_factory.mktemp("bin"))
 
 
 def run_walk(exe, tmp_path, child, G0=0, BL=0, cap=None):
@@ -43,29 +36,6 @@ def plan(exe, N, max_depth, capacity, top_levels=0, brick_levels=3, n_roots=1000
 
 
 # ---- trees ---------------------------------------------------------------------------------------
-
-def rows_of(tree):
-    return tree.child.reshape(tree.capacity, -1).astype(np.int64)
-
-
-def scrambled(child, seed=7):
-    """The construction of tests/test_gpu_chain.py::test_tree_with_backward_links on the child array:
-    the nodes in a random order, root first.  -> (new child array, new index of every old node)."""
-    cap = child.shape[0]
-    new_of = np.concatenate([[0], 1 + np.random.default_rng(seed).permutation(cap - 1)])
-    tgt = np.where(child != 0, np.arange(cap)[:, None] + child, -1)
-    out = np.zeros_like(child)
-    out[new_of] = np.where(tgt >= 0, new_of[np.maximum(tgt, 0)] - new_of[:, None], 0)
-    return out, new_of
-
-
-def with_unreachable(child):
-    """Five nodes behind the tree that nothing links to: one links on to the next, one back into the tree."""
-    extra = np.zeros((5, child.shape[1]), np.int64)
-    extra[1, 2] = 1
-    extra[3, 0] = -(child.shape[0] + 2)       # -> node 1 of the tree
-    return np.concatenate([child, extra])
-
 
 def chain(levels, backward=False):
     """N = 2 nodes in a row: node levels 0 .. `levels`.  backward: root, then the chain from its far end."""

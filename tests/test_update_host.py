@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from volrend_amd import _abi, build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,16 +131,7 @@ def test_the_gpu_tests_data_sets_flip_sigma_in_every_kind_of_leaf():
 
 
 def test_refusals_through_cpp(L, tmp_path):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    exe = str(tmp_path / "update_refusals")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"),
-                           os.path.join(ROOT, "tests", "cpp", "update_refusals.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip", "-lz",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.check_output([exe], text=True, stderr=subprocess.DEVNULL)
-    got = dict(l.split(" ", 1) for l in out.splitlines() if not l.startswith("INFO:"))
+    got = build_util.run_key_values(build_util.cpp_program("update_refusals", tmp_path), refusals=True)
     for call in ("update", "read"):
         for case, word in (("null_tree", "NULL"), ("null_data", "NULL"), ("dtype", "dtype")):
             line = got[f"{call}_{case}"]

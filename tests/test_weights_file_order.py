@@ -2,26 +2,18 @@
 (inverse_permutation, volrend_amd/csrc/vr_tree_walk.cpp): the inverse of what node_permutation returns,
 unreachable nodes included.  tests/cpp/walk_inverse_check.cpp is built with plain g++ against that one
 source -- no HIP, no library."""
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from tests import common
-from tests.test_tree_walk import rows_of, scrambled, with_unreachable
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "volrend_amd", "csrc")
+from tests import build_util, common
+from tests.common import rows_of, scrambled, with_unreachable
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("bin") / "walk_inverse_check")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-Wall", "-I", CSRC,
-                           os.path.join(ROOT, "tests", "cpp", "walk_inverse_check.cpp"),
-                           os.path.join(CSRC, "vr_tree_walk.cpp"), "-o", out])
-    return out
+    return build_util.csrc_program("walk_inverse_check", "vr_tree_walk", tmp_path_factory.mktemp("bin"))
 
 
 @pytest.mark.parametrize("G0,BL", [(0, 0), (2, 2), (1, 3)])

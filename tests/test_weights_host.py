@@ -5,15 +5,13 @@ never written)."""
 import ctypes as C
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from tests import common
+from tests import build_util, common
 from volrend_amd import _abi, build
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID = 1
 TREE, BUF = 0x1000, 0x3000   # never dereferenced
 
@@ -37,22 +35,12 @@ def test_symbol_prototype_and_abi_version(L):
 
 def test_vrleafweights_layout_matches_the_c_compiler():
     st = _abi.VrLeafWeights
-    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "volrend_hip.h"', 'int main(void){',
-             'printf("size %zu\\n", sizeof(VrLeafWeights));', 'printf("abi %d\\n", (int)VR_ABI_VERSION);',
-             'printf("batch %d\\n", (int)VR_MAX_BATCH);']
-    for fname, _ in st._fields_:
-        lines.append(f'printf("{fname} %zu\\n", offsetof(VrLeafWeights, {fname}));')
-    lines.append("return 0;}")
-    with tempfile.TemporaryDirectory() as td:
-        src, exe = os.path.join(td, "layout.c"), os.path.join(td, "layout")
-        open(src, "w").write("\n".join(lines))
-        subprocess.check_call(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), src, "-o", exe])
-        got = dict(l.split() for l in subprocess.check_output([exe], text=True).splitlines())
+    got = build_util.c_struct_layout("VrLeafWeights", st, [("abi", "VR_ABI_VERSION"), ("batch", "VR_MAX_BATCH")])
     assert [f for f, _ in st._fields_] == ["max_weight", "hits"]
-    assert int(got["size"]) == C.sizeof(st) == 16
+    assert got["size"] == C.sizeof(st) == 16
     for fname, _ in st._fields_:
-        assert int(got[fname]) == getattr(st, fname).offset, fname
-    assert (int(got["abi"]), int(got["batch"])) == (3, _abi.MAX_BATCH)
+        assert got[fname] == getattr(st, fname).offset, fname
+    assert (got["abi"], got["batch"]) == (3, _abi.MAX_BATCH)
 
 
 def _args(n=1, w=64, h=48):
@@ -131,14 +119,6 @@ def test_refusals_through_python(L):
 
 
 def test_refusals_through_cpp(L, tmp_path):
-    subprocess.check_call(["make", "-C", ROOT, "host"], stdout=subprocess.DEVNULL)
-    exe = str(tmp_path / "weights_refusals")
-    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tests", "cpp", "weights_refusals.cpp"),
-                           os.path.join(ROOT, "volrend_amd", "libvolrend_host.a"),
-                           "-L", os.path.join(ROOT, "volrend_amd"), "-lvolrend_hip", "-lz",
-                           "-Wl,-rpath," + os.path.join(ROOT, "volrend_amd"),
-                           "-Wl,-rpath,/opt/rocm/lib", "-o", exe])
-    out = subprocess.check_output([exe], text=True, stderr=subprocess.DEVNULL)
-    got = dict(l.split(" ", 1) for l in out.splitlines() if not l.startswith("INFO:"))
+    got = build_util.run_key_values(build_util.cpp_program("weights_refusals", tmp_path), refusals=True)
     for case, word in [("both_null", "both outputs"), ("fp_mode", "fp_mode"), ("step_size", "step_size")]:
         assert got[case].startswith("runtime_error: vr_accumulate_weights:") and word in got[case], (case, got[case])

@@ -1,10 +1,11 @@
 """The yardstick of the vr_accumulate_weights tests is tied to the oracle (no GPU needed).
 
-tests/cpp/weights_restatement.c restates trace_ray's loop without the colour and applies the per-leaf rule
-(hits += 1; max over the weights > 0).  The oracle has no per-leaf output, so the tie goes through what it
-does have, bit for bit in both FP models:
+tests/cpp/weights_restatement.c applies the per-leaf rule (hits += 1; max over the weights > 0) to the hit
+samples of the one restatement of trace_ray's loop (tests/cpp/march_restatement.h).  The oracle has no per-leaf
+output, so the tie goes through what it does have, bit for bit in both FP models:
   per pixel  D, T and "ended by stop_thresh" equal tests/aov_util.restate (itself tied to or_render on every
-             pixel by tests/test_aov_restatement.py): the same rays take the same samples with the same weights;
+             pixel by tests/test_aov_restatement.py; the same C loop, here with the callback: this half pins the
+             callback path and the Python plumbing);
   per frame  hits.sum() equals the oracle's counters.hit_samples: every hit sample was counted in some slot.
 This validates the yardstick, not the feature."""
 import numpy as np

@@ -138,3 +138,27 @@ def flips(tree, top_levels, brick_levels, d_from, d_to):
     s1 = (np.asarray(d_to)[..., -1].astype(np.float32) > SIGMA_THRESH).reshape(kinds.shape)
     return {k: (int((~s0 & s1 & (kinds == k)).sum()), int((s0 & ~s1 & (kinds == k)).sum()))
             for k in (TOP, BRICK, WORD) if (kinds == k).sum() >= 4}
+
+
+# ---- shared by the GPU tests (torch is handed in: the module imports without it) -----------------------------------
+def upload(name, data=None):
+    """The scene with `data` (None: its own), under the scene's upload-time tuning."""
+    from volrend_amd import api
+    c = case(name)
+    tree = c["tree"] if data is None else with_data(c["tree"], data)
+    if c["tuning"]:
+        api.set_tuning(**c["tuning"])
+    try:
+        t = api.N3Tree.from_synth(tree, ndc=c["ndc"])
+    finally:
+        if c["tuning"]:
+            api.set_tuning(top_levels=0, brick_levels=3, brick_blocked=-1)
+    if c["tuning"]:
+        info = t.info()
+        assert all(info[k] == v for k, v in c["tuning"].items()), info
+    return t
+
+
+def dev(torch, a, dtype=None):
+    x = torch.from_numpy(np.array(a, copy=True)).cuda()
+    return x if dtype is None else x.to(dtype)

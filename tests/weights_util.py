@@ -1,42 +1,26 @@
-"""Helpers of the vr_accumulate_weights tests: the C restatement of trace_ray's loop with the per-leaf
-rule (tests/cpp/weights_restatement.c), compiled on first use with the oracle's flags, and the cases the
-CPU and GPU tests share.  Scenes and option sets are those of tests/aov_util.py."""
+"""Helpers of the vr_accumulate_weights tests: the per-leaf rule over the C restatement of the march
+(tests/cpp/weights_restatement.c over march_restatement.h), and the cases the CPU and GPU tests share.
+Scenes and option sets are those of tests/aov_util.py."""
 from __future__ import annotations
 
-import atexit
 import ctypes as C
 import functools
-import os
-import shutil
-import subprocess
-import tempfile
 
 import numpy as np
 
 from tests import aov_util as au
-from tests import common
+from tests import build_util, common
 from tests.common import ob
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "tests", "cpp", "weights_restatement.c")
-_lib = None
 
-
+@functools.lru_cache(maxsize=None)
 def lib():
-    global _lib
-    if _lib is None:
-        td = tempfile.mkdtemp(prefix="vr_weights_restate_")
-        atexit.register(shutil.rmtree, td, ignore_errors=True)
-        so = os.path.join(td, "libweights_restatement.so")
-        subprocess.check_call(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-mfma", "-fPIC", "-shared",
-                               "-Wno-unused-function", "-I", os.path.join(ROOT, "oracle"), SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
-        L.weights_restate.restype = C.c_int
-        L.weights_restate.argtypes = [C.POINTER(ob.OrTree), C.POINTER(ob.OrCamera), C.POINTER(ob.OrOptions), C.c_int,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.POINTER(C.c_uint64)]
-        _lib = L
-    return _lib
+    L = build_util.c_library("weights_restatement.c")
+    L.weights_restate.restype = C.c_int
+    L.weights_restate.argtypes = [C.POINTER(ob.OrTree), C.POINTER(ob.OrCamera), C.POINTER(ob.OrOptions), C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.POINTER(C.c_uint64)]
+    return L
 
 
 def slots_shape(tree):
@@ -125,3 +109,36 @@ def reference(scene_name, optset, fp_mode, n_poses, size=None):
     mw.setflags(write=False)
     hc.setflags(write=False)
     return tree, trs, size, size, f, mw, hc, bad
+
+
+# ---- shared by the GPU tests (torch is handed in: the module imports without it) -----------------------------------
+SENT_W = np.float32(2.0 ** -100)          # a known non-negative float: a reached slot holds max(weight, this)
+SENT_H = np.uint32(0xFFFFFFF0)            # sixteen short of the wrap: busy slots count through 2^32
+
+
+def buffers(torch, tree, want=("max_weight", "hits")):
+    shape = slots_shape(tree)
+    mw = torch.full(shape, float(SENT_W), dtype=torch.float32, device="cuda") if "max_weight" in want else None
+    hc = torch.full(shape, -16, dtype=torch.int32, device="cuda") if "hits" in want else None   # SENT_H
+    return mw, hc
+
+
+def expected(want_mw, want_hits):
+    """What sentinel-initialised buffers hold after accumulating a reference that started from zero."""
+    with np.errstate(over="ignore"):
+        return np.maximum(want_mw, SENT_W), (want_hits + SENT_H).astype(np.uint32)
+
+
+def host(t):
+    return None if t is None else t.cpu().numpy()
+
+
+def accumulate(torch, t, w, h, f, trs, fp_mode=0, want=("max_weight", "hits"), stream=None, mw=None, hc=None,
+               tree=None, fy=None, **opt_kw):
+    from volrend_amd import api
+    if mw is None and hc is None:
+        mw, hc = buffers(torch, tree, want)
+    cam = api.Camera(w, h, f, f if fy is None else fy)
+    t.accumulate_weights(cam, trs, api.RenderOptions(**opt_kw), max_weight=mw, hits=hc,
+                         want=(), fp_mode=fp_mode, stream=stream)
+    return mw, hc
