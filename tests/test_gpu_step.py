@@ -5,7 +5,9 @@ Everything about the step is bit-exact: the expected side is the numpy binary32 
 the dense vr_tree_update_data or a FRESH upload of the expected data.  The marks are compared with hits > 0 of
 vr_accumulate_weights_rays, an independently tested call; the marked gradient passes the check and the bound of
 tests/test_gpu_grad.py (no new tolerance).  Scenes: tests/update_util.py; rays: the scene's two poses through
-tests/rays_util.rays_of_camera."""
+tests/rays_util.rays_of_camera.  The step's value domain (section 8) runs the catalogue of tests/step_util.py, whose
+strength tests/test_step_host.py shows on the CPU; every record shape and the bitmap patterns:
+tests/test_gpu_step_shapes.py."""
 import functools
 
 import numpy as np
@@ -263,7 +265,7 @@ def made_up_step(name):
     return master0, grad.astype(np.float32), mask, expected, want
 
 
-@pytest.mark.parametrize("name", ["mixed", "blocked", "sh16", "chain"])
+@pytest.mark.parametrize("name", ["mixed", "blocked", "sh16", "chain", "sh9", "sh25", "sg21", "sg22"])
 def test_the_tree_is_a_fresh_uploads(torch_cuda, name):
     torch = torch_cuda
     tree = uu.case(name)["tree"]
@@ -493,3 +495,117 @@ def test_sparse_tree_optimizer(torch_cuda):
         assert not np.array_equal(renders[0], renders[1]), "the second render equals the first"
     finally:
         t.free_device()
+
+
+def test_sparse_tree_optimizer_adam(torch_cuda):
+    """Three iterations of render -> backward -> step on SH9 (two slots per wave instruction, eight idle lanes): the
+    optimiser's arrays are the restatement of the gradients and marks it read, the tree is binary16(master) in every
+    slot ever touched."""
+    torch = torch_cuda
+    from volrend_amd import optim
+    name = "sh9"
+    tree = uu.case(name)["tree"]
+    slots = n_slots(tree)
+    o, d, _ = rays_of(name)
+    kw = dict(lr=0.02, lr_sigma=0.3, betas=(0.9, 0.999), eps=1e-8)
+    t = upload(name)
+    try:
+        opt = optim.SparseTreeOptimizer(t, "adam", **kw)
+        od, dd_ = dev(torch, o), dev(torch, d)
+        old16 = t.read_data().cpu().numpy()
+        want = dict(master=opt.master.cpu().numpy(), m=opt.m.cpu().numpy(), v=opt.v.cpu().numpy())
+        assert not want["m"].any() and not want["v"].any()
+        ever = np.zeros(slots, bool)
+        for it in (1, 2, 3):
+            accum = opt.render(od, dd_)
+            opt.backward(od, dd_, 2.0 * (accum - 0.5))
+            torch.cuda.synchronize()
+            g, mask = opt.grad.cpu().numpy(), su.unpack_bits(host_bits(opt.touched), slots)
+            assert mask.sum() > 50 and g.any()
+            want = su.restate("adam", want["master"], g, mask, m=want["m"], v=want["v"], step=it, **kw)
+            ever |= mask
+            opt.step()
+            read = t.read_data()
+            torch.cuda.synchronize()
+            for key, x in (("master", opt.master), ("m", opt.m), ("v", opt.v)):
+                assert np.array_equal(x.cpu().numpy().view(np.uint32), want[key].view(np.uint32)), (it, key)
+            assert not bool(opt.grad.any()) and not bool(opt.touched.any())
+            expected = uu.stored(tree, su.mixture(old16, want["master"], ever))
+            assert np.array_equal(read.cpu().numpy().view(np.uint16), expected.view(np.uint16)), it
+        assert t.status() == 0 and opt.steps == 3
+        assert not np.array_equal(expected.view(np.uint16), old16.view(np.uint16))
+    finally:
+        t.free_device()
+
+
+# ---- 8. the value domain -----------------------------------------------------------------------------------------
+def frame(torch, t, name, pose=0):
+    """One frame of the scene through the camera path (ray generation with the block cull at its default)."""
+    from volrend_amd import api
+    c = uu.case(name)
+    cam = api.Camera(c["w"], c["h"], c["f"], c["f"])
+    cam.transform = c["trs"][pose]
+    img = torch.zeros((c["h"], c["w"], 4), dtype=torch.uint8, device="cuda")
+    acc = torch.zeros((c["h"], c["w"], 4), dtype=torch.float32, device="cuda")
+    api.launch_renderer(t, cam, api.RenderOptions(), img, None, torch.cuda.current_stream(), True, accum=acc)
+    torch.cuda.synchronize()
+    return img.cpu().numpy(), acc.cpu().numpy()
+
+
+@pytest.mark.parametrize("call_name", list(su.CALLS))
+@pytest.mark.parametrize("name", su.CATALOGUE_SCENES)
+def test_value_domain(torch_cuda, name, call_name):
+    """One call over the catalogue of step_util.catalogue (what it holds and what it shows: tests/test_step_host.py):
+    subnormal, overflowing and non-finite gradients and moments, eps = 0, extreme betas, step counts and rates,
+    master on binary16 ties, subnormals and overflow.  Everything that is not NaN is bit-exact against the
+    restatement; NaN stands in exactly the same elements, in binary32 and in the binary16 the tree holds, and leaks
+    into no other element.  Then the tree is a fresh upload's of that data, byte for byte in every output -- the
+    fresh upload takes the tree's own NaN bits, since the header leaves a NaN's sign and payload open -- and for SH16
+    its frame is the oracle's: sigma has become NaN, +-inf, negative, -0 and subnormal in marked leaves and has
+    crossed sigma_thresh both ways, so lookup refresh and block-cull occupancy have to follow."""
+    torch = torch_cuda
+    from tests import common
+    c, call = su.catalogue(name), su.CALLS[call_name]
+    tree = uu.case(name)["tree"]
+    mask = c["mask"]
+    want, expected16 = su.catalogue_expected(name, call_name)
+    found = su.sigma_outcomes(name, expected16)
+    need = su.SIGMA_OUTCOMES if su.passes_through(call) else ("rises", "falls", "nan")
+    assert all(found[k] > 0 for k in need), found
+    corners, sizes, _, slots = qu.leaf_boxes(tree)
+    cat_leaves = np.isin(slots, np.concatenate(list(c["sigma"].values())))
+    pts = (corners[cat_leaves] + 0.5 * sizes[cat_leaves, None]).astype(np.float32)
+    assert len(pts) == len(su.entries()) * su.SIGMA_COPIES
+    t = upload(name, c["old16"])
+    fresh = None
+    try:
+        before = frame(torch, t, name)[0]
+        got = su.device_call(torch, t, call["kind"], c, mask, su.pack_bits(mask), **su.call_kw(call))
+        stored16 = uu.stored(tree, expected16)
+        su.assert_call(got, want, mask, stored16, f"{name} {call_name}", nan_ok=True)
+        assert np.isnan(want["master"]).any() and np.isinf(want["master"]).any()
+        obs = observe(torch, t, name, pts)
+        obs["frame_rgba"], obs["frame_accum"] = frame(torch, t, name)
+        assert t.status() == 0
+        nan16 = np.isnan(stored16)
+        fresh = upload(name, np.where(nan16, got["read"], stored16))
+        ref = observe(torch, fresh, name, pts)
+        ref["frame_rgba"], ref["frame_accum"] = frame(torch, fresh, name)
+    finally:
+        t.free_device()
+        if fresh is not None:
+            fresh.free_device()
+    for k in ref:
+        assert obs[k].dtype == ref[k].dtype and obs[k].shape == ref[k].shape, k
+        bad = obs[k].view(np.uint8) != ref[k].view(np.uint8)
+        assert not bad.any(), (f"{name} {call_name}: {k} differs from the fresh upload in {int(bad.sum())} of "
+                               f"{bad.size} bytes")
+    assert (obs["hits"] != 0).sum() > 50
+    assert not np.array_equal(obs["frame_rgba"], before), "the step changed nothing in the frame"
+    if name == "sh16":
+        sc = uu.case(name)
+        rgba_o, acc_o, cnt = common.oracle_frame(uu.with_data(tree, expected16), sc["trs"][0], sc["w"], sc["h"], sc["f"],
+                                                 0)
+        assert cnt["hit_samples"] > 0
+        common.assert_same_values(obs["frame_rgba"], obs["frame_accum"], rgba_o, acc_o,
+                                  f"{name} {call_name} against the oracle")

@@ -178,18 +178,6 @@ def test_an_array_off_the_16_byte_grid(torch_cuda, dtype):
 
 
 # ---- 3. rounding ------------------------------------------------------------------------------------------
-def edge_values():
-    h = np.float32
-    ties = [1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 1 + 2.0 ** -11 + 2.0 ** -20, 1 + 2.0 ** -11 - 2.0 ** -20, 0.1, 1 / 3,
-            2049.0, 2051.0, 2050.5, 1023.75]
-    sub = [2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * (1 + 2.0 ** -20), 3 * 2.0 ** -25, 2.0 ** -26, 2.0 ** -14 * (1 - 2.0 ** -12),
-           2.0 ** -14 - 2.0 ** -25, 2.0 ** -15, 1e-7, 5.5e-8, 1e-40, 2.0 ** -149]
-    big = [65504.0, 65519.0, 65520.0, 65536.0, 70000.0, 1e38, 3.4e38]
-    vals = ties + sub + big
-    vals = vals + [-v for v in vals] + [0.0, -0.0, np.inf, -np.inf, np.nan]
-    return np.array(vals, h)
-
-
 def test_float32_rounds_like_numpy(torch_cuda):
     """update_data(float32) stores numpy.astype(float16): ties to even, subnormal halves, overflow to +-inf, the sign
     of zero; NaN stays NaN.  Renders nothing."""
@@ -201,7 +189,7 @@ def test_float32_rounds_like_numpy(torch_cuda):
     # random binary32 values across the binary16 range (and below it), all 23 fraction bits in use
     k = a.size // 2
     a[rng.choice(a.size, k, replace=False)] = (rng.standard_normal(k) * 2.0 ** rng.integers(-30, 17, k)).astype(np.float32)
-    edges = edge_values()
+    edges = uu.edge_values()
     at = rng.choice(a.size, 64 * edges.size, replace=False)
     a[at] = np.tile(edges, 64)
     a = a.reshape(tree.data.shape)
@@ -228,7 +216,7 @@ def test_float32_rounds_like_numpy(torch_cuda):
 
 
 # ---- 4. no residue ----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["mixed", "blocked", "n4"])
+@pytest.mark.parametrize("name", ["mixed", "blocked", "n4", "n4_sh9", "sg22"])
 def test_there_and_back_leaves_no_residue(torch_cuda, name):
     torch = torch_cuda
     tree = uu.case(name)["tree"]

@@ -269,3 +269,284 @@ def test_mixture_rounds_only_marked_slots():
     got = su.mixture(old, master, mask)
     assert np.array_equal(got[~mask], old[~mask])
     assert np.array_equal(got[mask].view(np.uint16), master[mask].astype(np.float16).view(np.uint16))
+
+
+# ---- the value-domain catalogue (step_util.catalogue; the GPU side: tests/test_gpu_step.py) -----------------------
+f32, f64 = np.float32, np.float64
+TINY = f32(2.0 ** -126)
+BETAS = [(0.0, 0.0), (0.9, 0.999), (0.5, su.BELOW_ONE), (su.BELOW_ONE, 0.0)]
+STEPS = [1, 2, 1000, 2 ** 31 - 1]
+
+
+def flushed(x):
+    """binary32 subnormals as zero, the sign kept."""
+    x = np.asarray(x, f32)
+    return np.where(np.abs(x) < TINY, np.copysign(f32(0), x), x).astype(f32)
+
+
+def fused(a, b, c):
+    """a * b + c with the product exact (binary64) and one rounding to binary32."""
+    return (np.asarray(a, f64) * np.asarray(b, f64) + np.asarray(c, f64)).astype(f32)
+
+
+def wrong_restate(variant, kind, master, grad, mask, *, lr, lr_sigma, m=None, v=None, betas=(0.9, 0.999), eps=1e-8,
+                  step=1):
+    """su.restate with one deliberate mistake -> (master, m, v).  variant: "ftz" | "fma" | "eps_in_sqrt" |
+    "bias_in_sqrt" | "lr_for_sigma" (anything else: no mistake)."""
+    dd = master.shape[-1]
+    mask = np.asarray(mask, bool).reshape(-1)
+    z = flushed if variant == "ftz" else (lambda x: np.asarray(x, f32))
+    op = lambda f, *xs: z(f(*[z(x) for x in xs]))     # noqa: E731  (one operator: inputs and output through z)
+    w0, g = master.reshape(-1, dd)[mask], grad.reshape(-1, dd)[mask]
+    m1 = v1 = None
+    with np.errstate(all="ignore"):
+        if kind == "sgd":
+            rates, x = (f32(lr), f32(lr_sigma)), g
+        else:
+            omb1, omb2, sbc2, a, a_sigma = su.host_scalars(lr, lr_sigma, betas, step)
+            beta1, beta2, e = f32(betas[0]), f32(betas[1]), f32(eps)
+            rates = (a, a_sigma)
+            m0, v0 = m.reshape(-1, dd)[mask], v.reshape(-1, dd)[mask]
+            if variant == "fma":
+                m1, v1 = fused(omb1, g, beta1 * m0), fused(omb2 * g, g, beta2 * v0)
+            else:
+                m1 = op(np.add, op(np.multiply, beta1, m0), op(np.multiply, omb1, g))
+                v1 = op(np.add, op(np.multiply, beta2, v0), op(np.multiply, op(np.multiply, omb2, g), g))
+            if variant == "eps_in_sqrt":
+                den = np.sqrt(v1 + e) / sbc2
+            elif variant == "bias_in_sqrt":
+                den = np.sqrt(v1 / (sbc2 * sbc2)) + e
+            else:
+                den = op(np.add, op(np.divide, op(np.sqrt, v1), sbc2), e)
+            x = op(np.divide, m1, den)
+        rate = np.full(dd, rates[0], f32)
+        rate[-1] = rates[0] if variant == "lr_for_sigma" else rates[1]
+        w = fused(-rate, x, w0) if variant == "fma" else op(np.subtract, w0, op(np.multiply, rate, x))
+    assert w.dtype == f32
+    out = [np.array(a, f32).reshape(-1, dd) if a is not None else None for a in (master, m, v)]
+    for a, new in zip(out, (w, m1, v1)):
+        if new is not None:
+            a[mask] = new
+    return [None if a is None else a.reshape(master.shape) for a in out]
+
+
+def half_truncated(x):
+    """binary32 -> binary16 towards zero."""
+    with np.errstate(over="ignore"):
+        h = np.asarray(x, f32).astype(np.float16)
+    away = np.abs(h.astype(f32)) > np.abs(x)
+    return np.where(away, np.nextafter(h, np.float16(0)), h).astype(np.float16)
+
+
+def half_flushed(x):
+    """binary32 -> binary16 to nearest even, subnormal halves as zero."""
+    with np.errstate(over="ignore"):
+        h = np.asarray(x, f32).astype(np.float16)
+    sub = (h.view(np.uint16) & 0x7C00) == 0
+    return np.where(sub, np.copysign(np.float16(0), h), h).astype(np.float16)
+
+
+def changed(a, b):
+    """Elements in which b is another value than a non-NaN a."""
+    bits = {2: np.uint16, 4: np.uint32}[a.dtype.itemsize]
+    return int(((a.view(bits) != b.view(bits)) & ~np.isnan(a)).sum())
+
+
+def test_wrong_restate_without_a_mistake_is_the_restatement():
+    c = su.catalogue("sh25")
+    for call_name, call in su.CALLS.items():
+        want, _ = su.catalogue_expected("sh25", call_name)
+        got = wrong_restate(None, call["kind"], c["master"], c["grad"], c["mask"], m=c["m"], v=c["v"], **su.call_kw(call))
+        for key, a in zip(("master", "m", "v"), got):
+            if want[key] is not None:
+                assert su.same_or_nan(a, want[key]).all(), (call_name, key)
+
+
+@pytest.mark.parametrize("variant", ["ftz", "fma", "eps_in_sqrt", "bias_in_sqrt", "lr_for_sigma", "half_truncated",
+                                     "half_flushed"])
+@pytest.mark.parametrize("name", su.CATALOGUE_SCENES)
+def test_the_catalogue_sees_a_wrong_step(name, variant):
+    """Each mistake a kernel could make changes a non-NaN bit of master, m, v or the binary16 data on this scene."""
+    c = su.catalogue(name)
+    seen = {}
+    for call_name, call in su.CALLS.items():
+        want, expected16 = su.catalogue_expected(name, call_name)
+        if variant.startswith("half_"):
+            wrong16 = {"half_truncated": half_truncated, "half_flushed": half_flushed}[variant](want["master"])
+            marked = c["mask"].reshape(expected16.shape[:-1])
+            seen[call_name] = changed(expected16[marked], wrong16[marked])
+            continue
+        got = wrong_restate(variant, call["kind"], c["master"], c["grad"], c["mask"], m=c["m"], v=c["v"],
+                            **su.call_kw(call))
+        seen[call_name] = sum(changed(want[key], a) for key, a in zip(("master", "m", "v"), got) if want[key] is not None)
+    print(name, variant, "elements changed per call:", seen)
+    assert sum(seen.values()) > 0, "the catalogue does not see this mistake"
+    if variant in ("ftz", "fma", "lr_for_sigma", "half_truncated", "half_flushed"):   # (the others are Adam's alone)
+        assert seen["sgd"] > 0
+    if variant in ("ftz", "fma", "eps_in_sqrt", "bias_in_sqrt"):
+        assert seen["adam"] > 0
+
+
+def formula64(call, w0, g, m, v, sigma):
+    """The header's Adam formulas in binary64 with the exact binary32 scalars -> (w, the error unit, in scope): in
+    scope is an element none of whose binary32 intermediates overflows, is non-finite or underflows (the unit is
+    purely relative: it has no term for a result below 2^-126)."""
+    omb1, omb2, sbc2, a, a_sigma = (float(x) for x in su.host_scalars(call["lr"], call["lr_sigma"], call["betas"],
+                                                                      call["step"]))
+    b1, b2, e = float(f32(call["betas"][0])), float(f32(call["betas"][1])), float(f32(call["eps"]))
+    w0, g, m, v = (np.asarray(x, f64) for x in (w0, g, m, v))
+    rate = np.where(sigma, a_sigma, a)
+    with np.errstate(all="ignore"):
+        steps = [b1 * m, omb1 * g, b1 * m + omb1 * g, omb2 * g, omb2 * g * g, b2 * v, b2 * v + omb2 * g * g]
+        m1, v1 = steps[2], steps[6]
+        steps += [np.sqrt(v1), np.sqrt(v1) / sbc2, np.sqrt(v1) / sbc2 + e]
+        den = steps[-1]
+        steps += [m1 / den, rate * (m1 / den), w0 - rate * (m1 / den), w0, g, m, v]
+        unit = 2.0 ** -24 * (np.abs(w0) + np.abs(rate) * (np.abs(b1 * m) + np.abs(omb1 * g)) / den)
+        ok = np.ones(w0.shape, bool)
+        for s in steps:
+            ok &= np.isfinite(s) & (np.abs(s) <= float(np.finfo(f32).max)) & ((s == 0) | (np.abs(s) >= float(TINY)))
+    return steps[12], unit, ok
+
+
+def random_draws(seed, n=20000):
+    rng = np.random.default_rng(seed)
+    sign = lambda: rng.choice([-1.0, 1.0], n)     # noqa: E731
+    w0 = (rng.standard_normal(n) * 10.0 ** rng.uniform(-3, 2, n)).astype(f32)
+    g = (sign() * 10.0 ** rng.uniform(-6, 3, n)).astype(f32)
+    m = (sign() * 10.0 ** rng.uniform(-6, 1, n)).astype(f32)
+    v = (10.0 ** rng.uniform(-12, 2, n)).astype(f32)
+    return w0, g, m, v
+
+
+def test_restatement_against_float64():
+    """su.restate("adam") against the formulas in binary64, in units of 2^-24 times the MAGNITUDES that enter an
+    element (not the cancelled m'): the finite part of the catalogue, and random draws under every pair of betas, eps
+    and step count.  Ties the restatement to the formula; no GPU tolerance comes from it."""
+    worst, worst_case = 0.0, None
+    cases = []
+    for name in su.CATALOGUE_SCENES:
+        c = su.catalogue(name)
+        dd = c["master"].shape[-1]
+        mask = c["mask"]
+        pick = lambda a: a.reshape(-1, dd)[mask]      # noqa: E731
+        sigma = np.zeros((int(mask.sum()), dd), bool)
+        sigma[:, -1] = True
+        for call_name, call in su.CALLS.items():
+            if call["kind"] == "adam":
+                want, _ = su.catalogue_expected(name, call_name)
+                cases.append((f"{name} {call_name}", call, pick(c["master"]), pick(c["grad"]), pick(c["m"]), pick(c["v"]),
+                              sigma, pick(want["master"])))
+    n = 0
+    for betas in BETAS:
+        for eps in (0.0, 1e-8, 1.0):
+            for step in STEPS:
+                call = dict(kind="adam", lr=1e-3, lr_sigma=-0.5, betas=betas, eps=eps, step=step)
+                w0, g, m, v = (x.reshape(-1, 2) for x in random_draws(900 + n))
+                n += 1
+                sigma = np.zeros(w0.shape, bool)
+                sigma[:, -1] = True
+                got = su.restate("adam", w0, g, np.ones(w0.shape[0], bool), m=m, v=v, **su.call_kw(call))["master"]
+                cases.append((f"random draws, betas {betas}, eps {eps}, step {step}", call, w0, g, m, v, sigma, got))
+    judged = 0
+    for what, call, w0, g, m, v, sigma, got in cases:
+        w64, unit, ok = formula64(call, w0, g, m, v, sigma)
+        assert ok.sum() > 0.25 * ok.size, (what, int(ok.sum()), ok.size)   # (lr = 3e38 overflows in most elements)
+        judged += int(ok.sum())
+        err = np.abs(got.astype(f64)[ok] - w64[ok])
+        zero = unit[ok] == 0
+        assert (err[zero] == 0).all(), what
+        ratio = float((err[~zero] / unit[ok][~zero]).max()) if (~zero).any() else 0.0
+        if ratio > worst:
+            worst, worst_case = ratio, what
+    print(f"worst |binary32 - binary64| / unit: {worst:.3f} ({worst_case}), {judged} elements judged")
+    assert worst <= su.K_STEP32, (worst, worst_case)
+    assert worst > 0.5, "the comparison judged nothing"
+
+
+def test_host_scalars_of_the_catalogue():
+    lr, lr_sigma = 1e-3, 0.5
+    for betas in BETAS:
+        for step in STEPS:
+            s = su.host_scalars(lr, lr_sigma, betas, step)
+            assert all(x.dtype == f32 and np.isfinite(x) and x > 0 for x in s), (betas, step, s)
+            b1, b2 = float(f32(betas[0])), float(f32(betas[1]))
+            if 1.0 - b1 ** step == 1.0:        # beta1^step has underflowed against 1
+                assert s[3] == f32(lr) and s[4] == f32(lr_sigma), (betas, step)
+            else:
+                assert s[3] > f32(lr)
+            if b2 == 0.0:
+                assert s[2] == f32(1.0)
+    assert su.host_scalars(lr, lr_sigma, (0.9, 0.999), 1000)[3] == f32(lr)
+    assert su.host_scalars(lr, lr_sigma, (su.BELOW_ONE, 0.0), 2 ** 31 - 1)[3] == f32(lr)
+    assert su.host_scalars(lr, lr_sigma, (su.BELOW_ONE, 0.0), 1)[3] == f32(float(f32(lr)) * 2.0 ** 24)
+    for call in su.CALLS.values():     # the calls themselves: a and a_sigma stay finite
+        if call["kind"] == "adam":
+            assert all(np.isfinite(x) for x in su.host_scalars(call["lr"], call["lr_sigma"], call["betas"], call["step"]))
+    used = [c for c in su.CALLS.values() if c["kind"] == "adam"]
+    assert {c["betas"] for c in used} == set(BETAS) and {c["step"] for c in used} == set(STEPS)
+    assert {c["eps"] for c in used} == {0.0, 1e-8, 1.0}
+    assert {c["lr"] for c in su.CALLS.values()} == {0.0, 1e-3, -0.5, 3e38}
+    assert all(c["lr_sigma"] * c["lr"] < 0 or (c["lr"] == 0 and c["lr_sigma"] < 0) for c in su.CALLS.values())
+
+
+@pytest.mark.parametrize("name", su.CATALOGUE_SCENES)
+def test_catalogue_caps(name):
+    """Every entry is where it should be, often enough; NaN stays a small share, so that bit-exactness judges the
+    rest; sigma goes everywhere a sigma can go."""
+    from tests import update_util as uu
+    c = su.catalogue(name)
+    tree = uu.case(name)["tree"]
+    dd = tree.data_dim
+    internal = np.asarray(tree.child).reshape(-1) != 0
+    mask = c["mask"]
+    assert (mask & internal).sum() >= 3 and (mask & ~internal).sum() > 1000
+    flat = {k: c[k].reshape(-1) for k in ("master", "grad", "m", "v")}
+    sig = {k: c[k].reshape(-1, dd)[:, -1] for k in ("master", "grad", "m", "v")}
+    for label, w0, g, m, v in su.entries():
+        at, leaves = c["coeff"][label], c["sigma"][label]
+        slot = at // dd
+        assert at.size >= 8 and (at % dd != dd - 1).all() and mask[slot].all() and not internal[slot].any(), label
+        assert leaves.size >= 4 and mask[leaves].all() and not internal[leaves].any(), label
+        for key, x in (("master", w0), ("grad", g), ("m", m), ("v", v)):
+            x = np.full(1, x, f32)
+            assert su.same_or_nan(flat[key][at], np.repeat(x, at.size)).all(), (label, key)
+            assert su.same_or_nan(sig[key][leaves], np.repeat(x, leaves.size)).all(), (label, key)
+    marked_elems = int(mask.sum()) * dd
+    for call_name, call in su.CALLS.items():
+        want, expected16 = su.catalogue_expected(name, call_name)
+        nan = int(np.isnan(want["master"]).sum())
+        assert nan <= 0.15 * marked_elems, (call_name, nan, marked_elems)
+        found = su.sigma_outcomes(name, expected16)
+        print(name, call_name, "NaN in master:", nan, "of", marked_elems, "sigma:", found)
+        need = su.SIGMA_OUTCOMES if su.passes_through(call) else ("rises", "falls", "nan")
+        assert all(found[k] > 0 for k in need), (call_name, found)
+        if su.passes_through(call):    # g = m = v = 0: the step hands master through, and the tree rounds it
+            edges = uu.edge_values()
+            for x in edges:
+                at = c["coeff"][f"pass {float(x)!r}"]
+                assert su.same_or_nan(want["master"].reshape(-1)[at], np.repeat(x, at.size)).all(), (call_name, x)
+                with np.errstate(over="ignore"):
+                    h = np.repeat(x, at.size).astype(np.float16)
+                assert su.same_or_nan(expected16.reshape(-1)[at], h).all(), (call_name, x)
+
+
+def test_bitmap_patterns_mark_the_groups_they_name():
+    from tests import update_util as uu
+    for name in ("rgba", "basis1", "sh9", "sh16", "sh25"):
+        tree = uu.case(name)["tree"]
+        slots = tree.capacity * tree.N ** 3
+        patterns = su.bitmap_patterns(slots)
+        assert len(patterns) == 1 + 4 + 2 + len(su.COUNTS) + 2
+        for label, words, groups in patterns:
+            assert words.dtype == np.uint32 and words.size == su.n_words(slots) and groups, (name, label)
+            mask = su.unpack_bits(words, slots)
+            for g in groups:
+                assert mask[g * su.GROUP:(g + 1) * su.GROUP].any(), (name, label, g)
+            named = np.zeros(slots, bool)
+            for g in groups:
+                named[g * su.GROUP:(g + 1) * su.GROUP] = True
+            assert not (mask & ~named).any(), (name, label, "a bit outside the groups the pattern names")
+        counts = [int(su.unpack_bits(w, slots).sum()) for label, w, _ in patterns if "bits in group 0" in label]
+        assert counts == list(su.COUNTS)
+        assert slots % su.GROUP != 0, "the last group is not partial"

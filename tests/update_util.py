@@ -12,13 +12,18 @@ from tests import grad_util as gu
 
 SIGMA_THRESH = 1e-2   # RenderOptions' default
 
+# Depth-4 SG / ASG scenes at the record lengths where vr_tree_step changes its lane layout (3 * basis_dim + 1 = 22, 31,
+# 34, 64, 67: two slots per wave instruction with 20 and with 2 idle lanes, one slot with 30 and with no idle lane,
+# two chunks with three lanes in the second).  Their lobe table (tree.extra) is not part of `data`.
+SHAPE_SCENES = {"asg7": ("ASG", 7), "sg10": ("SG", 10), "sg11": ("SG", 11), "sg21": ("SG", 21), "sg22": ("SG", 22)}
 
 @functools.lru_cache(maxsize=None)
 def case(name):
     """-> dict(tree, ndc, trs (two poses), w, h, f, tuning): the grad tests' small scenes, the 28-level chain (float
     descent), `mixed` -- depth 5 under top_levels = 2, brick_levels = 1, so that most leaves lie below top grid and
     bricks and their sigma exists in node words only -- and `n3`, whose file-side runs (27 * 13 elements) are not
-    whole 16-byte pieces.  `edge_<case>`: the full-catalogue tree of grad_util.EDGE_CASES[case]."""
+    whole 16-byte pieces.  `edge_<case>`: the full-catalogue tree of grad_util.EDGE_CASES[case].  `sh9`, `n4_sh9`
+    and SHAPE_SCENES: the record lengths and runs at which the step and the value passes take another path."""
     tuning = None
     if name == "chain":
         tree, target = common.deep_chain_tree_n2()
@@ -29,6 +34,13 @@ def case(name):
         tree, ndc, tuning = common.small_scene(depth=5, basis_dim=4, seed=77), None, dict(top_levels=2, brick_levels=1)
     elif name == "n3":
         tree, ndc = common.random_tree_general_n(N=3, depth=3, basis_dim=4, seed=5), None
+    elif name == "n4_sh9":   # a run of 64 * 28 halfs: longer than the staged value kernels take, on an aligned array
+        tree, ndc = common.random_tree_general_n(N=4, depth=3, basis_dim=9, seed=22), None
+    elif name == "sh9":      # 17,224 slots: nine 2048-slot groups of the step, the last partial
+        tree, ndc = common.small_scene(depth=5, basis_dim=9, seed=609), None
+    elif name in SHAPE_SCENES:
+        fmt, basis_dim = SHAPE_SCENES[name]
+        tree, ndc = common.small_scene(depth=4, basis_dim=basis_dim, fmt=fmt, seed=600 + basis_dim), None
     elif name.startswith("edge_"):   # the full-catalogue value-domain trees of tests/grad_util.py: NaN, +-inf
         tree, ndc = gu.edge_tree(name[5:], "full"), None
     else:
@@ -43,7 +55,22 @@ def case(name):
     return dict(tree=tree, ndc=ndc, trs=trs, w=w, h=h, f=f, tuning=tuning)
 
 
-CASES = ["sh16", "sh9_near", "sh25", "rgba", "basis1", "n4", "blocked", "ndc", "chain", "mixed", "n3"]
+CASES = ["sh16", "sh9_near", "sh25", "rgba", "basis1", "n4", "blocked", "ndc", "chain", "mixed", "n3",
+         "asg7", "sg10", "sg11", "sg21", "sg22", "n4_sh9", "sh9"]
+
+
+def edge_values():
+    """float32: what the binary32 -> binary16 rounding has to get right -- ties (to even), values around the binary16
+    subnormals and below them, around the largest binary16 and beyond, both signs, +-0, +-inf, NaN."""
+    h = np.float32
+    ties = [1 + 2.0 ** -11, 1 + 3 * 2.0 ** -11, 1 + 2.0 ** -11 + 2.0 ** -20, 1 + 2.0 ** -11 - 2.0 ** -20, 0.1, 1 / 3,
+            2049.0, 2051.0, 2050.5, 1023.75]
+    sub = [2.0 ** -24, 2.0 ** -25, 2.0 ** -25 * (1 + 2.0 ** -20), 3 * 2.0 ** -25, 2.0 ** -26, 2.0 ** -14 * (1 - 2.0 ** -12),
+           2.0 ** -14 - 2.0 ** -25, 2.0 ** -15, 1e-7, 5.5e-8, 1e-40, 2.0 ** -149]
+    big = [65504.0, 65519.0, 65520.0, 65536.0, 70000.0, 1e38, 3.4e38]
+    vals = ties + sub + big
+    vals = vals + [-v for v in vals] + [0.0, -0.0, np.inf, -np.inf, np.nan]
+    return np.array(vals, h)
 
 
 def slot_depths(tree):
