@@ -171,6 +171,31 @@ void or_expf_n(const float* x, float* out, int64_t n) {
 }
 float or_half2float(uint16_t h) { return vr_half_bits_to_float(h); }
 
+/* the small helpers of vr_oracle_core.inc, as the renderer above calls them */
+#define BY_MODE(call_fma, call_strict) \
+    if (fp_mode == OR_FP_FMA) call_fma; else call_strict
+
+uint8_t or_quant8(float v, int fp_mode) {
+    return fp_mode == OR_FP_FMA ? quant8_fma(v) : quant8_strict(v);
+}
+float or_dda_unit(const float cen[3], const float invdir[3], int fp_mode) {
+    return fp_mode == OR_FP_FMA ? dda_unit_fma(cen, invdir) : dda_unit_strict(cen, invdir);
+}
+float or_norm3(const float d[3], int fp_mode) {
+    return fp_mode == OR_FP_FMA ? norm3_fma(d) : norm3_strict(d);
+}
+void or_normalize3(float d[3], int fp_mode) { BY_MODE(normalize3_fma(d), normalize3_strict(d)); }
+void or_mv3(const float m[9], const float v[3], int fp_mode, float out[3]) {
+    BY_MODE(mv3_fma(m, v, out), mv3_strict(m, v, out));
+}
+float or_dot3(const float u[3], const float v[3], int fp_mode) {
+    return fp_mode == OR_FP_FMA ? dot3_fma(u, v) : dot3_strict(u, v);
+}
+void or_cross3(const float a[3], const float b[3], int fp_mode, float out[3]) {
+    BY_MODE(cross3_fma(a, b, out), cross3_strict(a, b, out));
+}
+#undef BY_MODE
+
 void or_basis(const OrTree* tree, const float dir[3], int fp_mode, float out[25]) {
     for (int i = 0; i < 25; ++i) out[i] = 0.f;
     if (fp_mode == OR_FP_FMA)

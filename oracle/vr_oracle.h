@@ -130,6 +130,19 @@ float or_expf(float x);
 void or_expf_n(const float* x, float* out, int64_t n);
 /* fp16 bits -> fp32, exact */
 float or_half2float(uint16_t h);
+/* The renderer's small helpers in either fp model (fp_mode = OR_FP_*), for the tests that run the
+ * kernels' counterparts over whole operand domains:
+ *   or_quant8      float -> uint8 of the frame (volrend.cu:166)
+ *   or_dda_unit    rt_core.cuh:37-49
+ *   or_norm3, or_normalize3 (in place), or_mv3 (column-major 3x3), or_dot3, or_cross3
+ *                  common.cuh:12-55; out must not alias an input */
+uint8_t or_quant8(float v, int fp_mode);
+float or_dda_unit(const float cen[3], const float invdir[3], int fp_mode);
+float or_norm3(const float d[3], int fp_mode);
+void or_normalize3(float d[3], int fp_mode);
+void or_mv3(const float m[9], const float v[3], int fp_mode, float out[3]);
+float or_dot3(const float u[3], const float v[3], int fp_mode);
+void or_cross3(const float a[3], const float b[3], int fp_mode, float out[3]);
 /* SH/SG/ASG basis of a direction (lumisphere.hpp:9-87), out[25] */
 void or_basis(const OrTree* tree, const float dir[3], int fp_mode, float out[25]);
 

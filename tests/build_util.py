@@ -1,6 +1,7 @@
 """How the tests build and run their helper programs: the C restatements (the oracle's flags), the C++ check
-programs of tests/cpp (the host archive's link line), the struct-layout probe, and the parse of a check
-program's `key value` output.  Each command stands here once."""
+programs of tests/cpp (the host archive's link line), the HIP check programs that include the kernels' headers
+(the product's flags), the struct-layout probe, and the parse of a check program's `key value` output.  Each
+command stands here once."""
 from __future__ import annotations
 
 import atexit
@@ -19,15 +20,21 @@ CPP = os.path.join(ROOT, "tests", "cpp")
 
 
 @functools.lru_cache(maxsize=None)
-def c_library(src, defines=()):
+def c_library(src, defines=(), oracle=False):
     """tests/cpp/<src> as a shared library, built with the oracle's flags (its FP model: no contraction, FMA
-    only where fmaf is written) into a directory removed at exit; once per (src, defines)."""
+    only where fmaf is written) into a directory removed at exit; once per argument list.
+    oracle: the file calls liboracle.so's or_* functions."""
     td = tempfile.mkdtemp(prefix="vr_" + os.path.splitext(src)[0] + "_")
     atexit.register(shutil.rmtree, td, ignore_errors=True)
     so = os.path.join(td, "lib" + os.path.splitext(src)[0] + ".so")
+    link = []
+    if oracle:
+        from oracle import binding as ob
+        where = os.path.dirname(ob.build_oracle())
+        link = ["-L", where, "-loracle", "-Wl,-rpath," + where]
     subprocess.check_call(["gcc", "-O2", "-std=c11", "-ffp-contract=off", "-mfma", "-fPIC", "-shared",
                            "-Wno-unused-function", *defines, "-I", os.path.join(ROOT, "oracle"),
-                           os.path.join(CPP, src), "-o", so, "-lm"])
+                           os.path.join(CPP, src), "-o", so, *link, "-lm"])
     return C.CDLL(so)
 
 
@@ -47,6 +54,29 @@ def cpp_program(name, out_dir, gpu=False):
                            os.path.join(CPP, name + ".cpp"), os.path.join(lib_dir, "libvolrend_host.a"),
                            "-L", lib_dir, "-lvolrend_hip", *hip_lib, "-lz", *threads,
                            "-Wl,-rpath," + lib_dir, "-Wl,-rpath,/opt/rocm/lib", "-o", out])
+    return out
+
+
+def hip_program(name, out_dir, c_sources=()):
+    """tests/cpp/<name>.hip, which includes the kernels' headers, compiled with the product's own flags
+    (volrend_amd/build.py FLAGS without -shared / -fPIC: -ffp-contract=off and -fno-gpu-flush-denormals-to-zero are
+    the contract under test) and linked with liboracle.so and the c_library of every file of c_sources -> the
+    program's path.  Skips the calling test when no device is visible."""
+    import torch
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU visible")
+    from oracle import binding as ob
+    from volrend_amd import build as vb
+    ob.build_oracle()
+    flags = [f for f in vb.FLAGS if f not in ("-shared", "-fPIC")]
+    assert "-ffp-contract=off" in flags and "-fno-gpu-flush-denormals-to-zero" in flags
+    libs = [("oracle", os.path.dirname(ob.ORACLE_SO))]
+    libs += [(os.path.splitext(src)[0], os.path.dirname(c_library(src, oracle=True)._name)) for src in c_sources]
+    out = os.path.join(str(out_dir), name)
+    subprocess.check_call([vb.HIPCC, *flags, "-I", vb.CSRC, "-I", os.path.join(ROOT, "include"),
+                           "-I", os.path.join(ROOT, "oracle"), os.path.join(CPP, name + ".hip"),
+                           *[a for lib, where in libs for a in ("-L", where, "-l" + lib, "-Wl,-rpath," + where)],
+                           "-pthread", "-o", out])
     return out
 
 

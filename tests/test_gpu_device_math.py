@@ -3,7 +3,7 @@ against the CPU oracle's C functions (oracle/vr_detmath.h through liboracle.so),
 (any NaN matches any NaN).
 
 tests/cpp/device_math_check.hip includes the header unchanged and is compiled with the product's
-own flags (volrend_amd/build.py FLAGS without -shared / -fPIC), so -ffp-contract=off and
+own flags (build_util.hip_program: volrend_amd/build.py FLAGS without -shared / -fPIC), so -ffp-contract=off and
 -fno-gpu-flush-denormals-to-zero are the contract under test:
   vr_expf / vr_expf2   all 2^32 float bit patterns (vr_expf2: a different pattern in the other lane)
   h2f                  all 65536 half patterns
@@ -11,34 +11,19 @@ own flags (volrend_amd/build.py FLAGS without -shared / -fPIC), so -ffp-contract
   mul_add_half         (b, c) operands: +-0, +-inf, NaN, subnormals, overflowing / underflowing
                        products and a few hundred random values
 """
-import os
 import re
 import subprocess
 
 import pytest
 
-from oracle import binding as ob
-from volrend_amd import build as vb
+from tests import build_util
 
 pytestmark = pytest.mark.gpu
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
 def exe(tmp_path_factory):
-    import torch
-    if not torch.cuda.is_available():
-        pytest.skip("no GPU visible")
-    ob.build_oracle()
-    out = str(tmp_path_factory.mktemp("bin") / "device_math_check")
-    flags = [f for f in vb.FLAGS if f not in ("-shared", "-fPIC")]
-    assert "-ffp-contract=off" in flags and "-fno-gpu-flush-denormals-to-zero" in flags
-    subprocess.check_call([vb.HIPCC, *flags, "-I", vb.CSRC,
-                           os.path.join(ROOT, "tests", "cpp", "device_math_check.hip"),
-                           "-L", os.path.dirname(ob.ORACLE_SO), "-loracle",
-                           "-Wl,-rpath," + os.path.dirname(ob.ORACLE_SO), "-pthread", "-o", out])
-    return out
+    return build_util.hip_program("device_math_check", tmp_path_factory.mktemp("bin"))
 
 
 def run_checks(exe, what):

@@ -56,7 +56,8 @@ struct Cursor {
 // the level-l digit is bit (23-l) of floor(x * 2^24) and the leaf-local
 // coordinate is fract(x * 2^d) for a leaf of depth d -- same leaf, same bits, no float
 // chain, and the digits of several levels index a table at once.
-// Valid while the deepest leaf has d <= 24 (checked at upload).
+// Valid while the deepest leaf has d <= 24 (checked at upload); tests/test_gpu_device_forms.py (n2_axis)
+// compares clamp, digits and the local coordinate of every depth 1..24 with the recurrence for every non-NaN x.
 // Returns the leaf id; *depth = d (child words the reference reads = d), *word low 16 bits = sigma.
 // BLK: entry order of the bricks -- 0 x-major, 1 blocked (both compile-time: the production flavours
 // exist once per order, a launch-uniform branch in the march round costs C1 1.5 %), -1 = as

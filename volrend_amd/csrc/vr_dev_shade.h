@@ -248,6 +248,18 @@ __device__ __forceinline__ void channel_sums(const char* row, GET&& get, float* 
     if constexpr (BASIS >= 4) add_group<FMA, BASIS, 1, 3, FENCE>(row, get, acc);
 }
 
+// rt_core.cuh:161 / volrend.cu:126: the colour of a channel sum, in the three spellings the kernels use.
+// (tests/cpp/device_forms_check.hip runs them over every float.)
+__device__ __forceinline__ float sigmoid(float x) { return 1.f / (1.f + vr_expf(-x)); }
+__device__ __forceinline__ float weighted_sigmoid(float weight, float x) {
+    return weight / (1.f + vr_expf(-x));
+}
+// two channels at once: their exponentials share packed mul / fma / add instructions
+__device__ __forceinline__ float2v weighted_sigmoid2(float weight, float x0, float x1) {
+    const float2v e01 = vr_expf2((float2v){-x0, -x1}) + splat2(1.f);
+    return (float2v){weight / e01.x, weight / e01.y};
+}
+
 __device__ __forceinline__ uint32_t quant8(float v) {
     // float -> uint8 the way a host build of the reference converts
     // (truncate to int32, keep the low byte); volrend.cu:166

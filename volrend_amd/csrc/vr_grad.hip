@@ -286,7 +286,7 @@ __global__ __launch_bounds__(kWave, kGradWaves) void grad_kernel(const KParams p
                         }
 #pragma unroll
                         for (int ch = 0; ch < 3; ++ch) {
-                            c[ch] = 1.f / (1.f + vr_expf(-u[ch]));
+                            c[ch] = sigmoid(u[ch]);
                             dc[ch] = c[ch] * (1.f - c[ch]);
                             if constexpr (BASIS == BASIS_1) dc[ch] *= (float)0.28209479177387814;
                         }

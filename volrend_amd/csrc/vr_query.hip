@@ -86,15 +86,15 @@ __device__ __forceinline__ void colour_of(const KParams& p, uint32_t leaf, const
     } else if constexpr (COL == BASIS_1) {
         // a basis size the reference's switch does not know: basis 0 of each channel (rt_core.cuh:131)
         const float b0 = (float)0.28209479177387814;
-        rgb[0] = 1.f / (1.f + vr_expf(-(b0 * rec.at(0))));
-        rgb[1] = 1.f / (1.f + vr_expf(-(b0 * rec.at(1))));
-        rgb[2] = 1.f / (1.f + vr_expf(-(b0 * rec.at(2))));
+        rgb[0] = sigmoid(b0 * rec.at(0));
+        rgb[1] = sigmoid(b0 * rec.at(1));
+        rgb[2] = sigmoid(b0 * rec.at(2));
     } else {
         float basis_fn[VR_MAX_BASIS];
         precalc_basis<0, false, COL>(p, dir, basis_fn);
-        rgb[0] = 1.f / (1.f + vr_expf(-channel_dot<0, COL, 0>(basis_fn, rec)));
-        rgb[1] = 1.f / (1.f + vr_expf(-channel_dot<0, COL, 1>(basis_fn, rec)));
-        rgb[2] = 1.f / (1.f + vr_expf(-channel_dot<0, COL, 2>(basis_fn, rec)));
+        rgb[0] = sigmoid(channel_dot<0, COL, 0>(basis_fn, rec));
+        rgb[1] = sigmoid(channel_dot<0, COL, 1>(basis_fn, rec));
+        rgb[2] = sigmoid(channel_dot<0, COL, 2>(basis_fn, rec));
     }
 }
 

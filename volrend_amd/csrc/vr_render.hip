@@ -350,10 +350,10 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void VR_R
                         channel_sums<FMA, BASIS>(row, basis_get, acc);
                         // rt_core.cuh:161: weight / (1 + expf(-tmp)) per channel
                         // (the sigmoids of channels 0 / 1 share packed mul / fma / add instructions)
-                        const float2v e01 = vr_expf2((float2v){-acc[0], -acc[1]}) + splat2(1.f);
-                        r0 = weight / e01.x;
-                        r1 = weight / e01.y;
-                        r2 = weight / (1.f + vr_expf(-acc[2]));
+                        const float2v s01 = weighted_sigmoid2(weight, acc[0], acc[1]);
+                        r0 = s01.x;
+                        r1 = s01.y;
+                        r2 = weighted_sigmoid(weight, acc[2]);
                     }
                     if (ST::kPasses > 1) __syncthreads();  // rows are free for the next pass
                 }
@@ -364,9 +364,9 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void VR_R
             Record<BASIS> rec;
             load_record<BASIS>(p, it_leaf[jmine], rec);
             if (HAS_BASIS) {  // runtime basis size: first coefficient of each channel only
-                r0 = weight / (1.f + vr_expf(-(b0 * rec.at(0))));
-                r1 = weight / (1.f + vr_expf(-(b0 * rec.at(1))));
-                r2 = weight / (1.f + vr_expf(-(b0 * rec.at(2))));
+                r0 = weighted_sigmoid(weight, b0 * rec.at(0));
+                r1 = weighted_sigmoid(weight, b0 * rec.at(1));
+                r2 = weighted_sigmoid(weight, b0 * rec.at(2));
             } else {  // RGBA: out[c] = madd(colour, weight, out[c]) is formed by the owner
                 r0 = rec.at(0);
                 r1 = rec.at(1);
@@ -597,10 +597,14 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void VR_R
                     // taken now; the colour of this sample -- which nothing else depends on --
                     // becomes a work item for the shade phase.
                     if (COUNT) rc.hits++;
-                    // vr_expf_nonan: the argument is never NaN -- sigma > sigma_thresh is false
-                    // for a NaN sigma, and delta_t (>= step_size > 0) and delta_scale are finite
-                    // and positive, so a sigma of +inf gives -inf, not NaN.  (Only a product
-                    // delta_t * delta_scale below 2^-150 could meet an infinite sigma as 0 * inf.)
+                    // vr_expf_nonan: for a ray with a finite, non-zero direction the argument is not
+                    // NaN -- sigma > sigma_thresh is false for a NaN sigma, delta_scale = 1 / |dir| is
+                    // finite and positive, and delta_t is never NaN (dda_unit is a minimum with 1e4,
+                    // which drops a NaN), so a sigma of +inf gives +-inf.  (Only a product
+                    // delta_t * delta_scale that rounds to 0, below 2^-150, could meet an infinite sigma
+                    // as 0 * inf.)  Every non-NaN argument, +-inf included, gives the bits of vr_expf
+                    // (tests/test_gpu_device_forms.py sweeps them all); a NaN one -- a ray list may hand
+                    // in a direction that is not finite -- gives 0 or +inf where vr_expf gives NaN.
                     const float att = vr_expf_nonan(-delta_t * ray.delta_scale * sigma);
                     weight = ray.light * (1.f - att);
                     if constexpr (AOV) depth_set(P::madd(weight, ray.t, depth_get()));
@@ -1021,7 +1025,7 @@ __global__ void probe_overlay_kernel(const KParams p) {
             const int off = tt * p.basis_dim;
             float tmp = 0.f;
             for (int i = lo; i <= hi; ++i) tmp = P::madd(basis_fn[i], p.probe_coeffs[off + i], tmp);
-            out[tt] = 1.f / (1.f + vr_expf(-tmp));
+            out[tt] = sigmoid(tmp);
         }
     } else {
         for (int i = 0; i < 3; ++i) out[i] = p.probe_coeffs[i];
