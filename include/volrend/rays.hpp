@@ -1,6 +1,6 @@
-// volrend::render_rays / accumulate_weights_rays / render_backward_rays -- colour, leaf weights and gradients
-// along caller-supplied rays, over the HIP C ABI (vr_render_rays, vr_accumulate_weights_rays,
-// vr_render_backward_rays; include/volrend_hip.h has the semantics).  What an optimiser of a PlenOctree calls
+// volrend::render_rays / accumulate_weights_rays / render_backward_rays / fit_rays -- colour, leaf weights,
+// gradients and the fused L2 loss + gradient along caller-supplied rays, over the HIP C ABI (vr_render_rays,
+// vr_accumulate_weights_rays, vr_render_backward_rays, vr_fit_rays; include/volrend_hip.h has the semantics).  What an optimiser of a PlenOctree calls
 // per step with rays drawn from all its training images; the reference renderer has no counterpart.
 // Asynchronous like launch_renderer: each returns after enqueueing one launch on `stream` (a hipStream_t passed
 // as void*); each throws std::runtime_error ("vr_render_rays: ..." etc.) where the C call refuses its arguments.
@@ -40,6 +40,20 @@ void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOpti
 void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options,
                           const float* grad_accum, float* grad_data, uint32_t* touched, void* stream,
                           int fp_mode = VR_FP_STRICT);
+
+// The L2 loss of the rays against target colours and its gradient with respect to the tree, in one launch
+// (vr_fit_rays): what render_rays (accum), the composite over background_brightness, the residual and the marked
+// render_backward_rays compute in sequence.  The loss is grad_scale / 2 * sum r^2 over rays and channels.
+struct Fit {
+    const float* target = nullptr;  // device, float32 [n][3]: the colour ray i should have
+    float grad_scale = 0.f;         // finite; 2 / (3 n) for the mean
+    float* grad_data = nullptr;     // as render_backward_rays: added into, required
+    uint32_t* touched = nullptr;    // ORed into; nullptr = not wanted
+    float* sq_err = nullptr;        // [n]: the squared residual of ray i summed over channels; nullptr = not wanted
+    float* accum = nullptr;         // [n][4]: the bits render_rays gives; nullptr = not wanted
+};
+void fit_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, const Fit& fit, void* stream,
+              int fp_mode = VR_FP_STRICT);
 
 // Sizes n_slots launch slots so that no later ray call of <= n rays on them allocates (vr_reserve_rays).
 void reserve_rays(const N3Tree& tree, int64_t n, int n_slots = 2);

@@ -505,6 +505,49 @@ int vr_render_backward_touched(vr_tree_t tree, int n_frames, const VrCamera* cam
 int vr_render_backward_rays_touched(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
                                     int fp_mode, const float* grad_accum, float* grad_data, uint32_t* touched,
                                     void* stream);
+/* ---- Fused L2 loss and backward of a ray list ---- */
+/* What every optimiser loop over ray batches writes as vr_render_rays(accum) -> composite, residual against a
+ * target colour, grad_accum -> vr_render_backward_rays_touched, in ONE launch: the march forms out[], the loss
+ * head and its gradient itself, and no [n][4] array travels between kernels.  For ray i:
+ *   out[0..3]  trace_ray's output for the ray exactly as vr_render_rays forms it in FP model fp_mode (what
+ *              VrRayOut.accum receives), the early-stop rescale and out[3] = 1 on a stop included.
+ *   The loss head is not part of trace_ray: uncontracted binary32 in BOTH FP models, one rounding per operator,
+ *   in this order, with bg = opt->background_brightness:
+ *     na = 1.f - out[3]
+ *     pred_ch = out[ch] + bg * na
+ *     r_ch = pred_ch - target[i][ch]
+ *     sq_err[i] = (r_0 * r_0 + r_1 * r_1) + r_2 * r_2
+ *     g_ch = grad_scale * r_ch
+ *     g_3 = -(bg * ((g_0 + g_1) + g_2))
+ *   i.e. the gradient of L = grad_scale / 2 * sum_i sum_ch r_{i,ch}^2 with respect to out[]; grad_scale =
+ *   2 / (3 n) makes L the mean squared error.
+ *   grad_data  receives what vr_render_backward_rays adds for grad_accum[i] = (g_0, g_1, g_2, g_3): the same
+ *              formulas, the same "the order of the sum is not defined", the same rule for non-finite values
+ *              (a non-finite target or grad_scale * r puts the ray outside the formulas as a non-finite
+ *              grad_accum pixel does) and the same untouched-elements rule.
+ *   touched    receives what vr_render_backward_rays_touched ORs in: a slot is marked when a hit sample falls
+ *              into it, whatever the value added -- a batch whose residual is zero still marks.
+ * accum and sq_err are bit-reproducible; grad_data is reproducible up to its summation order, as for the
+ * backward calls.  A ray that never enters the volume has out[] = 0: it gets its sq_err / accum and adds nothing.
+ * Contract: that of vr_render_backward_rays -- enqueue only, on a launch slot (vr_reserve_rays of the same n
+ * covers it), on the tree's device, 0 <= n < 2^30, n == 0 uploads the file-order table and launches nothing, the
+ * sample guard reports through vr_tree_status, the tree is only read.
+ * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed: NULL tree / rays / origins / dirs / opt / fit /
+ * target / grad_data, unknown fp_mode, n outside the range, a bad step_size, a non-finite grad_scale.
+ * VR_ERR_UNSUPPORTED: what vr_render_backward_rays refuses -- render_depth, enable_probe, non-zero rot_dirs, a
+ * narrowed basis_minmax, SG / ASG trees -- with vr_fit_rays named in the message.
+ * Not offered: frame (camera) siblings, losses other than L2, per-ray weights, a background other than
+ * background_brightness, gradients with respect to the rays. */
+typedef struct VrFit {       /* device pointers on the tree's device */
+    const float* target;     /* [n][3] float32: the colour ray i should have */
+    float        grad_scale; /* finite; L = grad_scale / 2 * sum_i sum_ch r_{i,ch}^2.  2 / (3 n) for the mean */
+    float*       grad_data;  /* as vr_render_backward_rays: ADDED into, required */
+    uint32_t*    touched;    /* as vr_render_backward_rays_touched: ORed into; NULL = not wanted */
+    float*       sq_err;     /* [n]: r_0^2 + r_1^2 + r_2^2 of ray i; NULL = not wanted */
+    float*       accum;      /* [n][4]: what vr_render_rays gives in VrRayOut.accum; NULL = not wanted */
+} VrFit;
+int vr_fit_rays(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
+                int fp_mode, const VrFit* fit, void* stream);
 /* Sizes n_slots (1..8) launch slots so that no later ray call of <= n rays on them allocates or blocks (the
  * colour record plus the scratch of a call without rgba: 80-232 bytes per ray).  Optional; synchronous. */
 int vr_reserve_rays(vr_tree_t tree, int64_t n, int n_slots);

@@ -89,6 +89,11 @@ class VrRayOut(C.Structure):
     _fields_ = [("rgba", C.c_void_p), ("accum", C.c_void_p)]
 
 
+class VrFit(C.Structure):
+    _fields_ = [("target", C.c_void_p), ("grad_scale", C.c_float), ("grad_data", C.c_void_p),
+                ("touched", C.c_void_p), ("sq_err", C.c_void_p), ("accum", C.c_void_p)]
+
+
 class VrStep(C.Structure):
     _fields_ = [("master", C.c_void_p), ("grad", C.c_void_p), ("touched", C.c_void_p), ("m", C.c_void_p),
                 ("v", C.c_void_p), ("kind", C.c_int32), ("lr", C.c_float), ("lr_sigma", C.c_float),
@@ -149,6 +154,8 @@ PROTOTYPES = {
                                              C.c_int, C.POINTER(VrLeafWeights), C.c_void_p]),
     "vr_render_backward_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vr_fit_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
+                              C.POINTER(VrFit), C.c_void_p]),
     "vr_reserve_rays": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     "vr_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "vr_reserve_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -205,7 +205,7 @@ def render_backward(tree, cam: Camera, transforms, options: RenderOptions, grad_
     return res["grad_data"]
 
 
-# ---- ray lists (vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays) ----
+# ---- ray lists (vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays / vr_fit_rays) ----
 def render_rays(tree, origins, dirs, options: RenderOptions, *, want=("accum",), rgba=None, accum=None,
                 fp_mode: int = _abi.FP_STRICT, stream=None, n=None) -> dict:
     """Colour along caller-supplied rays -- vr_render_rays, one launch, enqueued on ``stream``.
@@ -267,6 +267,41 @@ def render_backward_rays(tree, origins, dirs, options: RenderOptions, grad_accum
     _marked_call(L.vr_render_backward_rays, L.vr_render_backward_rays_touched, c.ptr.get("touched"), handle, c.n,
                  C.byref(rays), C.byref(o), int(fp_mode), g, d, stream=stream)
     return res["grad_data"]
+
+
+def fit_rays(tree, origins, dirs, options: RenderOptions, target, *, grad_scale, grad_data=None, touched=None,
+             want=("sq_err",), fp_mode: int = _abi.FP_STRICT, n=None, stream=None) -> dict:
+    """The L2 loss of the rays of a list against ``target`` and its gradient with respect to the tree's values --
+    vr_fit_rays, one launch: what ``render_rays`` ("accum"), the composite over background_brightness, the
+    residual and the marked ``render_backward_rays`` compute in sequence.
+
+    ``origins`` / ``dirs``: as ``render_rays`` takes them.  ``target``: float32 [n, 3], the colour ray i should
+    have.  ``grad_scale``: a finite number; the loss is grad_scale / 2 * sum r^2 over rays and channels, r the
+    composite minus the target -- 2 / (3 n) for the mean.  ``grad_data`` / ``touched``: as ``render_backward_rays``
+    takes them (added into / ORed into; ``grad_data`` is allocated zeroed when not given).  ``want``: "sq_err"
+    (float32 [n]: r_0^2 + r_1^2 + r_2^2 per ray) and / or "accum" (float32 [n, 4]: the bits of ``render_rays``),
+    or neither.  Returns a dict of torch tensors: "grad_data" and what ``want`` names.  include/volrend_hip.h has
+    the operations of the loss head; "sq_err" and "accum" are bit-reproducible."""
+    handle = tree.handle
+    want = parse_want(want, ("sq_err", "accum"))
+    scale = float(grad_scale)
+    if not abs(scale) <= float(np.finfo(np.float32).max):   # (NaN fails the comparison too)
+        raise ValueError(f"grad_scale must be a finite float32, not {grad_scale!r}")
+    bufs = _ray_bufs(origins, dirs) + [Buf("target", target, (F32,), ("n", 3))]
+    c, res = outputs(tree, bufs + _marks(tree, touched),
+                     {"grad_data": (F32, (tree.capacity, tree.N, tree.N, tree.N, tree.data_dim))},
+                     {"grad_data": grad_data}, ("grad_data",), zeros=True, n=n)
+    res.update(allocate(c, {"sq_err": (F32, ("n",)), "accum": (F32, ("n", 4))}, {}, want, zeros=False))
+    rays, o, fit = _rays_c(c), options.to_c(), _abi.VrFit()
+    fit.target, fit.grad_scale, fit.grad_data = c.ptr["target"], scale, c.ptr["grad_data"]
+    fit.touched = c.ptr.get("touched")
+    if c.n == 0:  # (empty tensors have no address to pass; the call only uploads the file-order table)
+        rays.origins = rays.dirs = fit.target = fit.grad_data
+    else:
+        fit.sq_err, fit.accum = c.ptr.get("sq_err"), c.ptr.get("accum")
+    _abi.check(_abi.lib().vr_fit_rays(handle, c.n, C.byref(rays), C.byref(o), int(fp_mode), C.byref(fit),
+                                      _stream_ptr(stream)))
+    return res
 
 
 # ---- the values of the device copy, in place (vr_tree_update_data / vr_tree_read_data) ----

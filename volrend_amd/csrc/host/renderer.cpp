@@ -187,6 +187,14 @@ void render_backward_rays(const N3Tree& tree, const Rays& rays, const RenderOpti
                        "vr_render_backward_rays_touched");
 }
 
+void fit_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, const Fit& fit, void* stream,
+              int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const VrRays r{rays.origins, rays.dirs};
+    const VrFit f{fit.target, fit.grad_scale, fit.grad_data, fit.touched, fit.sq_err, fit.accum};
+    internal::vr_check(vr_fit_rays(tree.device, rays.n, &r, &o, fp_mode, &f, stream), "vr_fit_rays");
+}
+
 void reserve_rays(const N3Tree& tree, int64_t n, int n_slots) {
     internal::vr_check(vr_reserve_rays(tree.device, n, n_slots), "vr_reserve_rays");
 }

@@ -1,5 +1,5 @@
 // vr_internal.h -- shared between the C-ABI host layer (vr_api.cpp, vr_upload.cpp, vr_launch.cpp, vr_slots.cpp, vr_values.cpp) and
-// the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_grad.hip, vr_update.hip, vr_tree_kernels.hip).  Not part of the public ABI.
+// the gfx950 kernels (vr_render.hip, vr_weights.hip, vr_grad.hip, vr_fit.hip, vr_update.hip, vr_tree_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -334,6 +334,24 @@ struct GradParams {
 // (rays: as launch_weights; GradParams.grad_accum is then [n][4], row i for ray i)
 hipError_t launch_grad(const KParams& p, const GradParams& g, int fp_mode, int n_cus, int waves_override,
                        int gen_waves, hipStream_t stream, const RayList* rays = nullptr);
+
+// ---------------------------------------------------------------------------
+// Fused loss and backward of a ray list (vr_fit_rays, vr_fit.hip): the backward list's records and queues, and
+// a march that forms out[], the L2 loss head and its gradient itself instead of reading grad_accum.
+// ---------------------------------------------------------------------------
+struct FitParams {
+    const float* target;        // [n][3]: the colour ray i should have
+    float* grad_data;           // as GradParams
+    const int32_t* file_node;
+    uint32_t* touched;          // ORed into; NULL = not wanted (a run-time test, one set of kernels)
+    float* sq_err;              // [n]; NULL = not wanted
+    float* accum;               // [n][4]: trace_ray's out[]; NULL = not wanted
+    float bg, grad_scale;       // background_brightness; g_ch = grad_scale * r_ch
+};
+// vr_fit.hip: ray generation (which also writes the outputs of the rays that never enter the volume) + the
+// persistent march.  `rays` is required: the call exists for lists only.
+hipError_t launch_fit(const KParams& p, const FitParams& f, int fp_mode, int n_cus, int waves_override, int gen_waves,
+                      hipStream_t stream, const RayList* rays);
 
 // ---------------------------------------------------------------------------
 // Value passes (vr_tree_update_data / vr_tree_read_data, vr_update.hip): the tree's values between the file's

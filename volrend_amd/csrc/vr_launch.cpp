@@ -1,6 +1,6 @@
 // vr_launch.cpp -- the march launches (include/volrend_hip.h): vr_render_batch, vr_render_aov, vr_accumulate_weights,
 // vr_render_backward and their ray-list siblings vr_render_rays / vr_accumulate_weights_rays / vr_render_backward_rays
-// (the backward calls also in their marked form, *_touched):
+// (the backward calls also in their marked form, *_touched) and vr_fit_rays, the fused loss + backward of a list:
 // argument checks, launch geometry, KParams, and the ONE sequence they all go through (run_launch).  The scheduling
 // rules are vr_launch_plan.cpp, the launch-slot ring is vr_slots.cpp.  Built with -ffp-contract=off (the host-side
 // Rodrigues pre-computation below must round like the oracle).
@@ -581,6 +581,34 @@ int vr_render_backward_rays_touched(vr_tree_t t, int64_t n, const VrRays* rays, 
     if (!touched) return fail(VR_ERR_INVALID_ARGUMENT, "vr_render_backward_rays_touched: NULL argument");
     return backward_rays("vr_render_backward_rays_touched", t, n, rays, opt, fp_mode, grad_accum, grad_data, touched,
                          stream);
+}
+
+// vr_fit_rays: the checks of backward_rays (its `out` is the VrFit), then a backward launch whose march forms
+// grad_accum itself.
+int vr_fit_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode, const VrFit* fit,
+                void* stream) {
+    const char* const what = "vr_fit_rays";
+    vr::KParams k;
+    memset(&k, 0, sizeof(k));
+    Views v;
+    if (int rc = validate_rays(what, t, n, rays, opt, fp_mode, fit, k, v)) return rc;
+    if (!fit->target || !fit->grad_data) return fail(VR_ERR_INVALID_ARGUMENT, "%s: NULL argument", what);
+    if (!std::isfinite(fit->grad_scale))
+        return fail(VR_ERR_INVALID_ARGUMENT, "%s: grad_scale must be finite (got %g)", what, (double)fit->grad_scale);
+    if (int rc = check_backward_options(what, opt)) return rc;
+    if (int rc = check_backward_tree(t, opt, what)) return rc;
+    return march_launch(t, LaunchKind::kBackward, v, opt, k, stream, [&](const Turn& u) {
+        vr::FitParams f;
+        f.target = fit->target;
+        f.grad_data = fit->grad_data;
+        f.file_node = t->file_node_dev.get<int32_t>();
+        f.touched = fit->touched;
+        f.sq_err = fit->sq_err;
+        f.accum = fit->accum;
+        f.bg = opt->background_brightness;
+        f.grad_scale = fit->grad_scale;
+        return vr::launch_fit(u.k, f, fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs, v.rays());
+    });
 }
 
 int vr_accumulate_weights(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,

@@ -8,7 +8,8 @@ master: the rounding is treated as the identity, as mixed-precision optimisers t
 half a binary16 ulp of a value therefore moves the master but not yet the render.
 
 ``SparseTreeOptimizer`` is the loop whose cost follows the rays and not the size of the tree: ``render_rays`` ->
-(the caller's loss) -> the marked ``render_backward_rays`` -> ``tree_step`` over the slots the rays hit.  The tree
+(the caller's loss) -> the marked ``render_backward_rays`` -> ``tree_step`` over the slots the rays hit, or
+``fit_rays`` -> ``tree_step`` where the loss is L2 against target colours.  The tree
 is always current, so nothing is rewritten whole, no dense gradient is zeroed and no dense optimiser pass runs.
 """
 from __future__ import annotations
@@ -65,7 +66,9 @@ class SparseTreeOptimizer:
     Owns ``master`` (float32, from ``read_data(float32)``), ``grad`` (float32, zero between steps), the bitmap
     ``touched`` and, for kind="adam", the moments ``m`` and ``v`` -- all in the file's indexing.  One iteration:
     ``accum = opt.render(origins, dirs)``; form dL/d accum; ``opt.backward(origins, dirs, grad_accum)``;
-    ``opt.step()``.  Several ``backward`` calls before one ``step`` accumulate.  Everything is enqueued on the
+    ``opt.step()`` -- or, for the L2 loss against target colours, ``opt.fit(origins, dirs, target)``; ``opt.step()``,
+    which is one launch where the former is two and a loss head in torch.  Several ``backward`` / ``fit`` calls
+    before one ``step`` accumulate.  Everything is enqueued on the
     current stream.  The gradient is handed straight through the binary16 rounding, as ``TreeRays`` does; Adam's
     moments of slots a step does not touch stand still (sparse-Adam semantics)."""
 
@@ -95,6 +98,16 @@ class SparseTreeOptimizer:
         api.render_backward_rays(self.tree, origins, dirs, self.options, grad_accum.contiguous().to(torch.float32),
                                  grad_data=self.grad, fp_mode=self.fp_mode, touched=self.touched,
                                  stream=torch.cuda.current_stream(self.master.device))
+
+    def fit(self, origins, dirs, target, grad_scale: "float | None" = None):
+        """``render``, the L2 loss against ``target`` [n, 3] and ``backward`` in one launch (``fit_rays``): adds the
+        gradient of grad_scale / 2 * sum r^2 into ``grad``, marks the slots and returns the squared error per ray
+        [n].  ``grad_scale`` defaults to 2 / (3 n): the mean over rays and channels."""
+        if grad_scale is None:
+            grad_scale = 2.0 / (3 * max(int(target.shape[0]), 1))
+        return api.fit_rays(self.tree, origins, dirs, self.options, target, grad_scale=grad_scale,
+                            grad_data=self.grad, touched=self.touched, want=("sq_err",), fp_mode=self.fp_mode,
+                            stream=torch.cuda.current_stream(self.master.device))["sq_err"]
 
     def step(self) -> None:
         """The optimiser step over the marked slots; afterwards ``grad`` and ``touched`` are zero again."""
