@@ -10,7 +10,7 @@ division, a square root, a float -> int conversion or an FP64 product under -ffp
 One pass over every float bit pattern x ("sweep"; NaN patterns stay out only where a row says so; sigmoid, sigmoid2,
 floor, invdir, div and the drawn-k part of ldexp_div take every OTHERS_EVERY-th pattern, see below):
   expf_nonan      vr_expf_nonan against or_expf; NaN is outside its contract: 2^32 - 2 (2^23 - 1) patterns
-  sigmoid         sigmoid(x) of vr_dev_shade.h, the spelling of vr_render.hip, vr_query.hip and vr_grad.hip
+  sigmoid         sigmoid(x) of vr_dev_shade.h, the spelling of vr_render.hip, vr_query.hip and vr_dev_backward.h
   sigmoid2        weighted_sigmoid2(1, x, partner(x)): one count per pair, both components compared
   quant8          quant8(x) against the oracle's
   recip, sqrt, floor, invdir

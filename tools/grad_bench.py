@@ -104,7 +104,7 @@ def main():
     hits_per_frame = int(hits.view(-1).to(torch.int64).bitwise_and(0xFFFFFFFF).sum().item()) / (n_sets * nf)
     del hits
     basis = stree.basis_dim
-    run = 3 * basis + 1 if basis in (4, 9, 16, 25) else 4     # floats a hit adds (vr_grad.hip GradTraits::kRun)
+    run = 3 * basis + 1 if basis in (4, 9, 16, 25) else 4     # floats a hit adds (vr_dev_backward.h GradTraits::kRun)
 
     # clocks and caches up, the buffer sees the whole pass, launches per window
     for key in KEYS:

@@ -1,6 +1,7 @@
 // vr_dev_march.h -- the guided march frame: render_kernel's march phase (vr_render.hip) without records, as the
-// consumers that need no colour pipeline run it -- weights_kernel (vr_weights.hip); grad_kernel (vr_grad.hip) takes
-// its ray generation and query kind from here and keeps a written-out copy of the loop, which measured faster.
+// consumers that need no colour pipeline run it -- weights_kernel (vr_weights.hip); backward_kernel
+// (vr_dev_backward.h, the one march of vr_grad.hip and vr_fit.hip) takes its ray generation and query kind from here
+// and keeps one written-out copy of the loop, which measured faster.
 // One wave per workgroup; a wave owns a chunk of consecutive ray ids (grab_chunk) and refills its idle lanes once
 // refill_min of them wait.  A lane's ray is alive while t < tmax (a stopped ray gets tmax = -1, a lane without a
 // ray has t = 0, tmax = -1).  Stated once here: the query kind, retire and refill, the sample guard, the sample
@@ -9,9 +10,10 @@
 // so a sample's leaf, delta_t and weight have the bits trace_ray (rt_core.cuh:66-196) gives them.
 // The state stays in plain locals of the kernel: the per-lane part is handed in by reference, the wave-uniform
 // part goes in and comes back by value (MarchFeed).  Other forms cost ten VGPRs (EXPERIMENTS.md "One march frame").
-// For the .hip files only: device functions and kernels, and the two host functions that pick among them
-// (query_kind, launch_march_raygen).
+// For the .hip files only: device functions and kernels, and the host functions that pick among them
+// (query_kind / dispatch_query, launch_raygen_waves / launch_march_raygen).
 #pragma once
+#include <type_traits>
 #include "vr_device_math.h"
 #include "vr_internal.h"
 #include "vr_dev_layout.h"
@@ -26,6 +28,13 @@ namespace {
 enum { kQueryN2 = 0, kQueryN2Blocked = 1, kQueryGeneric = 2 };
 inline int query_kind(const KParams& p) {
     return !uses_lookup(p) ? kQueryGeneric : (p.brick_blocked ? kQueryN2Blocked : kQueryN2);
+}
+// f(std::integral_constant<int, the kind>): what a launcher instantiates its kernels over.
+template <typename F>
+void dispatch_query(int query, F&& f) {
+    if (query == kQueryGeneric) f(std::integral_constant<int, kQueryGeneric>());
+    else if (query == kQueryN2Blocked) f(std::integral_constant<int, kQueryN2Blocked>());
+    else f(std::integral_constant<int, kQueryN2>());
 }
 
 // ---------------------------------------------------------------------------
@@ -96,18 +105,23 @@ __global__ __launch_bounds__(kWave* GW) void march_raygen_rays_kernel(const KPar
     store_march_record<GW, Record>(p, valid, lane, wave, nr, vdir, id);
 }
 
-template <int FMA, typename Record, int GW>
-void launch_march_raygen_gw(const KParams& p, hipStream_t s, const RayList* rays) {
-    const dim3 grid((unsigned)((p.n_wave_blocks * p.n_frames + GW - 1) / GW)), block(kWave * GW);
-    if (rays) hipLaunchKernelGGL((march_raygen_rays_kernel<FMA, GW, Record>), grid, block, 0, s, p, *rays);
-    else hipLaunchKernelGGL((march_raygen_kernel<FMA, GW, Record>), grid, block, 0, s, p);
+// Ray generation of a march launch runs in workgroups of 16 or 4 waves (gen_waves: vr_launch.cpp raygen_waves), one
+// wave per block of 64 ray ids: launch(std::integral_constant<int, GW>, grid, block) starts the kernel of that GW.
+template <typename Launch>
+void launch_raygen_waves(const KParams& p, int gen_waves, Launch&& launch) {
+    const int gw = gen_waves >= 16 ? 16 : 4;
+    const dim3 grid((unsigned)((p.n_wave_blocks * p.n_frames + gw - 1) / gw)), block(kWave * gw);
+    if (gw == 16) launch(std::integral_constant<int, 16>(), grid, block);
+    else launch(std::integral_constant<int, 4>(), grid, block);
 }
-// Ray generation of a march launch in workgroups of 16 or 4 waves (gen_waves: vr_launch.cpp raygen_waves), over
-// the pixels of the frame table or over `rays`.
+// Records of `Record`, over the pixels of the frame table or over `rays`.
 template <int FMA, typename Record>
 void launch_march_raygen(const KParams& p, int gen_waves, hipStream_t s, const RayList* rays) {
-    if (gen_waves >= 16) launch_march_raygen_gw<FMA, Record, 16>(p, s, rays);
-    else launch_march_raygen_gw<FMA, Record, 4>(p, s, rays);
+    launch_raygen_waves(p, gen_waves, [&](auto gw, dim3 grid, dim3 block) {
+        constexpr int GW = decltype(gw)::value;
+        if (rays) hipLaunchKernelGGL((march_raygen_rays_kernel<FMA, GW, Record>), grid, block, 0, s, p, *rays);
+        else hipLaunchKernelGGL((march_raygen_kernel<FMA, GW, Record>), grid, block, 0, s, p);
+    });
 }
 
 // ---------------------------------------------------------------------------

@@ -197,7 +197,7 @@ inline bool needs_full(const KParams& p) {
     return p.format == VR_FORMAT_SG || p.format == VR_FORMAT_ASG || p.instrumented || p.render_depth;
 }
 
-// The grid of a persistent march kernel (render_kernel, weights_kernel, grad_kernel; one wave per workgroup) over
+// The grid of a persistent march kernel (render_kernel, weights_kernel, backward_kernel; one wave per workgroup) over
 // total_blocks blocks of 64 rays: enough waves to fill the chip -- waves_per_cu of the flavour on each of
 // n_cus -- but no more than about one per 128 pixels (one per 64 rays that enter the volume), so that
 // small launches still rebalance through the ray queue.

@@ -204,7 +204,7 @@ __global__ void refresh_bricks_kernel(const uint32_t* nodes, const int32_t* bric
 // LDS table (a prefix sum of the popcounts places them), and the wave walks the table with its lanes ACROSS the
 // data_dim elements of a slot: the file-side run is contiguous (SH16: 196 bytes of master, grad and the moments
 // each).  Records shorter than half a wave pack kWave / data_dim slots into one instruction, each lane group a run
-// of its own (as GradTraits::kPack).  A slot costs two dependent trips to memory (its device node, then its node
+// of its own (as GradTraits::kPack, vr_dev_backward.h).  A slot costs two dependent trips to memory (its device node, then its node
 // word), and the slots of a batch cluster -- a wave may own two thousand of them -- so kStepFlight slots are in
 // flight per lane at a time: all their loads are issued before the first value is formed (one slot at a time ran
 // at 0.5 TB/s on the bench tree, latency bound).  The wave that owns a word clears it.  The arithmetic is the

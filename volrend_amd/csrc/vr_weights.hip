@@ -145,16 +145,11 @@ hipError_t launch_fp(const KParams& p, const WeightParams& w, int n_cus, int wav
     launch_march_raygen<FMA, WeightRecord>(p, gen_waves, s, rays);
     const dim3 grid(persistent_grid(total_blocks, n_cus, waves_override > 0 ? waves_override : 4 * kWeightWaves));
     const bool hits = w.hits != nullptr;
-    const int query = query_kind(p);
-#define VR_WEIGHTS(Q)                                                              \
-    do {                                                                           \
-        if (hits) launch_march_check<FMA, Q, true>(p, w, check_first, grid, s);    \
-        else launch_march_check<FMA, Q, false>(p, w, check_first, grid, s);        \
-    } while (0)
-    if (query == kQueryGeneric) VR_WEIGHTS(kQueryGeneric);
-    else if (query == kQueryN2Blocked) VR_WEIGHTS(kQueryN2Blocked);
-    else VR_WEIGHTS(kQueryN2);
-#undef VR_WEIGHTS
+    dispatch_query(query_kind(p), [&](auto query) {
+        constexpr int Q = decltype(query)::value;
+        if (hits) launch_march_check<FMA, Q, true>(p, w, check_first, grid, s);
+        else launch_march_check<FMA, Q, false>(p, w, check_first, grid, s);
+    });
     return hipGetLastError();
 }
 
