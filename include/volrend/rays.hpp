@@ -15,7 +15,7 @@ namespace volrend {
 // n rays: device, float32 [n][3] each, world space; a direction may have any finite non-zero length.  Ray i is
 // the ray of a pixel entered behind screen2worlddir's matrix product, marched as an offscreen frame without
 // mesh depth: a list built from a camera gives that frame's bits.  64 consecutive rays share a wave; the
-// library does not reorder them.
+// library does not reorder them (order_rays below computes an order for the caller to apply).
 struct Rays {
     const float* origins = nullptr;
     const float* dirs = nullptr;
@@ -54,6 +54,25 @@ struct Fit {
 };
 void fit_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, const Fit& fit, void* stream,
               int fp_mode = VR_FP_STRICT);
+
+// The order that makes a ray list coherent, and the list gathered into it (vr_order_rays; include/volrend_hip.h
+// has the key and the result rule).  order_out[j] = the index of the ray at sorted position j (a stable sort:
+// unique and bit-reproducible); the march calls above then take origins_out / dirs_out / payload_out, and per-ray
+// outputs go back to the caller's order through order_out.  The caller owns the workspace
+// (order_rays_workspace(n) bytes, 256-byte aligned).  No launch slot: safe beside any launch.
+struct RayOrder {
+    int bits = 0;                    // 1..5 key bits per coordinate; 0 = the library's default
+    uint32_t* order = nullptr;       // device, [n], required
+    uint32_t* keys = nullptr;        // device, [n]: the sorted keys; nullptr = not wanted
+    float* origins_out = nullptr;    // device, [n][3]; nullptr = not wanted
+    float* dirs_out = nullptr;       // device, [n][3], as given (not normalised); nullptr = not wanted
+    const float* payload = nullptr;  // device, [n][payload_dim], e.g. Fit::target; nullptr = none
+    float* payload_out = nullptr;    // required iff payload
+    int payload_dim = 0;             // 1..8 with a payload
+};
+size_t order_rays_workspace(int64_t n);
+void order_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, const RayOrder& out,
+                void* workspace, size_t workspace_bytes, void* stream, int fp_mode = VR_FP_STRICT);
 
 // Sizes n_slots launch slots so that no later ray call of <= n rays on them allocates (vr_reserve_rays).
 void reserve_rays(const N3Tree& tree, int64_t n, int n_slots = 2);

@@ -459,7 +459,8 @@ int vr_render_backward(vr_tree_t tree, int n_frames, const VrCamera* cams, const
  *     call gives for that pixel: RGBA8, accumulators, leaf weights;
  *   - results do not depend on the order of the rays, on n, or on how a list is split into calls (the backward
  *     sum is the exception, exactly as for frames);
- *   - 64 consecutive rays share a wave.  The library does not reorder them: coherence is the caller's business;
+ *   - 64 consecutive rays share a wave.  The library does not reorder them: coherence is the caller's business
+ *     (vr_order_rays, below, computes an order the caller can apply);
  *   - finite origins and finite non-zero directions are the contract; anything else is outside it, as a
  *     non-finite pose is for frames.
  * Each call keeps the contract of its frame sibling: enqueue only, on a launch slot, on the tree's device
@@ -468,8 +469,8 @@ int vr_render_backward(vr_tree_t tree, int n_frames, const VrCamera* cams, const
  * and backward calls it still uploads the file-order table, as their n_frames == 0 does).
  * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed or any device call: NULL tree / rays / origins /
  * dirs / opt / out, every output NULL, unknown fp_mode, n outside the range, a bad step_size.
- * Not offered for lists: a per-ray t_max / mesh depth, AOV planes, tile sharding, any reordering of the rays,
- * gradients with respect to the rays. */
+ * Not offered for lists: a per-ray t_max / mesh depth, AOV planes, tile sharding, any reordering of the rays
+ * by these calls (vr_order_rays is a call of its own), gradients with respect to the rays. */
 typedef struct VrRays {       /* device, [n][3] float32 each, tightly packed, world space */
     const float* origins;
     const float* dirs;        /* any finite non-zero length */
@@ -548,6 +549,51 @@ typedef struct VrFit {       /* device pointers on the tree's device */
 } VrFit;
 int vr_fit_rays(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt,
                 int fp_mode, const VrFit* fit, void* stream);
+/* ---- Ordering a ray list for coherence ---- */
+/* The march calls above take the rays in the caller's order, 64 consecutive rays to a wave, and rays drawn at
+ * random are the order the march likes least.  vr_order_rays computes, on the device, the order that puts rays
+ * with neighbouring segments through the volume next to each other, and gathers the list (and one payload array,
+ * e.g. VrFit.target) into that order; the caller then hands the gathered arrays to any ray-list call and takes
+ * per-ray outputs back through `order`.  It rests on "results do not depend on the order of the rays".
+ *   Setup: ray i is set up exactly as the ray-list launches set it up in FP model fp_mode (direction normalised,
+ *     maybe_world2ndc, offset + scale * cen, _get_delta_scale, the ray/box test against opt->render_bbox; step_size
+ *     is not read and rot_dirs does not matter), which leaves cen, dir, tmin, tmax in tree coordinates.
+ *   Key: a ray that does not enter the volume (the ray/box test fails, or tree N <= 0) has key 0xFFFFFFFF.
+ *     Otherwise e[c] = madd(tmin, dir[c], cen[c]) and x[c] = madd(tmax, dir[c], cen[c]) -- the march's position
+ *     formula, madd that of the FP model -- and each of the six coordinates v = (e0, e1, e2, x0, x1, x2)[c] is
+ *     quantised to `bits` bits: q = (uint32_t)min(max(v * 2^bits, 0.f), 2^bits - 1), truncating, NaN -> 0.  Bit
+ *     6 * b + c of the key is bit b of coordinate c: a 6-D Morton code in 6 * bits bits, the higher bits zero.
+ *   Result: order = the STABLE sort of 0 .. n-1 by key (ties in increasing index): unique and bit-reproducible.
+ *     keys[j] = key(order[j]); rays that miss come last.  The gathered arrays are bit copies: origins_out[j] =
+ *     origins[order[j]], dirs_out[j] = dirs[order[j]] (as given, NOT normalised), payload_out[j] =
+ *     payload[order[j]].  Nothing but the named outputs and the workspace is written; the inputs are not modified.
+ *   bits == 0 selects the library's default, 2 (12 key bits): the value with the cheapest order + march on the
+ *     bench tree.  Whether ordering pays at all depends on the tree and on the batch -- it did NOT for 65,536 rays
+ *     drawn from 64 frames (README.md "Ordering ray batches" has what was measured).
+ * Contract: that of the point queries -- enqueue only, on the tree's device, the tree is only read, no launch
+ * slot, no library-owned scratch, no mutex: safe beside any launch.  The caller owns `workspace`: at least
+ * vr_order_rays_workspace(n) bytes, 256-byte aligned, usable again once the call's work on `stream` is done.
+ * 0 <= n < 2^30; n == 0 is VR_OK and enqueues nothing.
+ * VR_ERR_INVALID_ARGUMENT, before the tree handle is followed or any device call: NULL tree / rays / origins /
+ * dirs / opt / out / order, unknown fp_mode, n outside the range, bits outside 0..5, payload without payload_out
+ * or the reverse, payload_dim outside 1..8 with a payload (or non-zero without), a NULL, misaligned or too small
+ * workspace when n > 0, an output equal to its input (origins_out == origins, dirs_out == dirs, payload_out ==
+ * payload). */
+typedef struct VrRayOrder {         /* device pointers on the tree's device */
+    int          bits;              /* 1..5 key bits per coordinate; 0 = the library's default (2) */
+    uint32_t*    order;             /* [n], required: order[j] = index of the ray at sorted position j */
+    uint32_t*    keys;              /* [n] sorted keys; NULL = not wanted */
+    float*       origins_out;       /* [n][3]: origins[order[j]]; NULL = not wanted */
+    float*       dirs_out;          /* [n][3]: dirs[order[j]] (as given, NOT normalised); NULL = not wanted */
+    const float* payload;           /* [n][payload_dim], e.g. VrFit.target; NULL = none */
+    float*       payload_out;       /* [n][payload_dim]: payload[order[j]]; required iff payload */
+    int          payload_dim;       /* 1..8 when payload is given, else 0 */
+} VrRayOrder;
+/* Bytes of workspace a vr_order_rays of n rays needs: 0 for n <= 0, non-decreasing in n; makes no device call.
+ * (A byte count as int64_t, like vr_compact_bytes.) */
+int64_t vr_order_rays_workspace(int64_t n);
+int vr_order_rays(vr_tree_t tree, int64_t n, const VrRays* rays, const VrRenderOptions* opt, int fp_mode,
+                  const VrRayOrder* out, void* workspace, size_t workspace_bytes, void* stream);
 /* Sizes n_slots (1..8) launch slots so that no later ray call of <= n rays on them allocates or blocks (the
  * colour record plus the scratch of a call without rgba: 80-232 bytes per ray).  Optional; synchronous. */
 int vr_reserve_rays(vr_tree_t tree, int64_t n, int n_slots);

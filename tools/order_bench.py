@@ -1,0 +1,211 @@
+#!/usr/bin/env python3
+"""What ordering a ray batch with vr_order_rays costs and brings back, on the tree of a bench.py config and the
+batch of tools/fit_bench.py -- ``--rays`` rays drawn at random (seeded) from the pixels of ``--frames`` bench poses
+-- in one process.  For vr_fit_rays (with touched and sq_err) and for vr_render_rays (accum), per batch:
+
+    (a)  a, a_b     the call on the batch as drawn: the path without the feature, and the yardstick; twice, the A/A
+                    pair that gives the spread
+    (b)  order_k    vr_order_rays alone, bits = k in 2..5 (order, origins, dirs and -- fit -- the targets as payload)
+    (c)  ordered_k  (b) followed by the call on the ordered batch
+    (d)  d          the call on the same rays in the frame launch's block order (8 x 8 pixel blocks in 4 x 4
+                    super-blocks, the frame the minor index of a block: vr_dev_rays.h locate()), which the tool can
+                    form because it knows each ray's frame and pixel: the floor an ordering can approach
+
+Nothing is promised.  The default ``bits`` is the k with the smallest (c) of vr_fit_rays; ordering pays -- and the
+tool exits 0 -- only if that (c) is below both (a) by more than the A/A spread (the largest of |a - a_b| and the
+window spreads of a, a_b and that c).  The (a) / (d) ratio is the size of the prize for this batch size.
+
+Each figure is the mean over one warmed window of >= ``--window`` seconds of back-to-back iterations between two HIP
+events; ``--reps`` windows per case, interleaved; the spread of a case is max - min over its windows.  One JSON line
+per case, appended to ``--out``; ``--markdown`` prints the tables.
+
+    python -m volrend_amd.build
+    python tools/order_bench.py --out profiles/order_rays.jsonl --markdown
+
+Measurement tooling, not the product.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+BITS = (2, 3, 4, 5)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="C1")
+    ap.add_argument("--rays", type=int, default=65536)
+    ap.add_argument("--frames", type=int, default=64, help="bench poses the rays are drawn from")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--window", type=float, default=0.5, help="seconds of iterations per timed window")
+    ap.add_argument("--out", default="")
+    ap.add_argument("--markdown", action="store_true")
+    args = ap.parse_args()
+
+    import numpy as np
+    import torch
+    from volrend_amd import _abi, api, synth
+    import bench as B
+
+    cfg = synth.CONFIGS[args.config]
+    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
+    if W % 32 or H % 32:
+        raise SystemExit("order (d) is written for frames of whole 4 x 4 super-blocks")
+    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
+    stream = torch.cuda.current_stream()
+    sp = api._stream_ptr(stream)
+    fp_mode = _abi.FP_STRICT
+    f32 = torch.float32
+    n, nf = args.rays, args.frames
+    L = _abi.lib()
+
+    # the batch of tools/fit_bench.py: pixels drawn from the frames of the bench poses
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    transforms = np.stack([synth.c2w_to_transform(p) for p in synth.make_poses(200)][:nf]).astype(np.float32)
+    m = torch.from_numpy(transforms).cuda()
+    pick = torch.randint(0, nf * H * W, (n,), device="cuda", generator=gen)
+    fr, px = pick // (H * W), pick % (H * W)
+    ix, iy = px % W, px // W
+    x = (ix.to(f32) - 0.5 * W) / torch.tensor(focal, dtype=f32, device="cuda")
+    y = -(iy.to(f32) - 0.5 * H) / torch.tensor(focal, dtype=f32, device="cuda")
+    dirs = torch.stack([(m[fr, i] * x + m[fr, 3 + i] * y) - m[fr, 6 + i] for i in range(3)], dim=-1).contiguous()
+    origins = m[fr, 9:12].contiguous()
+    target = torch.rand((n, 3), dtype=f32, device="cuda", generator=gen)
+    # (d): the rank of each ray in the frame launch's order -- super-block row, column, block row, column, frame, pixel
+    block_key = ((((((iy // 32) * (W // 32) + ix // 32) * 4 + (iy // 8) % 4) * 4 + (ix // 8) % 4) * nf + fr) * 8
+                 + iy % 8) * 8 + ix % 8
+    block_order = torch.argsort(block_key, stable=True)
+    options = api.RenderOptions()
+    opt = options.to_c()
+    grad_scale = 2.0 / (3 * n)
+
+    tree = api.N3Tree.from_synth(stree)
+    tree.reserve_rays(n, 1)
+    grad = torch.zeros((stree.capacity, stree.N, stree.N, stree.N, stree.data_dim), dtype=f32, device="cuda")
+    touched = torch.zeros(api.touched_words(tree), dtype=torch.int32, device="cuda")
+    sq_err = torch.zeros(n, dtype=f32, device="cuda")
+    accum = torch.zeros((n, 4), dtype=f32, device="cuda")
+    order = torch.zeros(n, dtype=torch.int32, device="cuda")
+    o_out, d_out, t_out = torch.zeros_like(origins), torch.zeros_like(dirs), torch.zeros_like(target)
+    ws_bytes = int(L.vr_order_rays_workspace(n))
+    ws = torch.zeros(ws_bytes, dtype=torch.uint8, device="cuda")
+
+    def rays_c(o, d):
+        r = _abi.VrRays()
+        r.origins, r.dirs = o.data_ptr(), d.data_ptr()
+        return r
+
+    lists = {"drawn": (origins, dirs, target), "ordered": (o_out, d_out, t_out),
+             "block": tuple(a[block_order].contiguous() for a in (origins, dirs, target))}
+    rays = {k: rays_c(v[0], v[1]) for k, v in lists.items()}
+    out = _abi.VrRayOut()
+    out.accum = accum.data_ptr()
+
+    def fit(which):
+        f = _abi.VrFit()
+        f.target, f.grad_scale, f.grad_data = lists[which][2].data_ptr(), grad_scale, grad.data_ptr()
+        f.touched, f.sq_err = touched.data_ptr(), sq_err.data_ptr()
+        _abi.check(L.vr_fit_rays(tree.handle, n, C.byref(rays[which]), C.byref(opt), fp_mode, C.byref(f), sp))
+
+    def render(which):
+        _abi.check(L.vr_render_rays(tree.handle, n, C.byref(rays[which]), C.byref(opt), fp_mode, C.byref(out), sp))
+
+    def order_rays(bits, payload):
+        ro = _abi.VrRayOrder()
+        ro.bits, ro.order, ro.origins_out, ro.dirs_out = bits, order.data_ptr(), o_out.data_ptr(), d_out.data_ptr()
+        if payload:
+            ro.payload, ro.payload_out, ro.payload_dim = target.data_ptr(), t_out.data_ptr(), 3
+        _abi.check(L.vr_order_rays(tree.handle, n, C.byref(rays["drawn"]), C.byref(opt), fp_mode, C.byref(ro),
+                                   ws.data_ptr(), ws_bytes, sp))
+
+    # the ordered call computes what the call on the batch as drawn computes: sq_err bit for bit through `order`
+    fit("drawn")
+    torch.cuda.synchronize()
+    ref_sq, ref_marks = sq_err.clone(), touched.clone()
+    touched.zero_()
+    order_rays(0, True)
+    fit("ordered")
+    torch.cuda.synchronize()
+    back = torch.empty_like(sq_err)
+    back[order.long()] = sq_err
+    same_sq_err = bool(torch.equal(back.view(torch.int32), ref_sq.view(torch.int32)))
+    same_marks = bool(torch.equal(touched, ref_marks))
+    del ref_sq, ref_marks, back
+
+    calls = {}
+    for op, fn, payload in (("fit", fit, True), ("render", render, False)):
+        calls[f"{op}_a"] = lambda fn=fn: fn("drawn")
+        calls[f"{op}_a_b"] = lambda fn=fn: fn("drawn")
+        for k in BITS:
+            calls[f"{op}_order_{k}"] = lambda k=k, payload=payload: order_rays(k, payload)
+            calls[f"{op}_ordered_{k}"] = lambda fn=fn, k=k, payload=payload: (order_rays(k, payload), fn("ordered"))
+        calls[f"{op}_d"] = lambda fn=fn: fn("block")
+    keys = tuple(calls)
+
+    def window(key, n_calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(n_calls):
+            calls[key]()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / n_calls   # ms per batch
+
+    for key in keys:   # clocks up, code objects loaded, the tables made
+        window(key, 4)
+    n_calls = {key: max(4, int(args.window * 1e3 / window(key, 4)) + 1) for key in keys}
+    ms = {key: [] for key in keys}
+    for _ in range(args.reps):
+        for key in keys:
+            ms[key].append(window(key, n_calls[key]))
+    status = tree.status()
+    tree.free_device()
+
+    mean = {k: sum(v) / len(v) for k, v in ms.items()}
+    spread = {k: max(v) - min(v) for k, v in ms.items()}
+    common = {"config": args.config, "rays": n, "frames": nf, "capacity": stree.capacity, "data_dim": stree.data_dim,
+              "reps": args.reps, "workspace_bytes": ws_bytes, "sq_err_bits_equal": same_sq_err,
+              "marks_equal": same_marks, "status": status}
+    lines, verdict = [], {}
+    for op in ("fit", "render"):
+        best = min(BITS, key=lambda k: mean[f"{op}_ordered_{k}"])
+        c = f"{op}_ordered_{best}"
+        aa = max(abs(mean[f"{op}_a"] - mean[f"{op}_a_b"]), spread[f"{op}_a"], spread[f"{op}_a_b"], spread[c])
+        pays = mean[c] < min(mean[f"{op}_a"], mean[f"{op}_a_b"]) - aa
+        verdict[op] = dict(best_bits=best, pays=bool(pays), aa_spread_ms=round(aa, 4),
+                           a_over_d=round(mean[f"{op}_a"] / mean[f"{op}_d"], 4),
+                           c_over_a=round(mean[c] / mean[f"{op}_a"], 4))
+        for key in keys:
+            if key.startswith(op + "_"):
+                lines.append(json.dumps(dict(common, op=op, case=key[len(op) + 1:], ms=round(mean[key], 4),
+                                             spread_ms=round(spread[key], 4), calls_per_window=n_calls[key],
+                                             **verdict[op])))
+    print("\n".join(lines), flush=True)
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+    if args.markdown:
+        for op, name in (("fit", "`vr_fit_rays`"), ("render", "`vr_render_rays`")):
+            v = verdict[op]
+            print(f"| {name}, {args.config}, {n} rays of {nf} frames | ms | spread |")
+            print("|---|---|---|")
+            rows = [("a", "(a) as drawn (A)"), ("a_b", "(a) as drawn (B)")]
+            rows += [(f"order_{k}", f"(b) `vr_order_rays`, bits = {k}") for k in BITS]
+            rows += [(f"ordered_{k}", f"(c) (b) + the call on the ordered batch, bits = {k}") for k in BITS]
+            rows += [("d", "(d) frame launch's block order")]
+            for key, text in rows:
+                print(f"| {text} | {mean[op + '_' + key]:.4f} | {spread[op + '_' + key]:.4f} |")
+            print(f"\nbest bits {v['best_bits']}, (c) / (a) = {v['c_over_a']}, (a) / (d) = {v['a_over_d']}, A/A spread "
+                  f"{v['aa_spread_ms']} ms: ordering {'pays' if v['pays'] else 'does not pay'}\n")
+    ok = same_sq_err and same_marks and status == 0
+    return 0 if ok and verdict["fit"]["pays"] else 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -28,6 +28,7 @@ DATA_F16, DATA_F32 = 0, 1  # vr_tree_update_data / vr_tree_read_data dtype
 STEP_SGD, STEP_ADAM = 0, 1  # VrStep.kind
 STEP_KINDS = {"sgd": STEP_SGD, "adam": STEP_ADAM}
 MAX_BASIS = 25
+ORDER_MAX_BITS, ORDER_MAX_PAYLOAD = 5, 8  # VrRayOrder.bits / .payload_dim
 
 
 class VrTreeDesc(C.Structure):
@@ -94,6 +95,12 @@ class VrFit(C.Structure):
                 ("touched", C.c_void_p), ("sq_err", C.c_void_p), ("accum", C.c_void_p)]
 
 
+class VrRayOrder(C.Structure):
+    _fields_ = [("bits", C.c_int), ("order", C.c_void_p), ("keys", C.c_void_p), ("origins_out", C.c_void_p),
+                ("dirs_out", C.c_void_p), ("payload", C.c_void_p), ("payload_out", C.c_void_p),
+                ("payload_dim", C.c_int)]
+
+
 class VrStep(C.Structure):
     _fields_ = [("master", C.c_void_p), ("grad", C.c_void_p), ("touched", C.c_void_p), ("m", C.c_void_p),
                 ("v", C.c_void_p), ("kind", C.c_int32), ("lr", C.c_float), ("lr_sigma", C.c_float),
@@ -156,6 +163,9 @@ PROTOTYPES = {
                                           C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vr_fit_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
                               C.POINTER(VrFit), C.c_void_p]),
+    "vr_order_rays_workspace": (C.c_int64, [C.c_int64]),
+    "vr_order_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
+                                C.POINTER(VrRayOrder), C.c_void_p, C.c_size_t, C.c_void_p]),
     "vr_reserve_rays": (C.c_int, [C.c_void_p, C.c_int64, C.c_int]),
     "vr_reserve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int]),
     "vr_reserve_tiles": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

@@ -216,7 +216,8 @@ def render_rays(tree, origins, dirs, options: RenderOptions, *, want=("accum",),
     does follows, so a list built from a camera gives that frame's bits.  ``want``: "accum" (float32 [n, 4]:
     trace_ray's output before the composite) and / or "rgba" (uint8 [n, 4]: composited over
     background_brightness); a buffer passed as ``rgba`` / ``accum`` is wanted too and is written.  Returns a
-    dict of torch tensors.  64 consecutive rays share a wave; the library does not reorder them.
+    dict of torch tensors.  64 consecutive rays share a wave; the library does not reorder them (``order_rays``
+    computes an order to apply).
     render_depth and enable_probe are refused."""
     handle = tree.handle
     want = parse_want(want, ("rgba", "accum"))
@@ -302,6 +303,86 @@ def fit_rays(tree, origins, dirs, options: RenderOptions, target, *, grad_scale,
     _abi.check(_abi.lib().vr_fit_rays(handle, c.n, C.byref(rays), C.byref(o), int(fp_mode), C.byref(fit),
                                       _stream_ptr(stream)))
     return res
+
+
+# ---- the order that makes a ray list coherent (vr_order_rays) ----
+_ORDER_OUT = {"order": "order", "keys": "keys", "origins": "origins_out", "dirs": "dirs_out", "payload": "payload_out"}
+
+
+def order_rays(tree, origins, dirs, options: RenderOptions, *, bits: int = 0, payload=None,
+               want=("order", "origins", "dirs"), out=None, workspace=None, fp_mode: int = _abi.FP_STRICT, stream=None,
+               n=None, payload_dim=None) -> dict:
+    """The order in which the rays of a list are coherent, and the list gathered into it -- vr_order_rays, enqueued
+    on ``stream``; no launch slot, the tree is only read.
+
+    ``origins`` / ``dirs``: as ``render_rays`` takes them.  Each ray gets a key from where it enters and leaves the
+    volume in tree coordinates (set up as the ray-list launches set it up in ``fp_mode``; of ``options`` only
+    render_bbox is read): a 6-D Morton code of ``bits`` bits per coordinate (1..5; 0 = the library's default), all
+    ones for a ray that misses.  "order" (int32 [n]) is the stable sort of 0..n-1 by that key -- unique and
+    bit-reproducible; ``order[j]`` is the index of the ray at sorted position j.  ``want``: any of "order" (always
+    produced), "keys" (int32 [n]: the sorted keys' bits), "origins" / "dirs" (float32 [n, 3]: the rows in sorted
+    order, bit copies) -- and "payload" (float32 [n, k]) is produced whenever ``payload`` (float32 [n, k], k in 1..8,
+    e.g. the targets of ``fit_rays``; a raw pointer needs ``payload_dim``) is given.  ``out``: a dict of buffers to
+    write instead of allocating, by the same names; none may be its own input.  ``workspace``: a uint8 buffer of at
+    least vr_order_rays_workspace(n) bytes, 256-byte aligned; allocated when not given.
+
+    Returns a dict of torch tensors by those names, plus "workspace" (keep the dict until the work on ``stream`` is
+    done).  Feed "origins" / "dirs" / "payload" to any ray-list call; a per-ray output ``y`` of that call goes back
+    to the caller's order as ``x = torch.empty_like(y); x[order.long()] = y``."""
+    handle = tree.handle
+    want = parse_want(want, tuple(_ORDER_OUT))
+    out = dict(out or {})
+    if any(k not in _ORDER_OUT for k in out):
+        raise ValueError(f"out names {sorted(_ORDER_OUT)}, not {sorted(out)!r}")
+    if not isinstance(bits, int) or isinstance(bits, bool) or not 0 <= bits <= _abi.ORDER_MAX_BITS:
+        raise ValueError(f"bits must be an integer in 0..{_abi.ORDER_MAX_BITS}, not {bits!r}")
+    k = payload_dim
+    if payload is None:
+        if "payload" in want or out.get("payload") is not None or payload_dim is not None:
+            raise ValueError("a gathered payload needs payload")
+    else:
+        shape = getattr(payload, "shape", None) or getattr(payload, "__cuda_array_interface__", {}).get("shape")
+        if k is None and shape is not None and len(shape) == 2:
+            k = int(shape[1])
+        if k is None:
+            raise ValueError("payload must have shape [n, k]; a raw pointer needs payload_dim")
+        if not isinstance(k, int) or not 1 <= k <= _abi.ORDER_MAX_PAYLOAD:
+            raise ValueError(f"payload must have 1..{_abi.ORDER_MAX_PAYLOAD} columns, not {k!r}")
+    bufs = _ray_bufs(origins, dirs)
+    if payload is not None:
+        bufs.append(Buf("payload", payload, (F32,), ("n", k)))
+    if workspace is not None:
+        bufs.append(Buf("workspace", workspace, (U8,)))
+    specs = {"order": (I32, ("n",)), "keys": (I32, ("n",)), "origins_out": (F32, ("n", 3)),
+             "dirs_out": (F32, ("n", 3)), "payload_out": (F32, ("n", k or 0))}
+    names = [_ORDER_OUT[w] for w in want] + ["order"] + (["payload_out"] if payload is not None else [])
+    c, res = outputs(tree, bufs, specs, {_ORDER_OUT[w]: v for w, v in out.items()}, names, zeros=False, n=n)
+    for a, b in (("origins", "origins_out"), ("dirs", "dirs_out"), ("payload", "payload_out")):
+        if c.n and c.ptr.get(b) is not None and c.ptr.get(b) == c.ptr.get(a):
+            raise ValueError(f"out[{a!r}] is its own input: the gather is not in place")
+    result = {w: res[name] for w, name in _ORDER_OUT.items() if name in res}
+    if c.n == 0:  # (empty tensors have no address to pass, and nothing would be enqueued)
+        return result
+    L = _abi.lib()
+    need = int(L.vr_order_rays_workspace(c.n))
+    if workspace is None:
+        import torch
+        workspace = torch.empty(need, dtype=torch.uint8, device=torch.device("cuda", c.device_index()))
+        c.ptr["workspace"], have = int(workspace.data_ptr()), need
+    else:   # (a raw pointer is taken to be large enough; the library checks what it is told)
+        have = need if isinstance(workspace, int) else int(np.prod(_shape_of(workspace), dtype=np.int64))
+    ro, rays, o = _abi.VrRayOrder(), _rays_c(c), options.to_c()
+    ro.bits, ro.payload, ro.payload_dim = bits, c.ptr.get("payload"), k or 0
+    for name in ("order", "keys", "origins_out", "dirs_out", "payload_out"):
+        setattr(ro, name, c.ptr.get(name))
+    _abi.check(L.vr_order_rays(handle, c.n, C.byref(rays), C.byref(o), int(fp_mode), C.byref(ro), c.ptr["workspace"],
+                               have, _stream_ptr(stream)))
+    result["workspace"] = workspace
+    return result
+
+
+def _shape_of(x) -> tuple:
+    return tuple(x.shape) if hasattr(x, "shape") else tuple(x.__cuda_array_interface__["shape"])
 
 
 # ---- the values of the device copy, in place (vr_tree_update_data / vr_tree_read_data) ----

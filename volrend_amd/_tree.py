@@ -298,7 +298,7 @@ class N3Tree:
     accumulate_weights, render_backward = _ops.accumulate_weights, _ops.render_backward
     render_rays, accumulate_weights_rays = _ops.render_rays, _ops.accumulate_weights_rays
     render_backward_rays, touched_words = _ops.render_backward_rays, _ops.touched_words
-    fit_rays = _ops.fit_rays
+    fit_rays, order_rays = _ops.fit_rays, _ops.order_rays
     step, update_data, read_data = _ops.tree_step, _ops.update_data, _ops.read_data
 
     def info(self) -> dict:

@@ -195,6 +195,18 @@ void fit_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options
     internal::vr_check(vr_fit_rays(tree.device, rays.n, &r, &o, fp_mode, &f, stream), "vr_fit_rays");
 }
 
+size_t order_rays_workspace(int64_t n) { return (size_t)vr_order_rays_workspace(n); }
+
+void order_rays(const N3Tree& tree, const Rays& rays, const RenderOptions& options, const RayOrder& out,
+                void* workspace, size_t workspace_bytes, void* stream, int fp_mode) {
+    const VrRenderOptions o = to_c(options);
+    const VrRays r{rays.origins, rays.dirs};
+    const VrRayOrder ro{out.bits, out.order, out.keys, out.origins_out, out.dirs_out, out.payload, out.payload_out,
+                        out.payload_dim};
+    internal::vr_check(vr_order_rays(tree.device, rays.n, &r, &o, fp_mode, &ro, workspace, workspace_bytes, stream),
+                       "vr_order_rays");
+}
+
 void reserve_rays(const N3Tree& tree, int64_t n, int n_slots) {
     internal::vr_check(vr_reserve_rays(tree.device, n, n_slots), "vr_reserve_rays");
 }
