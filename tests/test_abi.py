@@ -207,3 +207,15 @@ def test_product_sources_carry_no_experiment_hooks_and_the_patch_applies(tmp_pat
     assert "TL3_ROUND(go)" in patched("vr_render.hip") and "vr_experiment_hooks.h" in patched("vr_render.hip")
     with pytest.raises(ValueError):
         build.build(extra_flags=["-DVR_ABLATE=4"])          # never into libvolrend_hip.so
+
+
+def test_no_kernel_source_is_compiled_through_an_include():
+    """Kernel flavours are template arguments.  No file of csrc/ includes a .hip file -- itself or another --
+    to compile its text a second time under other macros, and none names a pass guard of that kind."""
+    csrc = os.path.join(ROOT, "volrend_amd", "csrc")
+    files = sorted(f for f in os.listdir(csrc) if os.path.isfile(os.path.join(csrc, f)))
+    assert "vr_render.hip" in files
+    for f in files:
+        text = open(os.path.join(csrc, f), errors="replace").read()
+        assert not re.search(r"^\s*#\s*include\s*[\"<][^\">]*\.hip[\">]", text, flags=re.M), f
+        assert "VR_KERNEL_PASS" not in text, f

@@ -1,4 +1,4 @@
-"""-m gpu: the ray hand-out of render_kernel / render_aov_kernel is scheduling only.
+"""-m gpu: the ray hand-out of render_kernel, colour and AOV flavours, is scheduling only.
 
 A wave takes its rays from the queue of its XCD in guided chunks of at most `chunk_max` rays (tuning key;
 0 = the host's rule for the kind of launch, vr_launch_plan.cpp plan_launch) and refills its idle lanes from the

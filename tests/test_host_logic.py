@@ -178,8 +178,9 @@ def test_measure_traffic_parses_rocprofv3_csvs(tmp_path):
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import measure_traffic as mt
-    k = "void vr::(anonymous namespace)::render_kernel<0, 16, 0>(vr::KParams)"
-    other = "void vr::(anonymous namespace)::render_kernel<0, 16, 1>(vr::KParams)"
+    k = "void vr::(anonymous namespace)::render_kernel<0, 16, 0, false>(vr::KParams)"
+    other = "void vr::(anonymous namespace)::render_kernel<0, 16, 1, false>(vr::KParams)"
+    aov = "void vr::(anonymous namespace)::render_kernel<0, 16, 0, false, vr::AovParams>(vr::KParams, vr::AovParams const)"
     d = tmp_path / "box" / "123"
     d.mkdir(parents=True)
     rows = ["Dispatch_Id,Kernel_Name,Counter_Name,Counter_Value"]
@@ -188,11 +189,12 @@ def test_measure_traffic_parses_rocprofv3_csvs(tmp_path):
             rows.append(f'{disp},"{k}",TCC_EA0_RDREQ_128B_sum,{base}')
             rows.append(f'{disp},"{k}",TCC_EA0_RDREQ_sum,{base}')
     rows.append(f'11,"{other}",TCC_EA0_RDREQ_128B_sum,99999')   # instrumented flavour: ignored
+    rows.append(f'12,"{aov}",TCC_EA0_RDREQ_128B_sum,77777')     # AOV flavour of the same template: ignored
     (d / "rdsize_counter_collection.csv").write_text("\n".join(rows) + "\n")
     (d / "rdsize_kernel_trace.csv").write_text(
         "Kernel_Name,Start_Timestamp,End_Timestamp\n"
-        f'"{k}",1000,3000\n"{k}",5000,9000\n"{other}",0,100000\n')
-    vals, dur = mt.collect(str(tmp_path), "rdsize", "render_kernel<0, 16, 0>")
+        f'"{k}",1000,3000\n"{k}",5000,9000\n"{other}",0,100000\n"{aov}",0,70000\n')
+    vals, dur = mt.collect(str(tmp_path), "rdsize", "render_kernel<0, 16, 0")    # main()'s selection
     assert sorted(vals["TCC_EA0_RDREQ_128B_sum"]) == [800.0, 2400.0]
     assert sorted(dur) == [2000.0, 4000.0]
     # the group table never offers the counters that abort rocprofv3 on this pool

@@ -97,7 +97,8 @@ def main():
         for basis in [int(b) for b in args.basis.split(",")]:
             for blk in (0, 1):  # brick entry order (x-major / line blocks): a template parameter of the FAST flavours
                 fma = 1 if fp == "fma" else 0
-                sym = f"_ZN2vr12_GLOBAL__N_113render_kernelILi{fma}ELi{basis}ELi0ELb{blk}EEEvNS_7KParamsE"
+                # the colour flavour: an empty pack, JE (the AOV sibling differs inside J...E only)
+                sym = f"_ZN2vr12_GLOBAL__N_113render_kernelILi{fma}ELi{basis}ELi0ELb{blk}EJEEEvNS_7KParamsEDpKT3_"
                 start = next(i for i, l in enumerate(text) if l.startswith(sym + ":"))
                 end = next(i for i in range(start, len(text)) if "s_endpgm" in text[i])
                 body = text[start:end + 1]

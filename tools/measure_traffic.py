@@ -87,11 +87,16 @@ def run_group(name: str, counters: str, bench_args: list[str], out_dir: str, tim
     return p.stdout.decode()
 
 
+def is_kernel(name: str, kernel_substr: str) -> bool:
+    """A colour flavour: the AOV flavours of the same template (..., vr::AovParams>) share its prefix."""
+    return kernel_substr in name and "AovParams" not in name
+
+
 def collect(out_dir: str, group: str, kernel_substr: str):
     per = defaultdict(float)
     for f in glob.glob(os.path.join(out_dir, "**", f"{group}_counter_collection.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if kernel_substr in row["Kernel_Name"]:
+            if is_kernel(row["Kernel_Name"], kernel_substr):
                 per[(row["Dispatch_Id"], row["Counter_Name"])] += float(row["Counter_Value"])
     vals = defaultdict(list)
     for (_, cname), v in per.items():
@@ -99,7 +104,7 @@ def collect(out_dir: str, group: str, kernel_substr: str):
     dur = []
     for f in glob.glob(os.path.join(out_dir, "**", f"{group}_kernel_trace.csv"), recursive=True):
         for row in csv.DictReader(open(f)):
-            if kernel_substr in row["Kernel_Name"]:
+            if is_kernel(row["Kernel_Name"], kernel_substr):
                 dur.append(float(row["End_Timestamp"]) - float(row["Start_Timestamp"]))
     return vals, dur
 
@@ -120,7 +125,7 @@ def main():
     cfg = synth.CONFIGS[args.config]
     basis = cfg["basis_dim"] if cfg["fmt"] != "RGBA" else -1
     fpi = 1 if args.fp == "fma" else 0
-    kernel = f"render_kernel<{fpi}, {basis}, 0"  # (+ the brick-order flavour: ", false>" / ", true>")
+    kernel = f"render_kernel<{fpi}, {basis}, 0"  # (+ the brick-order flavour: ", false>" / ", true>"; never ", vr::AovParams>")
     bench_args = ["--config", args.config, "--fp", args.fp, "--batch", str(args.batch), "--steps",
                   str(2 * args.batch), "--warmup", str(args.batch), "--no-cpu-baseline", "--no-parity",
                   "--live-traffic", "0", "--repeats", "0", "--preroll", "0",

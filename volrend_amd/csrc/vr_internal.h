@@ -242,7 +242,7 @@ struct AovTable {
 //   * Per launch, block_mask_kernel (vr_render.hip) splats every listed cell into every frame: one bit per 8x8
 //     block of the FRAME (block (bx, by) = bit by * nbx + bx of the frame's words, whatever the tile shard), in the
 //     launch slot behind the ray records, zeroed by prepare_launch_kernel.
-//   * The FAST flavours of raygen_kernel / raygen_aov_kernel read their block's bit (CullParams, their last
+//   * The FAST flavours of raygen_kernel, colour and AOV, read their block's bit (CullParams, their last
 //     argument; mask = NULL: no cull) and count blocks seen / culled.
 // KParams does not change: the march kernels keep their kernel descriptors (tools/kernel_digest.py).
 // ---------------------------------------------------------------------------

@@ -4,7 +4,7 @@
 namespace {
 
 // The knobs that are "auto" (0) by default, resolved for one launch.  `colour`: a colour or AOV launch
-// (render_kernel / render_aov_kernel); the leaf-weight and backward launches keep the values they were
+// (render_kernel, with or without AovParams); the leaf-weight and backward launches keep the values they were
 // measured with (guided chunks of up to 4096 rays, row-major block order).
 //   * chunk_max: the cap of a wave's guided chunk (grab_chunk, vr_dev_rays.h).  256 for colour launches of
 //     any shape: four block-poses.  With 4096 one wave marched an 8x8 pixel block through all the poses of a

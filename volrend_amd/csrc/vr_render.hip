@@ -15,13 +15,10 @@
 // This file: the kernels of a launch (ray generation, the persistent render kernel, the frame-table
 // write, the probe) and their launchers.  Layout, colour, point query and rays: vr_dev_*.h; the
 // upload-time build kernels: vr_tree_kernels.hip.
-// The text of the two big kernels (render_kernel, raygen_kernel) is compiled TWICE, under two pairs of
-// names: once as it stands, and once more -- as render_aov_kernel / raygen_aov_kernel, with a second
-// kernel argument -- through the #include of this very file behind raygen_kernel.  That inner pass
-// (VR_KERNEL_PASS_AOV) skips everything but the two kernels.  Two kernels over one text rather than
-// over one inlined function: the colour kernels keep the very machine code they had before the AOV
-// pair existed (tools/kernel_digest.py).
-#ifndef VR_KERNEL_PASS_AOV
+// The two big kernels (render_kernel, raygen_kernel) are templates with a trailing pack PLANES: empty for
+// the colour flavours, <AovParams> for the flavours of vr_render_aov, which take the planes as one more
+// kernel argument.  Per flavour the machine code is what two separate kernels would have
+// (tools/kernel_digest.py, profiles/render_pair_template_digest.txt).
 #include "vr_device_math.h"
 #include "vr_internal.h"
 #include "vr_dev_layout.h"
@@ -205,19 +202,16 @@ __device__ __forceinline__ void store_colour_ray(const KParams& p, uint32_t slot
     }
 }
 
-// names and arguments of the kernel pair of this pass (the colour pair; the AOV pair: behind raygen_kernel)
-#define VR_RENDER_KERNEL render_kernel
-#define VR_RAYGEN_KERNEL raygen_kernel
-#define VR_KERNEL_ARGS const KParams p
-#define VR_RAYGEN_ARGS const KParams p, const CullParams cull
-#define VR_KERNEL_AOV false
-#define VR_KERNEL_AOV_LOCAL const AovParams aov{};  // (never read)
-#endif  // VR_KERNEL_PASS_AOV
+// The planes of a kernel's pack PLANES: the AOV flavours' argument, or an empty table that the colour flavours
+// never read.
+__device__ __forceinline__ AovParams aov_arg() { return AovParams{}; }
+__device__ __forceinline__ const AovParams& aov_arg(const AovParams& a) { return a; }
 
-template <int FMA, int BASIS, int MODE, bool BLK = false>
-__global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void VR_RENDER_KERNEL(VR_KERNEL_ARGS) {
-    constexpr bool AOV = VR_KERNEL_AOV;
-    VR_KERNEL_AOV_LOCAL
+template <int FMA, int BASIS, int MODE, bool BLK, typename... PLANES>
+__global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>()))
+void render_kernel(const KParams p, const PLANES... planes) {
+    constexpr bool AOV = sizeof...(PLANES) != 0;
+    const AovParams aov = aov_arg(planes...);
     using P = Policy<FMA>;
     constexpr bool N2 = MODE != MODE_GENERIC;
     constexpr bool LOBES = MODE != MODE_FAST;
@@ -697,10 +691,12 @@ __global__ __launch_bounds__(kWave, (min_waves_per_eu<BASIS, MODE>())) void VR_R
 // render kernel of launch k + 1 cannot start before it has ended.  Smaller workgroups mean more
 // atomics: at 4 waves a 64-frame launch is 4 % slower, at 1 wave 35 % (profiles/r06_raygen_waves.jsonl).
 
-template <int FMA, bool FULL, int GW>
-__global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_RAYGEN_ARGS) {
-    constexpr bool AOV = VR_KERNEL_AOV;
-    VR_KERNEL_AOV_LOCAL
+// (PLANES sits between two arguments and is never deduced: every use names it.)
+template <int FMA, bool FULL, int GW, typename... PLANES>
+__global__ __launch_bounds__(kWave* GW)
+void raygen_kernel(const KParams p, const PLANES... planes, const CullParams cull) {
+    constexpr bool AOV = sizeof...(PLANES) != 0;
+    const AovParams aov = aov_arg(planes...);
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = threadIdx.x >> 6;
     const uint32_t id =
@@ -800,37 +796,12 @@ __global__ __launch_bounds__(kWave* GW) void VR_RAYGEN_KERNEL(VR_RAYGEN_ARGS) {
     }
 }
 
-#ifndef VR_KERNEL_PASS_AOV
-#undef VR_RENDER_KERNEL
-#undef VR_RAYGEN_KERNEL
-#undef VR_KERNEL_ARGS
-#undef VR_RAYGEN_ARGS
-#undef VR_KERNEL_AOV
-#undef VR_KERNEL_AOV_LOCAL
-// the AOV pair (vr_render_aov): the same text once more
-#define VR_KERNEL_PASS_AOV
-#define VR_RENDER_KERNEL render_aov_kernel
-#define VR_RAYGEN_KERNEL raygen_aov_kernel
-#define VR_KERNEL_ARGS const KParams p, const AovParams aov
-#define VR_RAYGEN_ARGS const KParams p, const AovParams aov, const CullParams cull
-#define VR_KERNEL_AOV true
-#define VR_KERNEL_AOV_LOCAL
-#include "vr_render.hip"
-#undef VR_KERNEL_PASS_AOV
-#undef VR_RENDER_KERNEL
-#undef VR_RAYGEN_KERNEL
-#undef VR_KERNEL_ARGS
-#undef VR_RAYGEN_ARGS
-#undef VR_KERNEL_AOV
-#undef VR_KERNEL_AOV_LOCAL
-
 // ---------------------------------------------------------------------------
 // raygen_rays_kernel: raygen_kernel for a ray list (vr_render_rays; vr_internal.h RayList): one lane per ray,
 // 64 consecutive rays per wave in the caller's order.  The ray comes from list_ray() instead of locate() +
 // setup_ray; its "pixel" is element `id` of the pseudo-frame's arrays.  A ray that misses the volume is
 // composited and stored here, the others are compacted into the queues as raygen_kernel's records -- lanes
-// behind the list's end neither reserve nor store.  (Compiled in the first pass of this file only: a list
-// has no AOV planes.)
+// behind the list's end neither reserve nor store.  (A list has no AOV planes.)
 // ---------------------------------------------------------------------------
 template <int FMA, bool FULL, int GW>
 __global__ __launch_bounds__(kWave* GW) void raygen_rays_kernel(const KParams p, const RayList rl) {
@@ -1055,24 +1026,21 @@ __global__ void probe_kernel(const KParams p, float probe0, float probe1, float 
 
 // grid = the persistent waves (persistent_grid, vr_internal.h): as many as the chip holds of this flavour
 // (or the tuning override)
-template <int FMA, int MODE, bool AOV>
-hipError_t launch_basis(const KParams& p, const AovParams& a, int64_t total_blocks, int n_cus, int waves_override,
-                        hipStream_t s) {
+// planes: none (colour), or the AovParams of an AOV launch -- the extra kernel argument of its flavours
+template <int FMA, int MODE, typename... PLANES>
+hipError_t launch_basis(const KParams& p, int64_t total_blocks, int n_cus, int waves_override, hipStream_t s,
+                        const PLANES&... planes) {
     const dim3 block(kWave);
+    constexpr bool kAov = sizeof...(PLANES) != 0;
 #define VR_LAUNCH(B)                                                                         \
     do {                                                                                     \
         const dim3 grid(persistent_grid(total_blocks, n_cus,                                 \
-                                        waves_override > 0 ? waves_override : waves_per_cu<B, MODE, AOV>())); \
+                                        waves_override > 0 ? waves_override : waves_per_cu<B, MODE, kAov>())); \
         constexpr bool kBlk = MODE == MODE_FAST;                                             \
-        if constexpr (AOV) {                                                                 \
-            if (kBlk && p.brick_blocked)                                                     \
-                hipLaunchKernelGGL((render_aov_kernel<FMA, B, MODE, kBlk>), grid, block, 0, s, p, a); \
-            else                                                                             \
-                hipLaunchKernelGGL((render_aov_kernel<FMA, B, MODE, false>), grid, block, 0, s, p, a); \
-        } else if (kBlk && p.brick_blocked)                                                  \
-            hipLaunchKernelGGL((render_kernel<FMA, B, MODE, kBlk>), grid, block, 0, s, p);   \
+        if (kBlk && p.brick_blocked)                                                         \
+            hipLaunchKernelGGL((render_kernel<FMA, B, MODE, kBlk, PLANES...>), grid, block, 0, s, p, planes...); \
         else                                                                                 \
-            hipLaunchKernelGGL((render_kernel<FMA, B, MODE, false>), grid, block, 0, s, p);  \
+            hipLaunchKernelGGL((render_kernel<FMA, B, MODE, false, PLANES...>), grid, block, 0, s, p, planes...); \
     } while (0)
     switch (basis_flavour(p.format, p.basis_dim)) {
         case BASIS_RGBA: VR_LAUNCH(BASIS_RGBA); break;
@@ -1086,30 +1054,30 @@ hipError_t launch_basis(const KParams& p, const AovParams& a, int64_t total_bloc
     return hipGetLastError();
 }
 
-template <int FMA, bool AOV>
-hipError_t launch_fp(const KParams& p, const AovParams& a, int64_t total_blocks, int n_cus, int waves_override,
-                     hipStream_t s) {
-    if (!uses_lookup(p)) return launch_basis<FMA, MODE_GENERIC, AOV>(p, a, total_blocks, n_cus, waves_override, s);
-    if (needs_full(p)) return launch_basis<FMA, MODE_FULL, AOV>(p, a, total_blocks, n_cus, waves_override, s);
-    return launch_basis<FMA, MODE_FAST, AOV>(p, a, total_blocks, n_cus, waves_override, s);
+template <int FMA, typename... PLANES>
+hipError_t launch_fp(const KParams& p, int64_t total_blocks, int n_cus, int waves_override, hipStream_t s,
+                     const PLANES&... planes) {
+    if (!uses_lookup(p)) return launch_basis<FMA, MODE_GENERIC>(p, total_blocks, n_cus, waves_override, s, planes...);
+    if (needs_full(p)) return launch_basis<FMA, MODE_FULL>(p, total_blocks, n_cus, waves_override, s, planes...);
+    return launch_basis<FMA, MODE_FAST>(p, total_blocks, n_cus, waves_override, s, planes...);
 }
 
 // Ray generation + the persistent march of one launch (the probe overlay is launch_render's own).
 // rays: a ray list takes the place of the frames' pixels (never with AOV planes).
-template <bool AOV>
-hipError_t launch_march(const KParams& p, const AovParams& a, const CullParams& cull, int fp_mode, int n_cus,
-                        int waves_override, int gen_waves, hipStream_t stream, const RayList* rays = nullptr) {
+template <typename... PLANES>
+hipError_t launch_march(const KParams& p, const CullParams& cull, int fp_mode, int n_cus, int waves_override,
+                        int gen_waves, hipStream_t stream, const RayList* rays, const PLANES&... planes) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
     {   // ray generation: gen_waves wave blocks (8x8 pixels each) per workgroup
         const bool full = needs_full(p);
 #define VR_GEN(FMA_, FULL_, GW_)                                                                    \
     do {                                                                                            \
         const dim3 grid_((unsigned)((total_blocks + GW_ - 1) / GW_)), block_(kWave * GW_);          \
-        if constexpr (AOV) hipLaunchKernelGGL((raygen_aov_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, a, cull); \
-        else if (rays) {                                                                            \
-            if constexpr (GW_ >= 4) hipLaunchKernelGGL((raygen_rays_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, *rays); \
+        if (rays) {                                                                                 \
+            if constexpr (sizeof...(PLANES) == 0 && GW_ >= 4)                                       \
+                hipLaunchKernelGGL((raygen_rays_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, *rays); \
         }                                                                                           \
-        else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, cull); \
+        else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_, PLANES...>), grid_, block_, 0, stream, p, planes..., cull); \
     } while (0)
 #define VR_GEN_GW(FMA_, FULL_)                                                                      \
     do {                                                                                            \
@@ -1126,8 +1094,8 @@ hipError_t launch_march(const KParams& p, const AovParams& a, const CullParams& 
 #undef VR_GEN
     }
     // the persistent march (its grid: persistent_grid, vr_internal.h)
-    return fp_mode == VR_FP_FMA ? launch_fp<1, AOV>(p, a, total_blocks, n_cus, waves_override, stream)
-                                : launch_fp<0, AOV>(p, a, total_blocks, n_cus, waves_override, stream);
+    return fp_mode == VR_FP_FMA ? launch_fp<1>(p, total_blocks, n_cus, waves_override, stream, planes...)
+                                : launch_fp<0>(p, total_blocks, n_cus, waves_override, stream, planes...);
 }
 
 }  // namespace
@@ -1150,8 +1118,7 @@ hipError_t launch_block_mask(const KParams& p, const MaskParams& m, hipStream_t 
 hipError_t launch_render(const KParams& p, const CullParams& cull, int fp_mode, int n_cus, int waves_override,
                          int gen_waves, hipStream_t stream, const RayList* rays) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    const hipError_t e =
-        launch_march<false>(p, AovParams{}, cull, fp_mode, n_cus, waves_override, gen_waves, stream, rays);
+    const hipError_t e = launch_march(p, cull, fp_mode, n_cus, waves_override, gen_waves, stream, rays);
     if (e != hipSuccess || !p.enable_probe || p.probe_disp_size <= 0) return e;
     const int side = p.probe_disp_size + 5;
     const dim3 pgrid((unsigned)((side * side + 255) / 256), (unsigned)p.n_frames);
@@ -1171,7 +1138,7 @@ hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream
 hipError_t launch_render_aov(const KParams& p, const AovParams& a, const CullParams& cull, int fp_mode, int n_cus,
                              int waves_override, int gen_waves, hipStream_t stream) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    return launch_march<true>(p, a, cull, fp_mode, n_cus, waves_override, gen_waves, stream);
+    return launch_march(p, cull, fp_mode, n_cus, waves_override, gen_waves, stream, /* rays */ nullptr, a);
 }
 
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
@@ -1182,4 +1149,3 @@ hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
 }
 
 }  // namespace vr
-#endif  // VR_KERNEL_PASS_AOV
