@@ -519,6 +519,41 @@ def test_frames_before_and_after_ray_launches(torch_cuda):
         assert np.array_equal(got[0], want_rgba) and np.array_equal(bits(got[1]), bits(want_accum))
 
 
+def test_bench_tools_pixel_rays_are_the_frames_rays(torch_cuda):
+    """tools/benchlib.py pixel_rays, from which the ray benchmarks draw their batches: the rays of all pixels of
+    three 64 x 48 frames (W != H, so that a swap of % W and // W, or of W and H, shows) render the bytes of the
+    batch launch of the same poses, strict model, offscreen; and a seeded pick of 1,000 (frame, pixel) pairs gives
+    the rows of the full list at those indices."""
+    import os
+    import sys
+    torch = torch_cuda
+    from volrend_amd import api
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import benchlib as bl
+    w, h = 64, 48
+    trs = [common.camera_for(pose_idx=i, size=w)[0] for i in range(3)]
+    focal = common.camera_for(size=w)[3]
+    m = dev(torch, np.stack(trs).astype(np.float32))
+    every = torch.arange(3 * h * w, device="cuda")
+    o, d = bl.pixel_rays(torch, m, w, h, focal, every // (h * w), every % (h * w))
+    assert o.dtype == d.dtype == torch.float32 and tuple(o.shape) == tuple(d.shape) == (3 * h * w, 3)
+    assert o.is_contiguous() and d.is_contiguous()
+    t = api.N3Tree.from_synth(common.small_scene())
+    try:
+        imgs = torch.zeros((3, h, w, 4), dtype=torch.uint8, device="cuda")
+        api.launch_renderer_batch(t, api.Camera(w, h, focal, focal), trs, api.RenderOptions(), list(imgs), None, True)
+        got = t.render_rays(o, d, api.RenderOptions(), want=("rgba",))["rgba"]
+        torch.cuda.synchronize()
+        assert t.status() == 0
+    finally:
+        t.free_device()
+    assert bool((imgs[..., :3] != imgs[0, 0, 0, :3]).any()), "the scene must be in view"
+    assert torch.equal(got, imgs.view(-1, 4))
+    pick = torch.randint(0, 3 * h * w, (1000,), device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))
+    po, pd = bl.pixel_rays(torch, m, w, h, focal, pick // (h * w), pick % (h * w))
+    assert torch.equal(po, o[pick]) and torch.equal(pd, d[pick])
+
+
 # ---- 7. optim ------------------------------------------------------------------------------------------------
 def test_optim_forward_and_gradient(torch_cuda):
     torch = torch_cuda

@@ -10,9 +10,8 @@ tree of a bench.py config at its frame size, ``--frames`` poses per launch:
     (c) new:    vr_render_aov with both planes (one march)
     (d) new:    the colour launch (the same machine code as (a): tools/kernel_digest.py)
 
-Each figure is the mean over one warmed window of >= ``--window`` seconds of back-to-back launches
-between two HIP events; ``--reps`` windows per variant, interleaved a, b, c, d, a, b, ...; the spread
-of a variant is max - min over its windows.  Conditions (exit status 1 when one fails):
+Figures, windows and spreads are those of tools/benchlib.py: ``--window`` seconds of launches per window,
+``--reps`` windows per variant, interleaved a, b, c, d, a, b, ...  Conditions (exit status 1 when one fails):
     (c) < (b) by more than the largest spread;   |(d) - (a)| <= the largest spread.
 (c) / (a) gets no threshold: it is recorded.  One JSON line per run, appended to ``--out``.
 
@@ -25,25 +24,12 @@ Measurement tooling, not the product.
 from __future__ import annotations
 
 import argparse
-import ctypes as C
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
 
-
-def load(_abi, path, without=()):
-    """A library build with the prototypes of _abi (minus the symbols an older build lacks)."""
-    L = C.CDLL(path)
-    for name, (res, args) in _abi.PROTOTYPES.items():
-        if name in without:
-            continue
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    assert L.vr_abi_version() == _abi.ABI_VERSION
-    return L
+ROOT = bl.ROOT
 
 
 def main():
@@ -58,15 +44,11 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    cfg = synth.CONFIGS[args.config]
-    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
-    transforms = [synth.c2w_to_transform(p) for p in synth.make_poses(200)]
+    sc = bl.scene(args.config)
+    W, H, focal, stree, transforms, stream = sc.W, sc.H, sc.focal, sc.stree, sc.transforms, sc.stream
     nf = args.frames
-    stream = torch.cuda.current_stream()
     fp_mode = _abi.FP_FMA if args.fp == "fma" else _abi.FP_STRICT
     cam = api.Camera(W, H, focal, focal)
     imgs = torch.zeros((nf, H, W, 4), dtype=torch.uint8, device="cuda")
@@ -74,8 +56,8 @@ def main():
     dp = torch.zeros((nf, H, W), dtype=torch.float32, device="cuda")
     tp = torch.zeros((nf, H, W), dtype=torch.float32, device="cuda")
 
-    libs = {"parent": load(_abi, args.parent_lib, without=("vr_render_aov",)),
-            "new": load(_abi, os.path.join(ROOT, "volrend_amd", "libvolrend_hip.so"))}
+    libs = {"parent": bl.load_build(_abi, args.parent_lib, without=("vr_render_aov",)),
+            "new": bl.load_build(_abi, os.path.join(ROOT, "volrend_amd", "libvolrend_hip.so"))}
     n_sets = 4   # launches of a window rotate over this many pose sets (as bench.py's timed region moves on)
 
     def poses(k):
@@ -100,26 +82,16 @@ def main():
             batches["c"] = (L, [[x] for x in aov])
             batches["d"] = (L, [[c] for c in colour])
 
-    def window(key, n_launches):
+    def window(key, n_launches):   # -> ms per launch of nf poses
         L, sets = batches[key]
         _abi._lib = L
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for k in range(n_launches):
+
+        def launch(k):
             for pb in sets[k % n_sets]:
                 pb.launch(stream)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_launches   # ms per launch of nf poses
+        return bl.timed(torch, stream, n_launches, launch)
 
-    # clocks and caches up (an MI355X out of idle needs tens of ms of work), then the launches per window
-    for key in "abcd":
-        window(key, 8)
-    n_launch = {key: max(4, int(args.window * 1e3 / window(key, 8)) + 1) for key in "abcd"}
-    ms = {key: [] for key in "abcd"}
-    for _ in range(args.reps):
-        for key in "abcd":
-            ms[key].append(window(key, n_launch[key]))
+    ms, n_launch, mean, spread = bl.measure("abcd", window, warm=8, floor=4, window_s=args.window, reps=args.reps)
     status = {}
     for name, L in libs.items():
         _abi._lib = L
@@ -127,8 +99,6 @@ def main():
         trees[name].free_device()
     _abi._lib = None
 
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
     worst = max(spread.values())
     ok_one_march = mean["c"] < mean["b"] - worst
     ok_colour = abs(mean["d"] - mean["a"]) <= worst
@@ -142,10 +112,7 @@ def main():
            "aov_below_two_launches_by_more_than_spread": ok_one_march,
            "colour_launch_unchanged_within_spread": ok_colour, "status": status,
            "what": "a parent colour, b parent colour + render_depth launch, c vr_render_aov (both planes), d new colour"}
-    print(json.dumps(rec), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+    bl.emit(rec, args.out)
     return 0 if ok_one_march and ok_colour and not any(status.values()) else 1
 
 

@@ -13,9 +13,7 @@ arithmetic and the traffic of a step do not depend on the rate.  No ratio is pro
 the same run with the A/A spread (the largest of |a - b| and the window spreads of a, b and the fused case) as the
 margin.  Exit status 1 when (ii) is not faster than (i) beyond the spread, with or without the step.
 
-Each figure is the mean over one warmed window of >= ``--window`` seconds of back-to-back iterations between two HIP
-events; ``--reps`` windows per case, interleaved; the spread of a case is max - min over its windows.  One JSON line
-per case, appended to ``--out``; ``--markdown`` prints the table.
+Figures, windows and spreads are those of tools/benchlib.py (``--window``, ``--reps``).  One JSON line per case, appended to ``--out``; ``--markdown`` prints the table.
 
     python -m volrend_amd.build
     python tools/fit_bench.py --out profiles/fit_rays.jsonl --markdown
@@ -26,12 +24,9 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
 
 
 def main():
@@ -47,29 +42,20 @@ def main():
 
     import numpy as np
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    cfg = synth.CONFIGS[args.config]
-    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
-    stream = torch.cuda.current_stream()
-    sp = api._stream_ptr(stream)
+    sc = bl.scene(args.config)
+    W, H, focal, stree, stream, sp = sc.W, sc.H, sc.focal, sc.stree, sc.stream, sc.sp
     fp_mode = _abi.FP_STRICT
     f32 = torch.float32
     n = args.rays
     L = _abi.lib()
 
-    # the batch: pixels drawn from the frames of the bench poses, directions as the strict kernel forms them
+    # the batch: pixels drawn from the frames of the bench poses
     gen = torch.Generator(device="cuda").manual_seed(1)
-    transforms = np.stack([synth.c2w_to_transform(p) for p in synth.make_poses(200)][:args.frames]).astype(np.float32)
-    m = torch.from_numpy(transforms).cuda()
+    m = torch.from_numpy(np.stack(sc.transforms[:args.frames]).astype(np.float32)).cuda()
     pick = torch.randint(0, args.frames * H * W, (n,), device="cuda", generator=gen)
-    fr, px = pick // (H * W), pick % (H * W)
-    x = ((px % W).to(f32) - 0.5 * W) / torch.tensor(focal, dtype=f32, device="cuda")
-    y = -((px // W).to(f32) - 0.5 * H) / torch.tensor(focal, dtype=f32, device="cuda")
-    dirs = torch.stack([(m[fr, i] * x + m[fr, 3 + i] * y) - m[fr, 6 + i] for i in range(3)], dim=-1).contiguous()
-    origins = m[fr, 9:12].contiguous()
+    origins, dirs = bl.pixel_rays(torch, m, W, H, focal, pick // (H * W), pick % (H * W))
     rays = _abi.VrRays()
     rays.origins, rays.dirs = origins.data_ptr(), dirs.data_ptr()
     options = api.RenderOptions()
@@ -137,30 +123,15 @@ def main():
     }
     keys = tuple(calls)
 
-    def window(key, n_calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(n_calls):
-            calls[key]()
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_calls   # ms per iteration
+    def window(key, n_calls):   # -> ms per iteration
+        return bl.timed(torch, stream, n_calls, lambda _: calls[key]())
 
-    for key in keys:   # clocks up, code objects loaded, the tables made
-        window(key, 4)
-    n_calls = {key: max(4, int(args.window * 1e3 / window(key, 4)) + 1) for key in keys}
-    ms = {key: [] for key in keys}
-    for _ in range(args.reps):
-        for key in keys:
-            ms[key].append(window(key, n_calls[key]))
+    ms, n_calls, mean, spread = bl.measure(keys, window, warm=4, floor=4, window_s=args.window, reps=args.reps)
     step()
     torch.cuda.synchronize()
     unchanged = bool(torch.equal(before, tree.read_data()))   # (as values: every rate was 0)
     status = tree.status()
     tree.free_device()
-
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
 
     def margin(a, b, c):
         return max(abs(mean[a] - mean[b]), spread[a], spread[b], spread[c])
@@ -179,11 +150,8 @@ def main():
             rec.update(saved_ms=round(mean["unfused" + s] - mean[key], 4),
                        fused_over_unfused=round(mean[key] / mean["unfused" + s], 4),
                        faster_beyond_spread=bool(faster[s]))
-        lines.append(json.dumps(rec))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+        lines.append(rec)
+    bl.emit(lines, args.out)
     if args.markdown:
         print(f"| {args.config}, {n} rays, {n_marked} of {n_slots} slots marked | ms | spread |")
         print("|---|---|---|")

@@ -8,9 +8,8 @@ One process, the tree of a bench.py config at its frame size, ``--frames`` poses
     (a)  vr_render_batch colour launches
     (b)  vr_render_backward into a buffer that has already seen the whole pass (steady state)
 
-Each figure is the mean over one warmed window of >= ``--window`` seconds of back-to-back launches between
-two HIP events; ``--reps`` windows per variant, interleaved; the spread of a variant is max - min over its
-windows.  Also reported: the bytes (b) adds per second -- hit samples per frame (the hits buffer of one
+Figures, windows and spreads are those of tools/benchlib.py (``--window``, ``--reps``), a window a whole number
+of passes.  Also reported: the bytes (b) adds per second -- hit samples per frame (the hits buffer of one
 vr_accumulate_weights pass) x the floats a hit adds x 4 -- next to the 1.3 TB/s at which the chip's memory
 side executes float atomic adds of the right shape.  A record, not a gate: one JSON line per run, appended to
 ``--out``; ``--markdown`` prints the rows of the DESIGN.md table.
@@ -23,12 +22,9 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
 
 KEYS = ("a", "b")
 ATOMIC_RATE_TBS = 1.3
@@ -46,16 +42,11 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    cfg = synth.CONFIGS[args.config]
-    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
-    transforms = [synth.c2w_to_transform(p) for p in synth.make_poses(200)]
+    sc = bl.scene(args.config)
+    W, H, focal, stree, transforms, stream, sp = sc.W, sc.H, sc.focal, sc.stree, sc.transforms, sc.stream, sc.sp
     nf, n_sets = args.frames, 3
-    stream = torch.cuda.current_stream()
-    sp = api._stream_ptr(stream)
     fp_mode = _abi.FP_FMA if args.fp == "fma" else _abi.FP_STRICT
     cam = api.Camera(W, H, focal, focal)
     L = _abi.lib()
@@ -87,14 +78,8 @@ def main():
         _abi.check(L.vr_render_backward(tree.handle, nf, cams[k % n_sets], C.byref(opt), fp_mode, g.data_ptr(),
                                         grad.data_ptr(), sp))
 
-    def window(key, n_launches):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for k in range(n_launches):
-            launch(key, k)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_launches   # ms per launch of nf poses
+    def window(key, n_launches):   # -> ms per launch of nf poses
+        return bl.timed(torch, stream, n_launches, lambda k: launch(key, k))
 
     # hit samples per frame: the count buffer of one leaf-weight pass over the same poses
     hits = torch.zeros((stree.capacity, stree.N, stree.N, stree.N), dtype=torch.int32, device="cuda")
@@ -106,21 +91,13 @@ def main():
     basis = stree.basis_dim
     run = 3 * basis + 1 if basis in (4, 9, 16, 25) else 4     # floats a hit adds (vr_dev_backward.h GradTraits::kRun)
 
-    # clocks and caches up, the buffer sees the whole pass, launches per window
-    for key in KEYS:
-        window(key, 2 * n_sets)
-    n_launch = {key: max(n_sets, (int(args.window * 1e3 / window(key, 2 * n_sets)) // n_sets + 1) * n_sets)
-                for key in KEYS}
-    ms = {key: [] for key in KEYS}
-    for _ in range(args.reps):
-        for key in KEYS:
-            ms[key].append(window(key, n_launch[key]))
+    # the warm windows are two passes: the buffer has seen the whole pass before a timed window
+    ms, n_launch, mean, spread = bl.measure(KEYS, window, warm=2 * n_sets, floor=n_sets, multiple=n_sets,
+                                            window_s=args.window, reps=args.reps)
     status = tree.status()
     finite = bool(torch.isfinite(grad).all())
     tree.free_device()
 
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
     per_frame = {k: mean[k] / nf for k in KEYS}
     added_tbs = hits_per_frame * run * 4 / (per_frame["b"] * 1e-3) / 1e12
     rec = {"config": args.config, "fp": args.fp, "frames_per_launch": nf, "width": W, "height": H,
@@ -132,10 +109,7 @@ def main():
            "added_TB_per_s": round(added_tbs, 4), "atomic_rate_TB_per_s": ATOMIC_RATE_TBS,
            "backward_over_colour": round(mean["b"] / mean["a"], 3), "finite": finite, "status": status,
            "what": "a colour, b vr_render_backward into a buffer that has seen the pass"}
-    print(json.dumps(rec), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+    bl.emit(rec, args.out)
     if args.markdown:
         names = {"a": "colour launch (`vr_render_batch`)", "b": "`vr_render_backward`, steady state"}
         print(f"| {args.config} variant | ms / frame | spread | / colour |")

@@ -15,9 +15,7 @@ Nothing is promised.  The default ``bits`` is the k with the smallest (c) of vr_
 tool exits 0 -- only if that (c) is below both (a) by more than the A/A spread (the largest of |a - a_b| and the
 window spreads of a, a_b and that c).  The (a) / (d) ratio is the size of the prize for this batch size.
 
-Each figure is the mean over one warmed window of >= ``--window`` seconds of back-to-back iterations between two HIP
-events; ``--reps`` windows per case, interleaved; the spread of a case is max - min over its windows.  One JSON line
-per case, appended to ``--out``; ``--markdown`` prints the tables.
+Figures, windows and spreads are those of tools/benchlib.py (``--window``, ``--reps``).  One JSON line per case, appended to ``--out``; ``--markdown`` prints the tables.
 
     python -m volrend_amd.build
     python tools/order_bench.py --out profiles/order_rays.jsonl --markdown
@@ -28,12 +26,10 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
+
 BITS = (2, 3, 4, 5)
 
 
@@ -50,16 +46,12 @@ def main():
 
     import numpy as np
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    cfg = synth.CONFIGS[args.config]
-    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
+    sc = bl.scene(args.config)
+    W, H, focal, stree, stream, sp = sc.W, sc.H, sc.focal, sc.stree, sc.stream, sc.sp
     if W % 32 or H % 32:
         raise SystemExit("order (d) is written for frames of whole 4 x 4 super-blocks")
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
-    stream = torch.cuda.current_stream()
-    sp = api._stream_ptr(stream)
     fp_mode = _abi.FP_STRICT
     f32 = torch.float32
     n, nf = args.rays, args.frames
@@ -67,15 +59,11 @@ def main():
 
     # the batch of tools/fit_bench.py: pixels drawn from the frames of the bench poses
     gen = torch.Generator(device="cuda").manual_seed(1)
-    transforms = np.stack([synth.c2w_to_transform(p) for p in synth.make_poses(200)][:nf]).astype(np.float32)
-    m = torch.from_numpy(transforms).cuda()
+    m = torch.from_numpy(np.stack(sc.transforms[:nf]).astype(np.float32)).cuda()
     pick = torch.randint(0, nf * H * W, (n,), device="cuda", generator=gen)
     fr, px = pick // (H * W), pick % (H * W)
     ix, iy = px % W, px // W
-    x = (ix.to(f32) - 0.5 * W) / torch.tensor(focal, dtype=f32, device="cuda")
-    y = -(iy.to(f32) - 0.5 * H) / torch.tensor(focal, dtype=f32, device="cuda")
-    dirs = torch.stack([(m[fr, i] * x + m[fr, 3 + i] * y) - m[fr, 6 + i] for i in range(3)], dim=-1).contiguous()
-    origins = m[fr, 9:12].contiguous()
+    origins, dirs = bl.pixel_rays(torch, m, W, H, focal, fr, px)
     target = torch.rand((n, 3), dtype=f32, device="cuda", generator=gen)
     # (d): the rank of each ray in the frame launch's order -- super-block row, column, block row, column, frame, pixel
     block_key = ((((((iy // 32) * (W // 32) + ix // 32) * 4 + (iy // 8) % 4) * 4 + (ix // 8) % 4) * nf + fr) * 8
@@ -148,27 +136,13 @@ def main():
         calls[f"{op}_d"] = lambda fn=fn: fn("block")
     keys = tuple(calls)
 
-    def window(key, n_calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(n_calls):
-            calls[key]()
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_calls   # ms per batch
+    def window(key, n_calls):   # -> ms per batch
+        return bl.timed(torch, stream, n_calls, lambda _: calls[key]())
 
-    for key in keys:   # clocks up, code objects loaded, the tables made
-        window(key, 4)
-    n_calls = {key: max(4, int(args.window * 1e3 / window(key, 4)) + 1) for key in keys}
-    ms = {key: [] for key in keys}
-    for _ in range(args.reps):
-        for key in keys:
-            ms[key].append(window(key, n_calls[key]))
+    ms, n_calls, mean, spread = bl.measure(keys, window, warm=4, floor=4, window_s=args.window, reps=args.reps)
     status = tree.status()
     tree.free_device()
 
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
     common = {"config": args.config, "rays": n, "frames": nf, "capacity": stree.capacity, "data_dim": stree.data_dim,
               "reps": args.reps, "workspace_bytes": ws_bytes, "sq_err_bits_equal": same_sq_err,
               "marks_equal": same_marks, "status": status}
@@ -183,13 +157,9 @@ def main():
                            c_over_a=round(mean[c] / mean[f"{op}_a"], 4))
         for key in keys:
             if key.startswith(op + "_"):
-                lines.append(json.dumps(dict(common, op=op, case=key[len(op) + 1:], ms=round(mean[key], 4),
-                                             spread_ms=round(spread[key], 4), calls_per_window=n_calls[key],
-                                             **verdict[op])))
-    print("\n".join(lines), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write("\n".join(lines) + "\n")
+                lines.append(dict(common, op=op, case=key[len(op) + 1:], ms=round(mean[key], 4),
+                                  spread_ms=round(spread[key], 4), calls_per_window=n_calls[key], **verdict[op]))
+    bl.emit(lines, args.out)
     if args.markdown:
         for op, name in (("fit", "`vr_fit_rays`"), ("render", "`vr_render_rays`")):
             v = verdict[op]

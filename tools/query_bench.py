@@ -21,15 +21,15 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 import time
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
+
+ROOT = bl.ROOT
 
 GATHER_LINES_PER_S = 53.5e9
 STREAM_BYTES_PER_S = 6.3e12
@@ -93,11 +93,10 @@ def main():
     import torch
     if not torch.cuda.is_available():
         sys.exit("query_bench needs a GPU")
-    import bench
-    from volrend_amd import _abi, api, synth
+    from volrend_amd import _abi, api
     L = _abi.lib()
 
-    tree = bench.load_or_make_tree(synth, args.config, 0, lambda: None)
+    tree = bl.scene(args.config).stree
     t = api.N3Tree.from_synth(tree)
     n = 1 << args.log2n
     rng = np.random.default_rng(7)
@@ -158,13 +157,7 @@ def main():
                 launch()
             stream.synchronize()
             reps = max(20, int(1.2 * args.seconds * 20 / (time.perf_counter() - t0)) + 1)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record(stream)
-            for _ in range(reps):
-                launch()
-            e1.record(stream)
-            stream.synchronize()
-            sec = e0.elapsed_time(e1) * 1e-3 / reps
+            sec = bl.timed(torch, stream, reps, lambda _: launch()) * 1e-3
             bytes_in = 0 if p_dev is None else 12 + (12 if "rgb" in want else 0)
             bytes_out = 4 + (4 * k if "coeffs" in want else 0) + (12 if "rgb" in want else 0)
             n_lines = distinct * record_lines if len(want) > 1 else 0
@@ -180,14 +173,11 @@ def main():
                        fraction_of_bound=round(max(t_lines, t_stream) / sec, 4),
                        device=torch.cuda.get_device_name(0))
             lines.append(row)
-            print(json.dumps(row), flush=True)
         del p_dev, outs
         torch.cuda.empty_cache()
     assert t.status() == 0
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
-    with open(args.out, "a") as f:
-        for row in lines:
-            f.write(json.dumps(row) + "\n")
+    bl.emit(lines, args.out)
 
 
 if __name__ == "__main__":

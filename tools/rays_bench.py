@@ -12,9 +12,8 @@ launch; the rays of those frames are formed on the device as screen2worlddir for
     (e)  vr_render_backward
     (f)  vr_render_backward_rays in order (c)
 
-All colour variants write RGBA8 only.  Each figure is the mean over one warmed window of >= ``--window`` seconds
-of back-to-back launches between two HIP events; ``--reps`` windows per variant, interleaved; the spread of a
-variant is max - min over its windows.
+All colour variants write RGBA8 only.  Figures, windows and spreads are those of tools/benchlib.py (``--window``,
+``--reps``).
 
 The one condition (exit status 1 when it fails): the march kernels of (c) are those of (a), byte for byte, and
 its rays arrive in the same order, so (c) may exceed (a) only by what ray generation pays for reading 24 more
@@ -30,14 +29,11 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import os
 import sys
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
 
 KEYS = ("a", "b", "c", "d", "e", "f")
 NAMES = {"a": "`vr_render_batch`", "b": "`vr_render_rays`, scanline order", "c": "`vr_render_rays`, block order",
@@ -56,33 +52,25 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    cfg = synth.CONFIGS[args.config]
-    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
+    sc = bl.scene(args.config)
+    W, H, focal, stree, stream, sp = sc.W, sc.H, sc.focal, sc.stree, sc.stream, sc.sp
     if W % 32 or H % 32:
         raise SystemExit("order (c) is written for frames of whole 4 x 4 super-blocks")
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
     nf = args.frames
-    transforms = [synth.c2w_to_transform(p) for p in synth.make_poses(200)][:nf]
-    stream = torch.cuda.current_stream()
-    sp = api._stream_ptr(stream)
+    transforms = sc.transforms[:nf]
     fp_mode = _abi.FP_STRICT
     cam = api.Camera(W, H, focal, focal)
     L = _abi.lib()
     n = nf * H * W
 
-    # the frames' rays, scanline order: (m[i] x + m[3 + i] y) + m[6 + i] z in float32, as the strict kernel forms them
+    # the frames' rays, scanline order, frame after frame
     f32 = torch.float32
-    ix = torch.arange(W, dtype=f32, device="cuda")
-    iy = torch.arange(H, dtype=f32, device="cuda")
-    x = ((ix - 0.5 * W) / torch.tensor(focal, dtype=f32, device="cuda")).expand(H, W)
-    y = (-(iy - 0.5 * H) / torch.tensor(focal, dtype=f32, device="cuda"))[:, None].expand(H, W)
     m = torch.from_numpy(np.stack(transforms).astype(np.float32)).cuda()        # [nf, 12]
-    dirs = torch.stack([(m[:, i, None, None] * x + m[:, 3 + i, None, None] * y) - m[:, 6 + i, None, None]
-                        for i in range(3)], dim=-1).reshape(n, 3).contiguous()
-    origins = m[:, None, 9:12].expand(nf, H * W, 3).reshape(n, 3).contiguous()
+    every = torch.arange(n, device="cuda")
+    origins, dirs = bl.pixel_rays(torch, m, W, H, focal, every // (H * W), every % (H * W))
+    del every
     pix = torch.arange(n, device="cuda").view(nf, H // 32, 4, 8, W // 32, 4, 8)   # f, sr, iy, ly, sc, ix, lx
     order = {"b": None, "c": pix.permute(1, 4, 2, 5, 0, 3, 6).reshape(-1),
              "d": torch.randperm(n, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1))}
@@ -122,14 +110,8 @@ def main():
             _abi.check(L.vr_render_backward_rays(tree.handle, n, C.byref(c_rays["c"]), C.byref(opt), fp_mode,
                                                  g_c.data_ptr(), grad.data_ptr(), sp))
 
-    def window(key, n_launches):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(n_launches):
-            launch(key)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_launches   # ms per launch of nf poses
+    def window(key, n_launches):   # -> ms per launch of nf poses
+        return bl.timed(torch, stream, n_launches, lambda _: launch(key))
 
     # the lists give the frames' bytes (and the clocks come up)
     launch("a")
@@ -140,18 +122,10 @@ def main():
         torch.cuda.synchronize()
         want = imgs.view(n, 4) if order[key] is None else imgs.view(n, 4)[order[key]]
         same[key] = bool(torch.equal(out, want))
-    for key in KEYS:
-        window(key, 2)
-    n_launch = {key: max(1, int(args.window * 1e3 / window(key, 2)) + 1) for key in KEYS}
-    ms = {key: [] for key in KEYS}
-    for _ in range(args.reps):
-        for key in KEYS:
-            ms[key].append(window(key, n_launch[key]))
+    ms, n_launch, mean, spread = bl.measure(KEYS, window, warm=2, floor=1, window_s=args.window, reps=args.reps)
     status = tree.status()
     tree.free_device()
 
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
     read_ms = n * 24 / (args.stream_tbs / 2 * 1e12) * 1e3            # per launch
     allowed = read_ms + max(spread.values())
     gap = mean["c"] - mean["a"]
@@ -166,10 +140,7 @@ def main():
            "lists_equal_frames": same, "status": status, "condition_met": ok,
            "what": "a frames, b list scanline, c list block order, d list shuffled, e backward frames, "
                    "f backward list block order; colour variants write RGBA8 only"}
-    print(json.dumps(rec), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+    bl.emit(rec, args.out)
     if args.markdown:
         print(f"| {args.config} variant | ms / frame | spread | / frames |")
         print("|---|---|---|---|")

@@ -27,9 +27,7 @@ this tree's.
 All rates are 0 in the timed loops, so that the tree, and with it the march, stays what it is from window to window;
 the arithmetic and the traffic of a step do not depend on the rate.
 
-Each figure is the mean over one warmed window of >= ``--window`` seconds of back-to-back calls between two HIP
-events; ``--reps`` windows per variant, interleaved; the spread of a variant is max - min over its windows.  One
-JSON line per run, appended to ``--out``; ``--markdown`` prints the tables.  Exit status 1 when a condition fails.
+Figures, windows and spreads are those of tools/benchlib.py (``--window``, ``--reps``).  One JSON line per run, appended to ``--out``; ``--markdown`` prints the tables.  Exit status 1 when a condition fails.
 
     python -m volrend_amd.build                      # this tree
     (build the parent commit's library the same way) # e.g. from `git worktree add ../parent HEAD~1`
@@ -41,26 +39,13 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
 
+ROOT = bl.ROOT
 NEW_SYMBOLS = ("vr_tree_step", "vr_render_backward_touched", "vr_render_backward_rays_touched")
-
-
-def load(_abi, path, without=()):
-    """A library build with the prototypes of _abi (minus the symbols an older build lacks)."""
-    L = C.CDLL(path)
-    for name, (res, args) in _abi.PROTOTYPES.items():
-        if name in without:
-            continue
-        fn = getattr(L, name)
-        fn.restype, fn.argtypes = res, args
-    assert L.vr_abi_version() == _abi.ABI_VERSION
-    return L
 
 
 def main():
@@ -78,36 +63,27 @@ def main():
 
     import numpy as np
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    cfg = synth.CONFIGS[args.config]
-    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
-    stream = torch.cuda.current_stream()
-    sp = api._stream_ptr(stream)
+    sc = bl.scene(args.config)
+    W, H, focal, stree, stream, sp = sc.W, sc.H, sc.focal, sc.stree, sc.stream, sc.sp
     fp_mode = _abi.FP_STRICT
     f32 = torch.float32
     n = args.rays
 
-    # the batch: pixels drawn from the frames of the bench poses, directions as the strict kernel forms them
+    # the batch: pixels drawn from the frames of the bench poses
     gen = torch.Generator(device="cuda").manual_seed(1)
-    transforms = np.stack([synth.c2w_to_transform(p) for p in synth.make_poses(200)][:args.frames]).astype(np.float32)
-    m = torch.from_numpy(transforms).cuda()
+    m = torch.from_numpy(np.stack(sc.transforms[:args.frames]).astype(np.float32)).cuda()
     pick = torch.randint(0, args.frames * H * W, (n,), device="cuda", generator=gen)
-    fr, px = pick // (H * W), pick % (H * W)
-    x = ((px % W).to(f32) - 0.5 * W) / torch.tensor(focal, dtype=f32, device="cuda")
-    y = -((px // W).to(f32) - 0.5 * H) / torch.tensor(focal, dtype=f32, device="cuda")
-    dirs = torch.stack([(m[fr, i] * x + m[fr, 3 + i] * y) - m[fr, 6 + i] for i in range(3)], dim=-1).contiguous()
-    origins = m[fr, 9:12].contiguous()
+    origins, dirs = bl.pixel_rays(torch, m, W, H, focal, pick // (H * W), pick % (H * W))
     rays = _abi.VrRays()
     rays.origins, rays.dirs = origins.data_ptr(), dirs.data_ptr()
     opt = api.RenderOptions().to_c()
 
-    libs = {"parent": load(_abi, args.parent_lib, without=NEW_SYMBOLS),
-            "new": load(_abi, os.path.join(ROOT, "volrend_amd", "libvolrend_hip.so"))}
+    libs = {"parent": bl.load_build(_abi, args.parent_lib, without=NEW_SYMBOLS),
+            "new": bl.load_build(_abi, os.path.join(ROOT, "volrend_amd", "libvolrend_hip.so"))}
     if args.alt_lib:
-        libs["alt"] = load(_abi, args.alt_lib)
+        libs["alt"] = bl.load_build(_abi, args.alt_lib)
     trees = {}
     for name, L in libs.items():
         _abi._lib = L
@@ -200,22 +176,11 @@ def main():
         calls["bwd_marked_alt"] = lambda: backward("alt", marked=True)
     keys = tuple(calls)
 
-    def window(key, n_calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(n_calls):
-            calls[key]()
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_calls   # ms per call
+    def window(key, n_calls):   # -> ms per call
+        return bl.timed(torch, stream, n_calls, lambda _: calls[key]())
 
-    for key in keys:   # clocks up, code objects loaded, the tables made, torch's optimiser state allocated
-        window(key, 4)
-    n_calls = {key: max(4, int(args.window * 1e3 / window(key, 4)) + 1) for key in keys}
-    ms = {key: [] for key in keys}
-    for _ in range(args.reps):
-        for key in keys:
-            ms[key].append(window(key, n_calls[key]))
+    # (the warm windows also make the tables and allocate torch's optimiser state)
+    ms, n_calls, mean, spread = bl.measure(keys, window, warm=4, floor=4, window_s=args.window, reps=args.reps)
     # every rate was 0: the tree holds what it held
     unchanged = bool(torch.equal(before, tree.read_data()))   # (as values: x - 0 * g may turn a -0 into +0)
     status = {}
@@ -225,8 +190,6 @@ def main():
         trees[name].free_device()
     _abi._lib = None
 
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
     step_ms = {k: mean["step_" + k] - mean["restore"] for k in ("sgd", "adam")}
     step_ms["empty"] = mean["step_empty"] - mean["zero_bits"]
     aa = max(abs(mean["bwd_new_a"] - mean["bwd_new_b"]), spread["bwd_new_a"], spread["bwd_new_b"], spread["bwd_parent"])
@@ -250,10 +213,7 @@ def main():
            "step_faster_than_dense_update": ok_step, "unmarked_within_aa_spread_of_parent": ok_unmarked,
            "tree_unchanged": unchanged, "status": status,
            "what": "a: step_* (restore + vr_tree_step), step_empty, update_f32; b: bwd_*; c: iter_*; ms per call"}
-    print(json.dumps(rec), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+    bl.emit(rec, args.out)
     if args.markdown:
         print(f"| {args.config}, {n} rays, {n_marked} of {n_slots} slots marked | ms | spread |")
         print("|---|---|---|")

@@ -14,10 +14,9 @@ One process, the tree of a bench.py config:
 
 The bytes of a pass come from the shapes (bytes_of below): the file-side array, the padded records, the node
 words (read, and written back for the update), the file-order table, and for the update's refresh every lookup
-entry read and written plus the node words it gathers.  Each GPU figure is the mean over one warmed window of
->= ``--window`` seconds of back-to-back calls between two HIP events; ``--reps`` windows per variant, interleaved;
-the spread of a variant is max - min over its windows.  A record, not a gate: one JSON line per run, appended to
-``--out``; ``--markdown`` prints a table.
+entry read and written plus the node words it gathers.  The GPU figures, their windows and spreads are those of
+tools/benchlib.py (``--window``, ``--reps``); an upload is timed behind each round.  A record, not a gate: one JSON
+line per run, appended to ``--out``; ``--markdown`` prints a table.
 
     python tools/update_bench.py --config C1 --out profiles/tree_update.jsonl --markdown
 
@@ -27,13 +26,10 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import os
 import sys
 import time
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
 
 PASSES = ("u16", "u32", "r16", "r32")
 
@@ -63,11 +59,10 @@ def main():
 
     import numpy as np
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
-    stream = torch.cuda.current_stream()
+    sc = bl.scene(args.config)
+    stree, stream = sc.stree, sc.stream
     L = _abi.lib()
     tree = api.N3Tree.from_synth(stree)
     info = tree.info()
@@ -94,14 +89,8 @@ def main():
         else:
             tree.read_data(out=outs[key[1:]], stream=stream)
 
-    def window(key, n_calls):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(n_calls):
-            call(key)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_calls   # ms per call
+    def window(key, n_calls):   # -> ms per call
+        return bl.timed(torch, stream, n_calls, lambda _: call(key))
 
     def upload_ms():
         d = _abi.VrTreeDesc()
@@ -120,17 +109,14 @@ def main():
         return ms
 
     keys = PASSES + tuple("c_" + k for k in PASSES)
-    for key in keys:   # clocks up, code objects loaded, the two tables made
-        window(key, 8)
-    upload_ms()
-    n_calls = {key: max(8, int(args.window * 1e3 / window(key, 8)) + 1) for key in keys}
-    ms = {key: [] for key in keys}
+    upload_ms()        # its code objects loaded; the warm windows make the two tables
     ups = []
-    for rep in range(args.reps):
-        for key in keys:
-            ms[key].append(window(key, n_calls[key]))
+
+    def upload_behind(rep):
         if rep < args.uploads:
             ups.append(upload_ms())
+    ms, n_calls, mean, spread = bl.measure(keys, window, warm=8, floor=8, window_s=args.window, reps=args.reps,
+                                           after_round=upload_behind)
     while len(ups) < args.uploads:
         ups.append(upload_ms())
     # every update wrote the tree's own values: nothing may have changed, and the read-backs return them
@@ -140,8 +126,6 @@ def main():
     status = tree.status()
     tree.free_device()
 
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
     rec = {"config": args.config, "capacity": stree.capacity, "data_dim": stree.data_dim,
            "device_bytes": info["device_bytes"], "lookup_bytes": lookup_bytes, "top_levels": info["top_levels"],
            "brick_levels": info["brick_levels"], "brick_blocked": info["brick_blocked"],
@@ -153,10 +137,7 @@ def main():
            "upload_over_update": {k: round(min(ups) / mean[k], 1) for k in ("u16", "u32")},
            "unchanged": unchanged, "read_back_exact": exact, "status": status,
            "what": "u update, r read-back, c_ a device copy of the same bytes, up vr_tree_upload from device arrays"}
-    print(json.dumps(rec), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+    bl.emit(rec, args.out)
     if args.markdown:
         names = {"u16": "`vr_tree_update_data`, binary16", "u32": "`vr_tree_update_data`, binary32",
                  "r16": "`vr_tree_read_data`, binary16", "r32": "`vr_tree_read_data`, binary32"}

@@ -12,9 +12,8 @@ One process, the tree of a bench.py config at its frame size, ``--frames`` poses
     (d)  max_weight + hits, steady state
     (b0) / (c0)  as (b) / (c) with the max issued unconditionally (tuning key weights_check = 0)
 
-Each figure is the mean over one warmed window of >= ``--window`` seconds of back-to-back launches between
-two HIP events; ``--reps`` windows per variant, interleaved; the spread of a variant is max - min over its
-windows.  Condition (exit status 1 when it fails): (b) < (a) by more than the largest spread.  (c), (d) and
+Figures, windows and spreads are those of tools/benchlib.py (``--window``, ``--reps``), a window a whole number
+of passes.  Condition (exit status 1 when it fails): (b) < (a) by more than the largest spread.  (c), (d) and
 the always-atomic forms get no threshold: they are recorded, with the atomics per second they imply
 (hit samples per frame come from the hits buffer of one pass).  One JSON line per run, appended to
 ``--out``; ``--markdown`` prints the rows of the DESIGN.md table.
@@ -27,12 +26,9 @@ from __future__ import annotations
 
 import argparse
 import ctypes as C
-import json
-import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import benchlib as bl
 
 KEYS = ("a", "b", "c", "d", "b0", "c0")
 
@@ -49,16 +45,11 @@ def main():
     args = ap.parse_args()
 
     import torch
-    from volrend_amd import _abi, api, synth
-    import bench as B
+    from volrend_amd import _abi, api
 
-    cfg = synth.CONFIGS[args.config]
-    W, H, focal = cfg["width"], cfg["height"], cfg["focal"]
-    stree = B.load_or_make_tree(synth, args.config, 0, lambda: None)
-    transforms = [synth.c2w_to_transform(p) for p in synth.make_poses(200)]
+    sc = bl.scene(args.config)
+    W, H, focal, stree, transforms, stream, sp = sc.W, sc.H, sc.focal, sc.stree, sc.transforms, sc.stream, sc.sp
     nf, n_sets = args.frames, 3
-    stream = torch.cuda.current_stream()
-    sp = api._stream_ptr(stream)
     fp_mode = _abi.FP_FMA if args.fp == "fma" else _abi.FP_STRICT
     cam = api.Camera(W, H, focal, focal)
     L = _abi.lib()
@@ -103,14 +94,8 @@ def main():
         _abi.check(L.vr_accumulate_weights(t.handle, nf, cams[k % n_sets], C.byref(opt), fp_mode,
                                            C.byref(out[key]), sp))
 
-    def window(key, n_launches):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for k in range(n_launches):
-            launch(key, k)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        return e0.elapsed_time(e1) / n_launches   # ms per launch of nf poses
+    def window(key, n_launches):   # -> ms per launch of nf poses
+        return bl.timed(torch, stream, n_launches, lambda k: launch(key, k))
 
     # hit samples per frame: the count buffer after exactly one pass
     tree.accumulate_weights(cam, [], api.RenderOptions(), want=("hits",))      # (the file-order tables)
@@ -121,22 +106,14 @@ def main():
     hits_per_frame = int(hits.view(-1).to(torch.int64).bitwise_and(0xFFFFFFFF).sum().item()) / (n_sets * nf)
     slots_touched = int((hits != 0).sum().item())
 
-    # clocks and caches up, steady buffers filled (b, d, b0 see the whole pass here), launches per window
-    for key in KEYS:
-        window(key, 2 * n_sets)
-    n_launch = {key: max(n_sets, (int(args.window * 1e3 / window(key, 2 * n_sets)) // n_sets + 1) * n_sets)
-                for key in KEYS}
-    ms = {key: [] for key in KEYS}
-    for _ in range(args.reps):
-        for key in KEYS:
-            ms[key].append(window(key, n_launch[key]))
+    # the warm windows are two passes: the steady buffers (b, d, b0) have seen the whole pass before a timed window
+    ms, n_launch, mean, spread = bl.measure(KEYS, window, warm=2 * n_sets, floor=n_sets, multiple=n_sets,
+                                            window_s=args.window, reps=args.reps)
     status = {"tree": tree.status(), "always": always.status()}
     same = bool(torch.equal(bufs["b"], bufs["b0"]) and torch.equal(bufs["b"], bufs["d"]))
     tree.free_device()
     always.free_device()
 
-    mean = {k: sum(v) / len(v) for k, v in ms.items()}
-    spread = {k: max(v) - min(v) for k, v in ms.items()}
     worst = max(spread.values())
     ok = mean["b"] < mean["a"] - worst
     per_frame = {k: mean[k] / nf for k in KEYS}
@@ -153,10 +130,7 @@ def main():
            "weights_over_colour": round(mean["b"] / mean["a"], 4),
            "steady_max_below_colour_by_more_than_spread": ok, "variants_agree": same, "status": status,
            "what": "a colour, b max steady, c max first pass, d max + hits steady, b0 / c0 the max always atomic"}
-    print(json.dumps(rec), flush=True)
-    if args.out:
-        with open(args.out, "a") as f:
-            f.write(json.dumps(rec) + "\n")
+    bl.emit(rec, args.out)
     if args.markdown:
         names = {"a": "colour launch (`vr_render_batch`)", "b": "`max_weight`, steady state",
                  "c": "`max_weight`, first pass (zeroed buffers)", "d": "`max_weight` + `hits`, steady state",
