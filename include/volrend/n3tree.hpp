@@ -22,6 +22,12 @@ namespace volrend {
 struct N3Tree {
     N3Tree();
     explicit N3Tree(const std::string& path);
+    // A tree uploaded from arrays that are ALREADY ON THE DEVICE, in the file's layout (vr_tree_upload with
+    // memory = 1; what refine_apply of volrend/refine.hpp writes): child_dev int32 [capacity][N^3], data_dev
+    // binary16 [capacity][N^3][data_dim], on the current device, their producers finished.  N, data_dim, format,
+    // geometry, extra_ and NDC are those of `like`.  The library copies what it needs; child_ and data_ stay
+    // empty.  Throws std::runtime_error where the upload refuses.
+    N3Tree(const N3Tree& like, const int32_t* child_dev, const uint16_t* data_dev, int capacity);
     ~N3Tree();
     N3Tree(const N3Tree&) = delete;
     N3Tree& operator=(const N3Tree&) = delete;
@@ -84,6 +90,7 @@ struct N3Tree {
    private:
     void load_npz(internal::NpzFile& npz);
     void load_device();  // load_cuda
+    void upload_arrays(const int32_t* child, const uint16_t* data, int memory);
     void free_device();  // free_cuda
 
     std::string npz_path_, poses_bounds_path_;

@@ -317,6 +317,71 @@ typedef struct VrStep {
     int32_t   step;      /* Adam: 1, 2, ... for the bias correction */
 } VrStep;
 int vr_tree_step(vr_tree_t tree, const VrStep* s, void* stream);
+/* ---- Refining a tree: subdividing selected leaves, on the device ---- */
+/* The calls above work on the topology fixed at upload.  These two restate a tree with SELECTED LEAVES SUBDIVIDED,
+ * as arrays IN THE FILE'S LAYOUT (VrTreeDesc.child / .data) in device memory, together with any companion arrays
+ * that are indexed the same way (a float32 master, Adam moments, leaf weights); vr_tree_upload with memory = 1
+ * then takes the new arrays without a host round trip.  The restatement is APPEND-ONLY in the file's node
+ * numbering: every old node and slot keeps its index and the new nodes follow behind the old ones, so everything
+ * indexed by slot stays valid and only grows at the end.  They take no tree handle and work on the calling thread's
+ * current device, as vr_decode_quantized does.  With N3 = N^3 and n_slots = capacity * N3, in plain integers:
+ *   - slot s < n_slots is REFINED iff bit s & 31 of sel[s >> 5] is set and child[s] == 0.  Bits of internal slots
+ *     and bits at or beyond n_slots are ignored.  n_new = the number of refined slots.
+ *   - the r-th refined slot in ascending s (r = 0, 1, ...) becomes node capacity + r: unique and bit-reproducible
+ *     (the order in which svox's refine appends).
+ *   - child_out[s] = capacity + r - s / N3 for a refined slot, child[s] for every other old slot, and 0 for all N3
+ *     slots of every new node (they are leaves).  src_slot[r] = s.
+ *   - per companion array: the first n_slots * dim elements of dst are the bits of src (a refined slot keeps its
+ *     values: it is an internal slot from now on); for each of the N3 slots of node capacity + r the dim elements
+ *     are those of src slot s (VR_REFINE_COPY) or zero bits (VR_REFINE_ZERO).  Elements move as bits.
+ * vr_refine_plan forms the effective mask words (sel AND leaf, tail bits cleared), their popcounts and an exclusive
+ * scan of those in the workspace, copies the total to *n_new and waits for `stream`: the call's one host-blocking
+ * step.  capacity + n_new > INT32_MAX is VR_ERR_UNSUPPORTED (child words are int32 node offsets), and so is a
+ * src_slot array for more than 2^31 slots.
+ * vr_refine_apply only enqueues on `stream`.  It takes the workspace of a plan of the same child and sel,
+ * unchanged, and that plan's n_new, and writes child_out, src_slot (when not NULL) and every dst; the old part of
+ * each array is one device-to-device copy.  Every store is bounded by capacity + n_new and a rank >= n_new writes
+ * nothing, so a caller's mistake (another n_new, a workspace that was written in between) gives wrong contents and
+ * never an out-of-range store.  n_new == 0 is legal: the outputs are copies of the inputs.
+ * The workspace is the caller's: at least vr_refine_workspace(N, capacity) bytes (-1 for arguments the calls
+ * refuse; no device call), 256-byte aligned, free again once apply's work on `stream` is done.  Of VrRefine, plan
+ * reads child, sel, workspace, workspace_bytes, capacity and N; apply reads everything.
+ * VR_ERR_INVALID_ARGUMENT, before any device call: NULL r, child, sel, workspace or n_new (plan) or child_out
+ * (apply); child_out == child; N outside what vr_tree_upload accepts (2..16); capacity < 1 or beyond INT32_MAX; n_new < 0;
+ * workspace_bytes too small or a misaligned workspace; n_arrays outside 0..VR_REFINE_MAX_ARRAYS, or arrays NULL
+ * when n_arrays > 0; per array elem_bytes not 2 or 4, dim < 1, an unknown fill, NULL src or dst, dst == src.
+ * Not offered: merging / pruning leaves and compacting the node array (that changes the numbering and needs a
+ * remap of everything indexed by slot; vr_tree_upload tolerates unreachable nodes, so a collapse without
+ * compaction is the natural next step), refining the device layout of an uploaded tree without a re-upload,
+ * quantised inputs, `extra` (it is not indexed by slot), and choosing what to refine: max_weight, hits and
+ * grad_data are already in the file's indexing, so a threshold is the caller's one line. */
+enum { VR_REFINE_COPY = 0, VR_REFINE_ZERO = 1 };
+#define VR_REFINE_MAX_ARRAYS 8
+typedef struct VrRefineArray {   /* one companion array, indexed as VrTreeDesc.data: slot * dim + e */
+    const void* src;             /* device, capacity * N^3 * dim elements */
+    void*       dst;             /* device, (capacity + n_new) * N^3 * dim elements, != src */
+    int32_t elem_bytes;          /* 2 or 4: elements move as bits, no conversion */
+    int32_t dim;                 /* elements per slot, >= 1 */
+    int32_t fill;                /* the slots of NEW nodes: VR_REFINE_COPY = the refined slot's elements,
+                                    VR_REFINE_ZERO = zero bits */
+    int32_t reserved;
+} VrRefineArray;
+typedef struct VrRefine {
+    const int32_t*  child;       /* device [capacity * N^3], the file's relative offsets, 0 = leaf */
+    const uint32_t* sel;         /* device, the `touched` bitmap format: bit s & 31 of word s >> 5 */
+    int32_t* child_out;          /* device [(capacity + n_new) * N^3], != child            (apply) */
+    int32_t* src_slot;           /* device [n_new]: the slot new node capacity + r came from; or NULL (apply) */
+    const VrRefineArray* arrays; /* HOST array of n_arrays entries                          (apply) */
+    void*   workspace;
+    int64_t workspace_bytes;
+    int64_t capacity;
+    int64_t n_new;               /* what plan returned                                      (apply) */
+    int32_t N;
+    int32_t n_arrays;            /* 0..VR_REFINE_MAX_ARRAYS */
+} VrRefine;
+int64_t vr_refine_workspace(int N, int64_t capacity);
+int vr_refine_plan(const VrRefine* r, int64_t* n_new, void* stream);
+int vr_refine_apply(const VrRefine* r, void* stream);
 
 /* ---- render ----------------------------------------------------------- */
 void vr_default_options(VrRenderOptions* opt);

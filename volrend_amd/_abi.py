@@ -29,6 +29,9 @@ STEP_SGD, STEP_ADAM = 0, 1  # VrStep.kind
 STEP_KINDS = {"sgd": STEP_SGD, "adam": STEP_ADAM}
 MAX_BASIS = 25
 ORDER_MAX_BITS, ORDER_MAX_PAYLOAD = 5, 8  # VrRayOrder.bits / .payload_dim
+REFINE_COPY, REFINE_ZERO = 0, 1  # VrRefineArray.fill
+REFINE_FILLS = {"copy": REFINE_COPY, "zero": REFINE_ZERO}
+REFINE_MAX_ARRAYS = 8
 
 
 class VrTreeDesc(C.Structure):
@@ -107,6 +110,17 @@ class VrStep(C.Structure):
                 ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("step", C.c_int32)]
 
 
+class VrRefineArray(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("elem_bytes", C.c_int32), ("dim", C.c_int32),
+                ("fill", C.c_int32), ("reserved", C.c_int32)]
+
+
+class VrRefine(C.Structure):
+    _fields_ = [("child", C.c_void_p), ("sel", C.c_void_p), ("child_out", C.c_void_p), ("src_slot", C.c_void_p),
+                ("arrays", C.POINTER(VrRefineArray)), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("capacity", C.c_int64), ("n_new", C.c_int64), ("N", C.c_int32), ("n_arrays", C.c_int32)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -155,6 +169,9 @@ PROTOTYPES = {
     "vr_render_backward_rays_touched": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),
                                                   C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vr_tree_step": (C.c_int, [C.c_void_p, C.POINTER(VrStep), C.c_void_p]),
+    "vr_refine_workspace": (C.c_int64, [C.c_int, C.c_int64]),
+    "vr_refine_plan": (C.c_int, [C.POINTER(VrRefine), C.POINTER(C.c_int64), C.c_void_p]),
+    "vr_refine_apply": (C.c_int, [C.POINTER(VrRefine), C.c_void_p]),
     "vr_render_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
                                  C.POINTER(VrRayOut), C.c_void_p]),
     "vr_accumulate_weights_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),

@@ -436,6 +436,95 @@ def read_data(tree, dtype=None, out=None, stream=None):
     return out
 
 
+# ---- a tree with selected leaves subdivided (vr_refine_plan / vr_refine_apply) ----
+def _pack_bits(flags):
+    """bool tensor [n] -> the int32 bitmap of the ``touched`` format: bit s & 31 of word s >> 5."""
+    import torch
+    n = flags.numel()
+    words = (n + 31) // 32
+    bits = torch.zeros(words * 32, dtype=torch.int64, device=flags.device)
+    bits[:n] = flags.reshape(-1)
+    w = (bits.reshape(words, 32) << torch.arange(32, dtype=torch.int64, device=flags.device)).sum(dim=1)
+    return torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+
+
+def refine(tree, sel, companions=(), stream=None) -> dict:
+    """A NEW tree in which the selected leaves of ``tree`` are subdivided into N^3 leaves that hold their parent's
+    values -- vr_refine_plan / vr_refine_apply on the tree's binary16 values (``read_data``) and its child array,
+    then an upload of the result from device memory (``N3Tree.from_device_arrays``).  No value crosses to the host.
+
+    ``sel``: a bool tensor of capacity * N^3 elements (any shape), or the int32 bitmap of ``touched_words()`` words
+    (bit s & 31 of word s >> 5, s = file node * N^3 + child slot).  A set bit refines its slot if the slot is a
+    leaf; bits of internal slots are ignored.  The refinement is append-only in the file's numbering: old nodes and
+    slots keep their indices, the r-th refined slot in ascending order becomes node capacity + r.
+    ``companions``: up to 7 ``(tensor, fill)`` pairs, each tensor float16 / float32 / int32 with capacity * N^3 * k
+    elements indexed like the file's ``data`` array (a float32 master, Adam moments, leaf weights ...); ``fill``
+    says what the slots of new nodes get: "copy" (the refined slot's elements) or "zero".
+
+    Returns {"tree": the new ``N3Tree`` (same geometry, format, ``extra`` and NDC), "companions": the restated
+    tensors [capacity + n_new, ...] in order, "src_slot": int32 [n_new], the slot new node capacity + r came from,
+    "n_new": int}.  Host-blocking (the plan's count and the upload).  The old tree stays valid; the caller frees it."""
+    _ = tree.handle
+    N3 = tree.N ** 3
+    n_slots, words = tree.capacity * N3, touched_words(tree)
+    companions = [tuple(p) if isinstance(p, (tuple, list)) else (p,) for p in companions]
+    if len(companions) + 1 > _abi.REFINE_MAX_ARRAYS:
+        raise ValueError(f"at most {_abi.REFINE_MAX_ARRAYS - 1} companions, not {len(companions)}")
+    packed = str(getattr(sel, "dtype", "")).replace("torch.", "") == "bool"
+    bufs = [Buf("sel", sel, ("bool",), None, (n_slots, f"capacity * N^3 = {n_slots} flags")) if packed else
+            _touched_buf(tree, sel)._replace(name="sel")]
+    dims = []
+    for i, p in enumerate(companions):
+        if len(p) != 2 or p[1] not in _abi.REFINE_FILLS:
+            raise ValueError(f"companions[{i}] must be (tensor, 'copy' or 'zero')")
+        count = int(np.prod(_shape_of(p[0]), dtype=np.int64)) if hasattr(p[0], "shape") or hasattr(
+            p[0], "__cuda_array_interface__") else 0
+        if count < n_slots or count % n_slots:
+            raise ValueError(f"companions[{i}] must have capacity * N^3 * k = {n_slots} * k elements, not {count}")
+        dims.append(count // n_slots)
+        bufs.append(Buf(f"companions[{i}]", p[0], (F16, F32, I32)))
+    c = check(tree, bufs)
+    import torch
+    from ._tree import N3Tree
+    device = torch.device("cuda", c.device_index())
+    L, sp = _abi.lib(), _stream_ptr(stream)
+    with torch.cuda.device(device):
+        if packed:
+            sel = _pack_bits(sel)
+            torch.cuda.current_stream(device).synchronize()   # (torch's stream need not be ``stream``)
+        data = read_data(tree, stream=stream)
+        child = torch.from_numpy(np.ascontiguousarray(tree.child_, dtype=np.int32)).to(device)
+        ws = torch.empty(int(L.vr_refine_workspace(tree.N, tree.capacity)), dtype=torch.uint8, device=device)
+        r = _abi.VrRefine()
+        r.child, r.sel = child.data_ptr(), int(sel.data_ptr()) if packed else c.ptr["sel"]
+        r.workspace, r.workspace_bytes = ws.data_ptr(), ws.numel()
+        r.capacity, r.N = tree.capacity, tree.N
+        n_new = C.c_int64(0)
+        _abi.check(L.vr_refine_plan(C.byref(r), C.byref(n_new), sp))
+        n_new = int(n_new.value)
+        cap = tree.capacity + n_new
+        child_out = torch.empty((cap, tree.N, tree.N, tree.N), dtype=torch.int32, device=device)
+        src_slot = torch.empty(n_new, dtype=torch.int32, device=device)
+        data_out = torch.empty((cap, tree.N, tree.N, tree.N, tree.data_dim), dtype=torch.float16, device=device)
+        outs = [torch.empty((cap, tree.N, tree.N, tree.N, k) if k > 1 else (cap, tree.N, tree.N, tree.N),
+                            dtype=getattr(torch, c.dtype[f"companions[{i}]"]), device=device)
+                for i, k in enumerate(dims)]
+        arrays = (_abi.VrRefineArray * (len(outs) + 1))()
+        srcs = [data.data_ptr()] + [c.ptr[f"companions[{i}]"] for i in range(len(companions))]
+        for a, src, dst, k, fill in zip(arrays, srcs, [data_out] + outs, [tree.data_dim] + dims,
+                                        ["copy"] + [p[1] for p in companions]):
+            a.src, a.dst, a.elem_bytes, a.dim, a.fill = src, dst.data_ptr(), dst.element_size(), k, \
+                _abi.REFINE_FILLS[fill]
+        r.child_out, r.src_slot, r.n_new = child_out.data_ptr(), src_slot.data_ptr() if n_new else None, n_new
+        r.arrays, r.n_arrays = arrays, len(arrays)
+        _abi.check(L.vr_refine_apply(C.byref(r), sp))
+        _abi.check(L.vr_stream_sync(sp))   # (the upload reads the arrays on streams of its own)
+        new = N3Tree.from_device_arrays(child_out, data_out, tree.offset, tree.scale, tree.data_format,
+                                        extra=getattr(tree, "extra_", None),
+                                        ndc=(tree.ndc_width, tree.ndc_height, tree.ndc_focal) if tree.use_ndc else None)
+    return {"tree": new, "companions": outs, "src_slot": src_slot, "n_new": n_new}
+
+
 # ---- a sparse optimiser step, in place (vr_tree_step) ----
 def tree_step(tree, master, grad, touched, *, kind="sgd", lr, lr_sigma=None, m=None, v=None, betas=(0.9, 0.999),
               eps: float = 1e-8, step: int = 1, stream=None) -> None:

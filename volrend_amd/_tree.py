@@ -8,7 +8,16 @@ import os
 import numpy as np
 
 from . import _abi, _ops
-from ._args import _stream_ptr
+from ._args import F16, I32, Buf, _stream_ptr, check
+
+
+class _CurrentDevice:
+    """Stands where ``_args.check`` asks a tree for its device, for arrays that are about to become one on the
+    calling thread's current device (asked of torch only then: the other checks come first and need no device)."""
+
+    def info(self) -> dict:
+        import torch
+        return {"device": int(torch.cuda.current_device())}
 
 
 def parse_data_format(s: str):
@@ -130,17 +139,54 @@ class N3Tree:
             self.load_device()
 
     # ---- device ----------------------------------------------------------
+    @classmethod
+    def from_device_arrays(cls, child_dev, data_dev, offset, invradius3, data_format: str, extra=None,
+                           ndc=None) -> "N3Tree":
+        """A tree uploaded from arrays that are ALREADY ON THE DEVICE (vr_tree_upload with memory = 1): what
+        ``refine`` produces, or anything else that builds the file's layout there.  ``child_dev``: int32
+        [capacity, N, N, N], ``data_dev``: float16 [capacity, N, N, N, data_dim], contiguous tensors on the calling
+        thread's current device, which becomes the tree's; the work that produced them must be finished (the
+        upload does not run on the caller's stream).  The library copies what it needs: both may be freed
+        afterwards.  ``child_`` holds a host copy of the child array; ``data_`` stays None, the state
+        ``clear_cpu_memory`` leaves (``read_data`` returns what the device holds)."""
+        shape = tuple(getattr(child_dev, "shape", ()))
+        if len(shape) != 4 or not (shape[1] == shape[2] == shape[3]):
+            raise ValueError("child_dev must be an int32 tensor [capacity, N, N, N]")
+        dshape = tuple(getattr(data_dev, "shape", ()))
+        if len(dshape) != 5 or dshape[:4] != shape or dshape[4] < 1:
+            raise ValueError(f"data_dev must be a float16 tensor [capacity, N, N, N, data_dim] over {shape}, not {dshape}")
+        c = check(_CurrentDevice(), [Buf("child_dev", child_dev, (I32,), shape), Buf("data_dev", data_dev, (F16,), dshape)])
+        t = cls()
+        t.capacity, t.N, t.data_dim = int(shape[0]), int(shape[1]), int(dshape[4])
+        t.child_ = child_dev.cpu().numpy().reshape(shape)
+        # (a tree's own (format name, basis_dim) pair is taken as it is: refine hands the old tree's on)
+        t.data_format = parse_data_format(data_format) if isinstance(data_format, str) else tuple(data_format)
+        t.scale = np.asarray(invradius3, dtype=np.float32).reshape(3).copy()
+        t.offset = np.asarray(offset, dtype=np.float32).reshape(3).copy()
+        t.extra_ = None if extra is None else np.ascontiguousarray(extra, dtype=np.float32)
+        if ndc:
+            t.use_ndc = True
+            t.ndc_width, t.ndc_height, t.ndc_focal = map(float, ndc)
+        t._upload(c.ptr["child_dev"], c.ptr["data_dev"], memory=1)
+        return t
+
     def load_device(self) -> None:
         """``N3Tree::load_cuda`` (src/cuda/n3tree.cu:9-41)."""
+        self.free_device()
+        if self.data_ is None and self.quant_ is None:
+            raise RuntimeError("tree has no data (clear_cpu_memory was called)")
+        self._upload(self.child_.ctypes.data, None if self.data_ is None else self.data_.ctypes.data, memory=0)
+
+    def _upload(self, child_ptr, data_ptr, memory: int) -> None:
+        """vr_tree_upload (or its quantised form when there is no data array) of arrays in host (``memory`` 0) or
+        device (1) memory."""
         L = _abi.lib()
         self.free_device()
         d = _abi.VrTreeDesc()
         L.vr_default_tree_desc(C.byref(d))
-        d.child = self.child_.ctypes.data
-        if self.data_ is not None:
-            d.data = self.data_.ctypes.data
-        elif self.quant_ is None:
-            raise RuntimeError("tree has no data (clear_cpu_memory was called)")
+        d.child = child_ptr
+        if data_ptr is not None:
+            d.data = data_ptr
         if self.extra_ is not None:
             d.extra = self.extra_.ctypes.data
             d.extra_count = self.extra_.size
@@ -155,9 +201,9 @@ class N3Tree:
         d.ndc_width = self.ndc_width if self.use_ndc else -1.0
         d.ndc_height = self.ndc_height
         d.ndc_focal = self.ndc_focal
-        d.memory = 0
+        d.memory = memory
         h = C.c_void_p()
-        if self.data_ is None:
+        if data_ptr is None:
             _abi.check(L.vr_tree_upload_quantized(C.byref(d), C.byref(self._quant_desc()),
                                                   C.byref(h)))
         else:
@@ -300,6 +346,7 @@ class N3Tree:
     render_backward_rays, touched_words = _ops.render_backward_rays, _ops.touched_words
     fit_rays, order_rays = _ops.fit_rays, _ops.order_rays
     step, update_data, read_data = _ops.tree_step, _ops.update_data, _ops.read_data
+    refine = _ops.refine
 
     def info(self) -> dict:
         i = _abi.VrTreeInfo()

@@ -265,16 +265,44 @@ void N3Tree::decode_quantized_host() {
 }
 
 void N3Tree::load_device() {
-    free_device();
-    VrTreeDesc d;
-    vr_default_tree_desc(&d);
     // const access: stored members stay zero-copy views into the mapped file
     const internal::NpyArray& cchild = child_;
     const internal::NpyArray& cdata = data_;
-    const internal::NpyArray& cextra = extra_;
-    d.child = cchild.data<int32_t>();
     const bool quantised = data_.empty() && !quant_map_.empty();
-    if (!quantised) d.data = cdata.data<uint16_t>();
+    upload_arrays(cchild.data<int32_t>(), quantised ? nullptr : cdata.data<uint16_t>(), 0);
+}
+
+N3Tree::N3Tree(const N3Tree& like, const int32_t* child_dev, const uint16_t* data_dev, int capacity_) {
+    N = like.N;
+    N2_ = like.N2_;
+    N3_ = like.N3_;
+    data_dim = like.data_dim;
+    data_format = like.data_format;
+    capacity = capacity_;
+    scale = like.scale;
+    offset = like.offset;
+    use_ndc = like.use_ndc;
+    ndc_width = like.ndc_width;
+    ndc_height = like.ndc_height;
+    ndc_focal = like.ndc_focal;
+    ndc_avg_up = like.ndc_avg_up;
+    ndc_avg_back = like.ndc_avg_back;
+    ndc_avg_cen = like.ndc_avg_cen;
+    extra_ = like.extra_;
+    if (!child_dev || !data_dev) throw std::runtime_error("N3Tree: NULL device array");
+    upload_arrays(child_dev, data_dev, 1);
+}
+
+// vr_tree_upload of child / data arrays in host (memory 0) or device (1) memory; without a data array, the
+// quantised upload of the codebook members.
+void N3Tree::upload_arrays(const int32_t* child, const uint16_t* data, int memory) {
+    free_device();
+    VrTreeDesc d;
+    vr_default_tree_desc(&d);
+    const internal::NpyArray& cextra = extra_;
+    d.child = child;
+    const bool quantised = data == nullptr;
+    if (!quantised) d.data = data;
     if (!extra_.empty()) {
         d.extra = cextra.data<float>();
         d.extra_count = extra_.num_bytes() / sizeof(float);
@@ -291,7 +319,7 @@ void N3Tree::load_device() {
     d.ndc_width = use_ndc ? ndc_width : -1.f;
     d.ndc_height = ndc_height;
     d.ndc_focal = ndc_focal;
-    d.memory = 0;
+    d.memory = memory;
     int rc;
     if (quantised) {
         const internal::NpyArray &cs = sigma_, &cm = quant_map_, &cc = quant_colors_,

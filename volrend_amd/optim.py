@@ -156,6 +156,22 @@ class SparseTreeOptimizer:
                               stream=self._stream())["sq_err"]
         return sq_err if order is None else _caller_order(order, sq_err)
 
+    def refine(self, sel):
+        """Subdivides the selected leaves (``api.refine``) between ``step()`` and the next ``backward`` / ``fit``:
+        ``self.tree`` becomes the refined tree, ``master`` grows by copies of the refined slots' values, ``m`` / ``v``
+        keep the old slots and are zero in the new ones, ``grad`` and ``touched`` are zeros of the new size (after
+        ``step()`` they were zero anyway).  Old slots keep their indices.  Returns ``src_slot`` (int32 [n_new]): the
+        slot each new node came from.  The old tree stays valid for whoever still holds it."""
+        pairs = [(self.master, "copy")] + ([(self.m, "zero"), (self.v, "zero")] if self.kind == "adam" else [])
+        res = api.refine(self.tree, sel, pairs, stream=self._stream())
+        self.tree = res["tree"]
+        self.master = res["companions"][0]
+        if self.kind == "adam":
+            self.m, self.v = res["companions"][1:3]
+        self.grad = torch.zeros_like(self.master)
+        self.touched = torch.zeros(api.touched_words(self.tree), dtype=torch.int32, device=self.master.device)
+        return res["src_slot"]
+
     def step(self) -> None:
         """The optimiser step over the marked slots; afterwards ``grad`` and ``touched`` are zero again."""
         self.steps += 1
