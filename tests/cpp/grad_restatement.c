@@ -53,6 +53,7 @@ typedef struct {
 typedef struct {
     int32_t pixel;    /* y * width + x */
     int32_t stopped;  /* stop_thresh ended the ray at its last hit */
+    int32_t entered;  /* the ray passed the ray/box test: the device gives it a lane */
     int64_t first, n; /* its hits: hits[first .. first + n) */
     float basis[25];
 } GradRay;
@@ -122,6 +123,7 @@ GradTrace* grad_trace_frame(const OrTree* tree, const OrCamera* cam, const OrOpt
             }
             ray->n = tr->n_hits - ray->first;
             ray->stopped = m.stopped;
+            ray->entered = m.entered;
             if (m.entered && tr->n_basis > 0) {
                 if (fp_mode == OR_FP_FMA) precalc_basis_fma(tree, m.vdir, ray->basis);
                 else precalc_basis_strict(tree, m.vdir, ray->basis);
@@ -136,6 +138,11 @@ void grad_trace_rays(const GradTrace* tr, int64_t* n_hits, uint8_t* stopped) {
         n_hits[r] = tr->rays[r].n;
         stopped[r] = (uint8_t)tr->rays[r].stopped;
     }
+}
+
+/* Per pixel: whether the ray entered the volume (a ray that did not is never marched). */
+void grad_trace_entered(const GradTrace* tr, uint8_t* entered) {
+    for (int64_t r = 0; r < tr->n_rays; ++r) entered[r] = (uint8_t)(tr->rays[r].entered != 0);
 }
 
 /* The slots of ray r's hits, in march order (out: ray's n entries). */

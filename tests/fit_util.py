@@ -1,11 +1,17 @@
 """Helpers of the vr_fit_rays tests: the numpy restatement of the loss head (include/volrend_hip.h), the rays of a
-camera as the FMA model's matrix product forms them, and the float64 gradient of a batch for the head's g."""
+camera as the FMA model's matrix product forms them, the float64 gradient of a batch for the head's g, and the four
+checks the GPU tests hold a fused call to (assert_four)."""
 from __future__ import annotations
+
+import ctypes as C
 
 import numpy as np
 
 from tests import grad_util as gu
 from tests import rays_util as ru
+from tests import step_util as su
+
+BG = 0.625                                   # not 0 and not 1: g_3 = -bg sum g_ch matters
 
 
 def head(out, target, bg, grad_scale, dtype=np.float32):
@@ -86,3 +92,95 @@ def reference_for(ref, g):
     for i, t in enumerate(ref["traces"]):
         t.backward64(d64, g[i], grad, mag, under)
     return dict(ref, g=g, grad=grad, mag=mag, under=under)
+
+
+# ---- shared by the GPU tests (torch is handed in: the module imports without it) -----------------------------------
+def dev(torch, a):
+    return torch.from_numpy(np.array(a, order="C")).cuda()      # (a copy: the references are read-only)
+
+
+def bits(a):
+    return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).view(np.uint32)
+
+
+def zero_bits(torch, tree):
+    return torch.zeros(su.n_words(tree.capacity * tree.N ** 3), dtype=torch.int32, device="cuda")
+
+
+def options(ref, **kw):
+    from volrend_amd import api
+    return api.RenderOptions(**dict(dict(ref["opt"], background_brightness=BG), **kw))
+
+
+def fit(torch, t, ref, o, d, target, fp_mode, grad_scale, start=None, grad_data=None, touched="new", want=("sq_err", "accum"),
+        opts=None, out=None):
+    """One fit_rays call -> (result dict, touched).  ``out``: the caller's own "sq_err" [n] and "accum" [n, 4]
+    tensors (the Python call allocates these two itself, so this goes through the C entry point)."""
+    if grad_data is None and start is not None:
+        grad_data = dev(torch, start)
+    if isinstance(touched, str):
+        touched = zero_bits(torch, ref["tree"])
+    od, dd, td, opts = dev(torch, o), dev(torch, d), dev(torch, target), opts or options(ref)
+    if out is None:
+        res = t.fit_rays(od, dd, opts, td, grad_scale=grad_scale, grad_data=grad_data, touched=touched, want=want,
+                         fp_mode=fp_mode)
+        return res, touched
+    from volrend_amd import _abi
+    assert len(o) > 0 and grad_data is not None and touched is not None
+    rays, c_opts, c_fit = _abi.VrRays(), opts.to_c(), _abi.VrFit()
+    rays.origins, rays.dirs = od.data_ptr(), dd.data_ptr()
+    c_fit.target, c_fit.grad_scale, c_fit.grad_data = td.data_ptr(), float(grad_scale), grad_data.data_ptr()
+    c_fit.touched, c_fit.sq_err, c_fit.accum = touched.data_ptr(), out["sq_err"].data_ptr(), out["accum"].data_ptr()
+    _abi.check(_abi.lib().vr_fit_rays(t.handle, len(o), C.byref(rays), C.byref(c_opts), int(fp_mode), C.byref(c_fit),
+                                      None))
+    torch.cuda.synchronize()       # (od, dd, td are this function's: they must outlive the launch)
+    return dict(out, grad_data=grad_data), touched
+
+
+def unfused(torch, t, ref, o, d, target, fp_mode, grad_scale, opts=None):
+    """The sequence the call fuses: render_rays -> the numpy head -> the marked render_backward_rays
+    -> (accum float32 [n, 4], the head's dict, grad_data, touched words)."""
+    opts = opts or options(ref)
+    od, dd = dev(torch, o), dev(torch, d)
+    accum = t.render_rays(od, dd, opts, want=("accum",), fp_mode=fp_mode)["accum"].cpu().numpy()
+    want = head(accum, target, BG, grad_scale)
+    touched = zero_bits(torch, ref["tree"])
+    grad = t.render_backward_rays(od, dd, opts, dev(torch, want["g"]), fp_mode=fp_mode, touched=touched)
+    return accum, want, grad, touched
+
+
+def assert_four(torch, t, ref, o, d, target, fp_mode, what, idx=None, guarded=None):
+    """The four checks of tests/test_gpu_fit.py's docstring for one list (rays ``idx`` of the views of ``ref``; all
+    when None).  ``guarded``: a factory (torch, shape, numpy dtype, init) -> an object with .tensor and .host() (the
+    Guarded of tests/rays_util.py): the call's four outputs then sit in such buffers, whose guard bands .host()
+    checks."""
+    n = len(o)
+    grad_scale = 2.0 / (3 * n)
+    start = gu.sentinel(ref["grad"].shape)
+    if guarded is None:
+        res, touched = fit(torch, t, ref, o, d, target, fp_mode, grad_scale, start=start)
+    else:
+        tree = ref["tree"]
+        bufs = dict(grad_data=guarded(torch, start.shape, np.float32, start),
+                    touched=guarded(torch, (su.n_words(tree.capacity * tree.N ** 3),), np.int32, 0),
+                    sq_err=guarded(torch, (n,), np.float32, None), accum=guarded(torch, (n, 4), np.float32, None))
+        fit(torch, t, ref, o, d, target, fp_mode, grad_scale, grad_data=bufs["grad_data"].tensor,
+            touched=bufs["touched"].tensor, out=dict(sq_err=bufs["sq_err"].tensor, accum=bufs["accum"].tensor))
+        res = {k: b.host() for k, b in bufs.items()}
+        touched = res.pop("touched")
+    accum, want, _, touched_b = unfused(torch, t, ref, o, d, target, fp_mode, grad_scale)
+    torch.cuda.synchronize()
+    assert t.status() == 0
+    assert np.isfinite(accum).all()
+    bad = (bits(res["accum"]) != bits(accum)).any(1)
+    assert not bad.any(), f"{what}: accum differs from render_rays in {int(bad.sum())} of {n} rays, first {np.flatnonzero(bad)[:4]}"
+    bad = bits(res["sq_err"]) != bits(want["sq_err"])
+    assert not bad.any(), f"{what}: sq_err differs from the numpy head in {int(bad.sum())} of {n} rays"
+    assert np.array_equal(bits(touched), bits(touched_b)), f"{what}: touched differs from the marked backward's"
+    assert bits(touched).any()
+    g = np.zeros((len(ref["traces"]) * ref["h"] * ref["w"], 4), np.float32)
+    g[np.arange(n) if idx is None else idx] = want["g"]
+    fref = reference_for(ref, g)
+    got = res["grad_data"]
+    gu.assert_parity(got.cpu().numpy() if hasattr(got, "cpu") else got, fref, start=start, what=what)
+    return res, want, fref

@@ -36,6 +36,8 @@ def lib(mutant=0):
     L.grad_trace_free.argtypes = [C.c_void_p]
     L.grad_trace_rays.restype = None
     L.grad_trace_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.grad_trace_entered.restype = None
+    L.grad_trace_entered.argtypes = [C.c_void_p, C.c_void_p]
     L.grad_trace_slots.restype = None
     L.grad_trace_slots.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     L.grad_trace_all_slots.restype = None
@@ -69,6 +71,9 @@ class Trace:
         stopped = np.zeros(w * h, np.uint8)
         lib().grad_trace_rays(self.ptr, _p(self.n_hits), _p(stopped))
         self.stopped = stopped.astype(bool)
+        entered = np.zeros(w * h, np.uint8)
+        lib().grad_trace_entered(self.ptr, _p(entered))
+        self.entered = entered.astype(bool)      # the ray passed the ray/box test: the device marches it
 
     def __del__(self):
         if getattr(self, "ptr", None):
@@ -213,6 +218,54 @@ PARITY_TREES = [("sh16", 96, 2), ("sh9_near", 96, 1), ("sh4", 40, 1), ("sh25", 4
                 ("rgba", 40, 1), ("n4", 40, 1), ("blocked", 40, 1), ("ndc", 0, 1)]
 PARITY_CASES = [(n, s, p, o, "normal") for n, s, p in PARITY_TREES for o in OPTION_SETS] + \
                [("sh16", 96, 2, "default", "colour"), ("sh16", 96, 2, "default", "alpha")]
+
+
+# The cases of tests/test_gpu_sched.py, where every wave of the backward march takes several chunks: 8 poses at
+# 96 x 96, so up to four times the contributions per element of the cases above.
+# (tree, size, poses, option set, gkind, FP models).  Their summation constant, measured like K32
+# (tests/test_grad_restatement.py::test_summation_constant_of_the_scheduling_cases): 13.855 (sh9_near without
+# early stop, strict, either order; every other case 2.1-5.1).  That is below K32, so the cases use K and K_EDGE
+# unchanged.
+NO_STOP = (("stop_thresh", 0.0),)
+SCHED_POSES, SCHED_SIZE = 8, 96
+SCHED_CASES = [("sh16", SCHED_SIZE, SCHED_POSES, "default", "normal", (0, 1)),
+               ("sh16", SCHED_SIZE, SCHED_POSES, "default", "alpha", (0,)),
+               ("sh9_near", SCHED_SIZE, SCHED_POSES, "default", "normal", (0,)),
+               ("sh9_near", SCHED_SIZE, SCHED_POSES, NO_STOP, "normal", (0,)),
+               ("sh25", SCHED_SIZE, SCHED_POSES, "default", "normal", (0,)),
+               ("rgba", SCHED_SIZE, SCHED_POSES, "default", "normal", (0,)),
+               ("basis1", SCHED_SIZE, SCHED_POSES, "default", "normal", (0,)),
+               ("n4", SCHED_SIZE, SCHED_POSES, "default", "normal", (0,))]
+SCHED_K32_MEASURED = 13.855
+
+
+def entering(ref):
+    """Rays of the views of ``ref`` that enter the volume -- the rays a march launch hands to its waves -- and
+    those among them without a hit sample -> (int, int)."""
+    return (sum(int(t.entered.sum()) for t in ref["traces"]),
+            sum(int((t.entered & (t.n_hits == 0)).sum()) for t in ref["traces"]))
+
+
+def hit_slots(ref, rays=None):
+    """bool [n_slots]: the slots a hit sample of the views of ``ref`` falls into (of the rays ``rays``, indices
+    into the frames' pixels frame after frame, when given) -- what a marked backward call must mark, exactly."""
+    dd = ref["grad"].shape[-1]
+    hit = np.zeros(ref["grad"].size // dd, bool)
+    keep = None
+    if rays is not None:
+        keep = np.zeros(len(ref["traces"]) * ref["w"] * ref["h"], bool)
+        keep[rays] = True
+    for i, t in enumerate(ref["traces"]):
+        slots, ray = t.all_slots()
+        hit[slots if keep is None else slots[keep[i * ref["w"] * ref["h"] + ray]]] = True
+    return hit
+
+
+def mark_words(hit):
+    """The ``touched`` bitmap of a slot mask: bit s & 31 of word s >> 5, uint32."""
+    padded = np.zeros((hit.size + 31) // 32 * 32, np.uint8)
+    padded[:hit.size] = hit
+    return np.packbits(padded.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1)
 
 
 def unit(ref):

@@ -91,3 +91,40 @@ def arbitrary_rays(tree, n=600, seed=0):
     combos = {tuple(s) for s in (dirs > 0).astype(int)}
     assert len(combos) == 8, "not every sign combination is present"
     return np.ascontiguousarray(origins, np.float32), np.ascontiguousarray(dirs)
+
+
+def strip_camera(n, fp_mode=0):
+    """A camera of n x 1 pixels whose rays fan through the middle of the volume -> (transform, w, h, focal): a ray
+    list of ANY length n that is also a frame, so the oracle, the leaf-weight restatement and the gradient trace
+    of that frame judge it.  The strict model takes an orbit pose; the FMA model a signed-permutation pose, whose
+    matrix product is exact fused or not.  (The focal length is that of max(n, 8) pixels: the one ray of n = 1
+    then looks at the middle of the volume, not past it.)"""
+    from tests import common
+    if fp_mode == 0:
+        return common.camera_for(pose_idx=1, size=96)[0], n, 1, max(n, 8) * 1111.111 / 800.0
+    return permutation_pose(), n, 1, max(n, 8) * 112.0 / 95.0
+
+
+# ---- shared by the GPU tests (torch is handed in: the module imports without it) -----------------------------------
+GUARD, POISON = 4096, 0xA5
+
+
+class Guarded:
+    """An output of exactly its own size with a poisoned guard band behind it (the idea of
+    tests/test_gpu_refine.py): ``tensor`` is what the call gets, ``host()`` the result once the band has been seen
+    intact.  init: None = poisoned like the band, a number or an array = what the buffer starts from."""
+
+    def __init__(self, torch, shape, dtype, init=None):
+        self.shape, self.dtype = tuple(int(x) for x in shape), np.dtype(dtype)
+        self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
+        self.raw = torch.full((self.nbytes + GUARD,), POISON, dtype=torch.uint8, device="cuda")
+        tdtype = {"float32": torch.float32, "int32": torch.int32, "uint8": torch.uint8}[self.dtype.name]
+        self.tensor = self.raw[:self.nbytes].view(tdtype).view(self.shape)
+        assert self.tensor.data_ptr() == self.raw.data_ptr() and self.tensor.is_contiguous()
+        if init is not None:
+            self.tensor.copy_(torch.from_numpy(np.broadcast_to(np.asarray(init, self.dtype), self.shape).copy()))
+
+    def host(self):
+        raw = self.raw.cpu().numpy()
+        assert (raw[self.nbytes:] == POISON).all(), "a store went beyond the end of an output"
+        return raw[:self.nbytes].view(self.dtype).reshape(self.shape).copy()

@@ -19,11 +19,10 @@ from tests import aov_util as au
 from tests import common
 from tests import fit_util as fu
 from tests import grad_util as gu
-from tests import step_util as su
+from tests.fit_util import BG, assert_four, bits, dev, fit, options, unfused, zero_bits
 from tests.grad_util import assert_parity, sentinel
 
 pytestmark = pytest.mark.gpu
-BG = 0.625                                   # not 0 and not 1: g_3 = -bg sum g_ch matters
 
 
 @pytest.fixture(scope="module")
@@ -32,70 +31,6 @@ def torch_cuda():
     if not torch.cuda.is_available():
         pytest.skip("no GPU visible")
     return torch
-
-
-def dev(torch, a):
-    return torch.from_numpy(np.array(a, order="C")).cuda()      # (a copy: the references are read-only)
-
-
-def bits(a):
-    return np.ascontiguousarray(a.cpu().numpy() if hasattr(a, "cpu") else a).view(np.uint32)
-
-
-def zero_bits(torch, tree):
-    return torch.zeros(su.n_words(tree.capacity * tree.N ** 3), dtype=torch.int32, device="cuda")
-
-
-def options(ref, **kw):
-    from volrend_amd import api
-    return api.RenderOptions(**dict(dict(ref["opt"], background_brightness=BG), **kw))
-
-
-def fit(torch, t, ref, o, d, target, fp_mode, grad_scale, start=None, grad_data=None, touched="new", want=("sq_err", "accum"),
-        opts=None):
-    """One fit_rays call -> (result dict, touched)."""
-    if grad_data is None and start is not None:
-        grad_data = dev(torch, start)
-    if isinstance(touched, str):
-        touched = zero_bits(torch, ref["tree"])
-    res = t.fit_rays(dev(torch, o), dev(torch, d), opts or options(ref), dev(torch, target), grad_scale=grad_scale,
-                     grad_data=grad_data, touched=touched, want=want, fp_mode=fp_mode)
-    return res, touched
-
-
-def unfused(torch, t, ref, o, d, target, fp_mode, grad_scale, opts=None):
-    """The sequence the call fuses: render_rays -> the numpy head -> the marked render_backward_rays
-    -> (accum float32 [n, 4], the head's dict, grad_data, touched words)."""
-    opts = opts or options(ref)
-    od, dd = dev(torch, o), dev(torch, d)
-    accum = t.render_rays(od, dd, opts, want=("accum",), fp_mode=fp_mode)["accum"].cpu().numpy()
-    want = fu.head(accum, target, BG, grad_scale)
-    touched = zero_bits(torch, ref["tree"])
-    grad = t.render_backward_rays(od, dd, opts, dev(torch, want["g"]), fp_mode=fp_mode, touched=touched)
-    return accum, want, grad, touched
-
-
-def assert_four(torch, t, ref, o, d, target, fp_mode, what, idx=None):
-    """The four checks of the module docstring for one list (rays ``idx`` of the views of ``ref``; all when None)."""
-    n = len(o)
-    grad_scale = 2.0 / (3 * n)
-    start = sentinel(ref["grad"].shape)
-    res, touched = fit(torch, t, ref, o, d, target, fp_mode, grad_scale, start=start)
-    accum, want, _, touched_b = unfused(torch, t, ref, o, d, target, fp_mode, grad_scale)
-    torch.cuda.synchronize()
-    assert t.status() == 0
-    assert np.isfinite(accum).all()
-    bad = (bits(res["accum"]) != bits(accum)).any(1)
-    assert not bad.any(), f"{what}: accum differs from render_rays in {int(bad.sum())} of {n} rays, first {np.flatnonzero(bad)[:4]}"
-    bad = bits(res["sq_err"]) != bits(want["sq_err"])
-    assert not bad.any(), f"{what}: sq_err differs from the numpy head in {int(bad.sum())} of {n} rays"
-    assert np.array_equal(bits(touched), bits(touched_b)), f"{what}: touched differs from the marked backward's"
-    assert bits(touched).any()
-    g = np.zeros((len(ref["traces"]) * ref["h"] * ref["w"], 4), np.float32)
-    g[np.arange(n) if idx is None else idx] = want["g"]
-    fref = fu.reference_for(ref, g)
-    assert_parity(res["grad_data"].cpu().numpy(), fref, start=start, what=what)
-    return res, want, fref
 
 
 def case_rays(ref, fp_mode):
