@@ -714,6 +714,16 @@ int vr_sched_stats(vr_tree_t tree, uint64_t out[8], int reset);
  * occupied cell.  out[0] = blocks that launches with the cull on have generated or skipped, out[1] = the skipped
  * ones among them.  Synchronous (copies from the device); reset != 0 clears them. */
 int vr_tree_cull_stats(vr_tree_t tree, uint64_t out[2], int reset);
+/* Lead-in march (tuning key "head_march", default 1): in colour and AOV frame launches of a tree on the N == 2
+ * lookup path, ray generation takes a ray's samples in front of its first sample with sigma > sigma_thresh -- they
+ * change nothing of the ray but t -- and hands the ray over at the t it has reached; a ray that reaches its tmax
+ * without such a sample gets the pixel of a ray without a hit sample there.  The sample sequence is the march
+ * kernel's own: no pixel and no plane changes.  Not with counters / render_depth / SG / ASG, ray lists, or
+ * "max_iter" below its default.  "head_min_lanes" (1..64) and "head_max" say when the 64 rays of a block are
+ * handed over: once fewer of them still march, or after that many rounds; 0 = the library's choice.
+ * out[0] = rays that entered the lead-in march, out[1] = those that ended in it, out[2] = samples marched there.
+ * Synchronous (copies from the device); reset != 0 clears them. */
+int vr_tree_head_stats(vr_tree_t tree, uint64_t out[3], int reset);
 /* Distinct-line meter (SURVEY.md 8(d) "B_unique", the compulsory-traffic lower bound): with
  * enable != 0 the tree gets one bit per 128-byte line of its device arrays, and every
  * INSTRUMENTED launch (frames with counters) sets the bits of the lines its accesses touch.

@@ -193,6 +193,7 @@ PROTOTYPES = {
     "vr_tree_set_tuning": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int]),
     "vr_sched_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 8), C.c_int]),
     "vr_tree_cull_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 2), C.c_int]),
+    "vr_tree_head_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 3), C.c_int]),
     "vr_touch_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "vr_touch_count": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64 * 4), C.c_int]),
     "vr_touch_read": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64),

@@ -285,6 +285,13 @@ class N3Tree:
         _abi.check(_abi.lib().vr_tree_cull_stats(self.handle, C.byref(out), 1 if reset else 0))
         return {"blocks": int(out[0]), "culled": int(out[1])}
 
+    def head_stats(self, reset: bool = False) -> dict:
+        """Rays that entered the lead-in march of ray generation, those that ended there without a hit sample, and
+        the samples marched there (vr_tree_head_stats)."""
+        out = (C.c_uint64 * 3)()
+        _abi.check(_abi.lib().vr_tree_head_stats(self.handle, C.byref(out), 1 if reset else 0))
+        return {"entered": int(out[0]), "retired": int(out[1]), "samples": int(out[2])}
+
     def touch_enable(self, enable: bool = True) -> None:
         """Distinct-line meter of instrumented launches on / off (vr_touch_enable)."""
         _abi.check(_abi.lib().vr_touch_enable(self.handle, 1 if enable else 0))

@@ -42,6 +42,9 @@ const Knob kKnobs[] = {
     {"max_iter", "VR_MAX_ITER", &Tuning::max_iter, kClamp, 1, INT_MAX, false},
     {"weights_check", "VR_WEIGHTS_CHECK", &Tuning::weights_check, kFlag, 0, 0, false},
     {"block_cull", "VR_BLOCK_CULL", &Tuning::block_cull, kFlag, 0, 0, false},
+    {"head_march", "VR_HEAD_MARCH", &Tuning::head_march, kFlag, 0, 0, false},
+    {"head_min_lanes", "VR_HEAD_MIN_LANES", &Tuning::head_min_lanes, kClamp, 0, 64, false},
+    {"head_max", "VR_HEAD_MAX", &Tuning::head_max, kClamp, 0, INT_MAX, false},
 };
 
 const Knob* find_knob(const char* key) {
@@ -226,6 +229,19 @@ int vr_tree_cull_stats(vr_tree_t t, uint64_t out[2], int reset) {
     for (int i = 0; i < vr::kCullStatLines; ++i) {
         out[0] += lines[i * vr::kCullStatStride];
         out[1] += lines[i * vr::kCullStatStride + 1];
+    }
+    return VR_OK;
+}
+
+int vr_tree_head_stats(vr_tree_t t, uint64_t out[3], int reset) {
+    if (!t || !out) return fail(VR_ERR_INVALID_ARGUMENT, "NULL argument");
+    DeviceGuard guard(t->device);
+    uint64_t lines[vr::kCullStatLines * vr::kCullStatStride];
+    HIP_TRY(hipMemcpy(lines, t->head_stats.get(), sizeof(lines), hipMemcpyDeviceToHost));
+    if (reset) HIP_TRY(hipMemset(t->head_stats.get(), 0, sizeof(lines)));
+    for (int k = 0; k < vr::kHeadStatWords; ++k) {
+        out[k] = 0;
+        for (int i = 0; i < vr::kCullStatLines; ++i) out[k] += lines[i * vr::kCullStatStride + k];
     }
     return VR_OK;
 }

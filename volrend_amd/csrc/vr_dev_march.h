@@ -234,6 +234,38 @@ __device__ __forceinline__ uint32_t march_sample(const KParams& p, float t, cons
     return leaf;
 }
 
+// The lead-in march of ray generation (vr_internal.h "Lead-in march"; every lane of the wave calls): the lanes
+// whose ray is alive take march_sample's samples in lockstep while they are no hits -- what a march round does to
+// such a ray is t += delta_t and nothing else.  A lane stops WITHOUT advancing t at its first sample with
+// sigma > sigma_thresh (the march kernel takes that sample again, from the same t: the same bits), and stops as not
+// alive once t >= tmax.  The wave stops when fewer than head.min_lanes (>= 1) lanes march or after head.max_rounds
+// rounds; a ray that still marches then keeps the t it has.  The cursor is a cache and is dropped.
+// Returns the samples the wave marched (wave-uniform).
+template <int FMA, int QUERY>
+__device__ __forceinline__ uint32_t head_march(const KParams& p, const HeadParams& head, Ray& nr) {
+    Cursor cur;
+    bool go = nr.alive;
+    uint32_t samples = 0;
+    for (int r = 0; r < head.max_rounds; ++r) {
+        const unsigned long long m_go = __builtin_amdgcn_ballot_w64(go);
+        if (__builtin_popcountll(m_go) < head.min_lanes) break;
+        bool stepped = false;
+        if (go) {
+            float delta_t, sigma;
+            march_sample<FMA, QUERY>(p, nr.t, nr.cen, nr.dir, nr.invdir, cur, delta_t, sigma);
+            if (sigma > p.sigma_thresh) {
+                go = false;
+            } else {
+                nr.t += delta_t;
+                stepped = true;
+                if (!(nr.t < nr.tmax)) go = nr.alive = false;
+            }
+        }
+        samples += (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(stepped));
+    }
+    return samples;
+}
+
 // A hit sample's compositing weight, and through `att` what it leaves of the light: rt_core.cuh:118-121,174
 // (the argument is never NaN: render_kernel says why).  `light *= att` is the caller's.
 __device__ __forceinline__ float sample_weight(float light, float delta_t, float delta_scale, float sigma, float& att) {

@@ -75,6 +75,7 @@ struct VrTreeOpaque : TreeShape {
     DeviceBuffer extra, status, sched_stats;  // float, uint32_t, vr::kSchedStats x u64 (vr_sched_stats)
     DeviceBuffer occ;            // vr::occ_words(occ_levels) uint32_t: length, bitmap and boundary list of the block cull
     DeviceBuffer cull_stats;     // vr::kCullStatLines x vr::kCullStatStride u64 (vr_tree_cull_stats)
+    DeviceBuffer head_stats;     // the same shape, vr::kHeadStatWords words of a line in use (vr_tree_head_stats)
     DeviceBuffer touch[4];       // distinct-line bitmaps of the arrays (vr_touch_enable)
     DeviceBuffer touch_out;      // 4 x u64
     DeviceBuffer probe_buf;      // kLaunchSlots x data_dim floats: the lumisphere at opt.probe

@@ -260,6 +260,22 @@ struct CullParams {
     uint32_t nbx;                    // 8x8 blocks per row of the frame
     unsigned long long* stats;       // kCullStatLines x kCullStatStride
 };
+// ---------------------------------------------------------------------------
+// Lead-in march (the FAST flavours of raygen_kernel, colour and AOV; tuning key head_march): the 64 rays of a block
+// run the sample recurrence of the march round (march_sample, vr_dev_march.h) right behind setup_ray, side by side,
+// while their samples are no hits.  A sample with sigma <= sigma_thresh changes nothing of a ray but t, so the
+// record's kRayT simply holds a later t of the same sequence and render_kernel computes the bits it would have
+// computed from the box entry; a ray that reaches tmax without a hit takes the path of a ray without a sample.
+// A lane stops, t unchanged, at its first hit sample; the wave stops when fewer than min_lanes lanes march or
+// after max_rounds rounds, and whoever still marches is handed over at the t it has.
+// HeadParams is raygen_kernel's own (last) argument: KParams does not change.  max_rounds = 0: no lead-in march.
+// ---------------------------------------------------------------------------
+constexpr int kHeadStatWords = 3;         // words of a kCullStatStride line: rays entered, rays retired, samples marched
+struct HeadParams {
+    int32_t max_rounds;              // rounds a wave marches at most; 0 = off
+    int32_t min_lanes;               // the wave hands over once fewer lanes march (1..64)
+    unsigned long long* stats;       // kCullStatLines x kCullStatStride (vr_tree_head_stats)
+};
 // What block_mask_kernel reads beside KParams (frames, n_frames, offset, scale, width, height, fx, fy).
 struct MaskParams {
     uint32_t* mask;
@@ -397,14 +413,15 @@ hipError_t launch_step_values(const StepArgs& a, int n_cus, hipStream_t stream);
 // vr_render.hip: the kernels of a launch
 hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream_t stream);
 // (cull: the block masks of the launch, CullParams{} = none; a ray list never has one)
-hipError_t launch_render_aov(const KParams& p, const AovParams& a, const CullParams& cull, int fp_mode, int n_cus,
-                             int waves_override, int gen_waves, hipStream_t stream);
+// (head: the lead-in march of ray generation, HeadParams{} = none)
+hipError_t launch_render_aov(const KParams& p, const AovParams& a, const CullParams& cull, const HeadParams& head,
+                             int fp_mode, int n_cus, int waves_override, int gen_waves, hipStream_t stream);
 // (mask: the block masks of the launch, which the kernel clears for its frames; NULL = none)
 hipError_t launch_prepare(const KParams& p, const FrameTable& tbl, hipStream_t stream, uint32_t* mask = nullptr,
                           uint32_t words_per_frame = 0);
 // (rays: as launch_weights; the frame table then holds the list's one pseudo-frame)
-hipError_t launch_render(const KParams& p, const CullParams& cull, int fp_mode, int n_cus, int waves_override,
-                         int gen_waves, hipStream_t stream, const RayList* rays = nullptr);
+hipError_t launch_render(const KParams& p, const CullParams& cull, const HeadParams& head, int fp_mode, int n_cus,
+                         int waves_override, int gen_waves, hipStream_t stream, const RayList* rays = nullptr);
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,
                         hipStream_t stream);
 

@@ -259,9 +259,17 @@ int record_words(LaunchKind kind, int ray_tail_words) {
 }
 bool needs_file_order(LaunchKind kind) { return kind == LaunchKind::kWeights || kind == LaunchKind::kBackward; }
 
+// Whether the tree and the kernel flavour of a launch admit the lead-in march of ray generation (vr_internal.h
+// "Lead-in march"): the N == 2 lookup path and the FAST flavours -- uses_lookup() and !needs_full(), asked before the
+// tree's part of `k` is filled in.  (The FULL flavours' counters equal the oracle's to the integer.)
+bool lead_in_applies(const VrTreeOpaque* t, const vr::KParams& k) {
+    return t->desc.N == 2 && t->top_levels > 0 && t->desc.format != VR_FORMAT_SG && t->desc.format != VR_FORMAT_ASG &&
+           !k.instrumented && !k.render_depth;
+}
+
 // What the enqueue step of a launch finds ready: the finished KParams, the knobs the launch goes by, the waves
 // of a ray-generation workgroup, its slot, its stream, and the pixel words it asked for (else NULL).
-struct Turn { const vr::KParams& k; const Tuning& tn; int gen_waves; unsigned slot; hipStream_t hs; void* extra; };
+struct Turn { const vr::KParams& k; const Tuning& tn; const LaunchPlan& plan; int gen_waves; unsigned slot; hipStream_t hs; void* extra; };
 
 // THE launch sequence; every march launch goes through it.  `k` holds what the entry point checked and filled
 // (geometry, caller's part); extra_bytes: that much more of the slot's buffer behind the records, Turn.extra
@@ -286,7 +294,7 @@ int run_launch(VrTreeOpaque* t, LaunchKind kind, const Views& v, size_t extra_by
     if (k.n_frames == 0) return VR_OK;
     const Tuning tn = t->tn;
     const LaunchPlan plan = plan_launch(kind, v.is_list ? RaySource::kList : RaySource::kFrames, k.n_frames, v.list.n,
-                                        tn, t->arrays[kTop].bytes() + t->arrays[kBricks].bytes());
+                                        tn, t->arrays[kTop].bytes() + t->arrays[kBricks].bytes(), lead_in_applies(t, k));
     fill_tuning_params(k, t, tn, plan);
     const size_t records = ray_buffer_bytes(k.total_rays, record_words(kind, k.ray_tail_words));
     unsigned slot;
@@ -295,7 +303,7 @@ int run_launch(VrTreeOpaque* t, LaunchKind kind, const Views& v, size_t extra_by
     SlotTurn turn;
     if (int rc = turn.begin(t->slots[slot], hs)) return rc;
     void* const extra = extra_bytes ? t->slots[slot].rays.get<char>() + records : nullptr;
-    return enqueue(Turn{k, tn, plan.raygen_waves, slot, hs, extra});  // (`turn` records the slot's event)
+    return enqueue(Turn{k, tn, plan, plan.raygen_waves, slot, hs, extra});  // (`turn` records the slot's event)
 }
 
 // What vr_render_aov adds to the checks of a batch; leaves pitch and depth_world in `a`.
@@ -375,6 +383,13 @@ bool culls_blocks(const VrTreeOpaque* t, const vr::KParams& k, const Tuning& tn,
     return block_mask_words(k) <= (uint32_t)vr::kMaskMaxWords;
 }
 
+// The lead-in march of the launch's ray generation (vr_internal.h "Lead-in march"), as the plan says (which was
+// told what lead_in_applies() found; the finished `k` must agree).
+vr::HeadParams head_params(const VrTreeOpaque* t, const vr::KParams& k, const LaunchPlan& plan) {
+    if (plan.head_max <= 0 || !vr::uses_lookup(k) || vr::needs_full(k)) return vr::HeadParams{};
+    return vr::HeadParams{plan.head_max, plan.head_min_lanes, t->head_stats.get<unsigned long long>()};
+}
+
 // vr_render_batch (aovs = NULL) and vr_render_aov.  Into the stream go the probe pre-kernel, the frame table
 // (for an AOV launch also the plane table, in the launch's slot), the block masks, ray generation + render.
 int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRenderOptions* opt,
@@ -408,10 +423,11 @@ int render_launch(vr_tree_t t, int n_frames, const VrCamera* cams, const VrRende
         }
         if (int rc = enqueue_tables(u.k, v, u.hs, frames, want_aov ? aovs : nullptr, a, m)) return rc;
         if (m.mask) HIP_TRY(vr::launch_block_mask(u.k, m, u.hs));
+        const vr::HeadParams head = head_params(t, u.k, u.plan);
         if (want_aov)
-            HIP_TRY(vr::launch_render_aov(u.k, a, cull, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
+            HIP_TRY(vr::launch_render_aov(u.k, a, cull, head, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
         else
-            HIP_TRY(vr::launch_render(u.k, cull, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
+            HIP_TRY(vr::launch_render(u.k, cull, head, frames[0].fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs));
         return VR_OK;
     });
 }
@@ -656,7 +672,7 @@ int vr_render_rays(vr_tree_t t, int64_t n, const VrRays* rays, const VrRenderOpt
     return run_launch(t, LaunchKind::kColour, v, pixel_bytes, k, stream, [&](const Turn& u) -> int {
         f.rgba = out->rgba ? out->rgba : u.extra;
         if (int rc = enqueue_tables(u.k, v, u.hs, &f)) return rc;
-        HIP_TRY(vr::launch_render(u.k, vr::CullParams{}, fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs, v.rays()));
+        HIP_TRY(vr::launch_render(u.k, vr::CullParams{}, vr::HeadParams{}, fp_mode, t->n_cus, u.tn.waves_per_cu, u.gen_waves, u.hs, v.rays()));
         return VR_OK;
     });
 }

@@ -20,14 +20,26 @@ namespace {
 // A colour launch of a ray list takes the colour rule's 256; super_block orders the blocks of a SCREEN and is
 // never consulted for a list (its ray generation does not call locate()).
 constexpr int kColourChunkCap = 256, kGuidedChunkCap = 4096;
+constexpr uint64_t kBigLookup = 128ull << 20;  // lookup structure (top + bricks) beyond 4x the aggregate L2
+// The lead-in march of ray generation (vr_internal.h "Lead-in march"): a wave marches while at least
+// kAutoHeadMinLanes of its 64 rays have not met density yet, kAutoHeadMax rounds at most.  On the C1 bench orbit the
+// rays of an 8x8 block need 21-23 lockstep rounds to their first hits.  The rounds beyond the bounds are the long
+// tails of a few rays: each costs a round of ray generation, and the persistent kernel marches them beside other
+// rays.  Measured on C1 at 64 frames per launch (EXPERIMENTS.md "Lead-in march"): 32 / 32 and 32 / 16 are the
+// fastest, 16 / 64 is 1 % behind them, marching every ray to its first hit (1 / unbounded) gains nothing.
+constexpr int kAutoHeadMinLanes = 32, kAutoHeadMax = 32;
 
 // waves per ray-generation workgroup: 16 (one atomic per 1024 pixels) -- except launches of one or
 // two frames, the ones that run beside the tail of a neighbour on another stream: workgroups of
 // 4 waves find room there much earlier (vr_render.hip raygen_kernel; profiles/r06_raygen_waves.jsonl:
 // two streams -10 % / -6.5 % at one / two frames per launch, one stream +-0; from four frames on the
 // 4x atomics cost a lone launch 3-4 %, and one-wave workgroups 35 %)
-int raygen_waves(const Tuning& tn, int n_frames) {
-    return tn.raygen_waves > 0 ? tn.raygen_waves : (n_frames <= 2 ? 4 : 16);
+// With the lead-in march (head) the waves of a workgroup run for as long as their blocks' lead-ins take, 0 to
+// head_max rounds: a workgroup of 16 waves waits at its barrier for the slowest of them, and its successor needs four
+// free wave slots on every SIMD at once.  Workgroups of 4 waves for every launch size then: a 64-frame C1 launch takes
+// 0.218 ms per frame against 0.237 with 16 (and 0.224 without the lead-in; EXPERIMENTS.md "Lead-in march").
+int raygen_waves(const Tuning& tn, int n_frames, bool head) {
+    return tn.raygen_waves > 0 ? tn.raygen_waves : (head || n_frames <= 2 ? 4 : 16);
 }
 // A ray list: the same reasoning by ray count.  The frame rule was measured at 800 x 800 pixels, where "two
 // frames" are 1 280 000 rays: lists up to kRayListSmall rays -- an optimiser's step, which runs beside the tail
@@ -41,16 +53,25 @@ int raygen_waves_list(const Tuning& tn, int64_t n) {
 }  // namespace
 
 LaunchPlan plan_launch(LaunchKind kind, RaySource source, int n_frames, int64_t list_rays, const Tuning& tn,
-                       uint64_t lookup_bytes) {
+                       uint64_t lookup_bytes, bool lead_in) {
     const bool colour = kind == LaunchKind::kColour || kind == LaunchKind::kAov;
     const bool list = source == RaySource::kList;
     LaunchPlan p;
     p.chunk_max = tn.chunk_max > 0 ? tn.chunk_max : colour ? kColourChunkCap : kGuidedChunkCap;
     p.super_block = tn.super_block > 0 ? tn.super_block : (colour && !list && n_frames > 2) ? 4 : 1;
-    p.raygen_waves = list ? raygen_waves_list(tn, list_rays) : raygen_waves(tn, n_frames);
+    // the lead-in march: frame launches of the colour kernels whose tree and flavour admit it, and only under the
+    // default sample guard -- a ray that a lowered max_iter cuts short must be cut, and reported, by the march kernel
+    // Not on auto for a lookup structure beyond 4x the aggregate L2 (the records_nt bound below): the lead-in's loads
+    // miss there as the march kernel's do, and C3 at 64 frames per launch is 2.3 % slower with it (one frame: even).
+    // A head_max of the caller's asks for it all the same.
+    const bool head = lead_in && tn.head_march && colour && !list && tn.max_iter >= Tuning().max_iter &&
+                      (tn.head_max > 0 || lookup_bytes <= kBigLookup);
+    p.head_max = !head ? 0 : tn.head_max > 0 ? tn.head_max : kAutoHeadMax;
+    p.head_min_lanes = tn.head_min_lanes > 0 ? tn.head_min_lanes : kAutoHeadMinLanes;
+    p.raygen_waves = list ? raygen_waves_list(tn, list_rays) : raygen_waves(tn, n_frames, head);
     // lookup structure (top + bricks) beyond 4x the aggregate L2 (8 x 4 MiB on MI355X): the record
     // stream would keep evicting it -- see the DMA loads in vr_render.hip
-    p.records_nt = tn.records_nt >= 0 ? tn.records_nt : lookup_bytes > (128ull << 20);
+    p.records_nt = tn.records_nt >= 0 ? tn.records_nt : lookup_bytes > kBigLookup;
     p.frame_group = tn.frame_group < 1 || tn.frame_group > n_frames ? n_frames : tn.frame_group;
     p.n_queues = tn.xcd_queues ? kPlanQueues : 1;
     return p;

@@ -35,6 +35,10 @@ struct Tuning {
                              // for a larger weight (0: one atomic per positive weight; vr_weights.hip, EXPERIMENTS.md)
     int block_cull = 1;      // colour / AOV frame launches: ray generation culls the 8x8 pixel blocks that meet no
                              // occupied cell (vr_internal.h "Block cull"; 0: every block generates its rays)
+    int head_march = 1;      // colour / AOV frame launches: ray generation marches a ray's samples in front of its first
+                             // hit sample (vr_internal.h "Lead-in march"; 0: every ray is handed over at the box entry)
+    int head_min_lanes = 0;  // the wave hands its rays over once fewer lanes march (1..64); 0 = auto (plan_launch)
+    int head_max = 0;        // lead-in rounds of a wave at most; 0 = auto (plan_launch)
 };
 
 // The march kernel of a launch, and what its rays come from: the pixels of n_frames poses, or a list of rays
@@ -47,11 +51,14 @@ constexpr int kPlanQueues = 8;  // vr::kMaxQueues, one per XCD (vr_launch.cpp as
 struct LaunchPlan {
     int chunk_max, super_block, records_nt, frame_group, n_queues;  // the KParams fields of these names
     int raygen_waves;                                               // waves per ray-generation workgroup
+    int head_max, head_min_lanes;  // the lead-in march of ray generation: rounds (0 = none) and the hand-over bound
 };
 
 // n_frames: the poses of the launch (a list: its one pseudo-frame); list_rays: the rays of a list (frames:
 // not read); lookup_bytes: the tree's lookup structure, top grid plus bricks.
+// lead_in: the tree and the kernel flavour of the launch admit the lead-in march of ray generation (vr_launch.cpp
+// lead_in_applies; the plan then says whether the launch runs it).
 LaunchPlan plan_launch(LaunchKind kind, RaySource source, int n_frames, int64_t list_rays, const Tuning& tn,
-                       uint64_t lookup_bytes);
+                       uint64_t lookup_bytes, bool lead_in = false);
 
 #pragma GCC visibility pop

@@ -25,6 +25,7 @@
 #include "vr_dev_shade.h"
 #include "vr_dev_query.h"
 #include "vr_dev_rays.h"
+#include "vr_dev_march.h"
 
 namespace vr {
 
@@ -692,9 +693,13 @@ void render_kernel(const KParams p, const PLANES... planes) {
 // atomics: at 4 waves a 64-frame launch is 4 % slower, at 1 wave 35 % (profiles/r06_raygen_waves.jsonl).
 
 // (PLANES sits between two arguments and is never deduced: every use names it.)
-template <int FMA, bool FULL, int GW, typename... PLANES>
+// HEAD: the flavours with the lead-in march (vr_internal.h; FAST only).  It is a flavour and not a branch on
+// HeadParams: with the loop in the kernel, ray generation without a lead-in takes 840 us instead of 567 us per
+// 64-frame C1 launch (EXPERIMENTS.md "Lead-in march").  The flavours without it never read `head`.
+template <int FMA, bool FULL, int GW, bool HEAD, typename... PLANES>
 __global__ __launch_bounds__(kWave* GW)
-void raygen_kernel(const KParams p, const PLANES... planes, const CullParams cull) {
+void raygen_kernel(const KParams p, const PLANES... planes, const CullParams cull, const HeadParams head) {
+    static_assert(!(HEAD && FULL), "the FULL flavours count every sample in the march kernel");
     constexpr bool AOV = sizeof...(PLANES) != 0;
     const AovParams aov = aov_arg(planes...);
     const int lane = threadIdx.x & (kWave - 1);
@@ -711,6 +716,18 @@ void raygen_kernel(const KParams p, const PLANES... planes, const CullParams cul
     uint32_t xy = 0;
     int frame = 0;
     float vdir[3] = {0.f, 0.f, 1.f};
+    // The lane's ray is set up: it goes to the ray buffer, or it is composited and stored right here.
+    auto keep_or_finish = [&]() {
+        if (nr.alive) {
+            valid = true;
+        } else {
+            RayCounters z;  // a ray without a single sample (HEAD: or without one that is a hit)
+            finish_ray<FMA, FULL>(p, nr, z, px, xy, frame);
+            if constexpr (AOV) store_aov(aov, frame, xy, 0.f, 1.f);  // no hit sample: D = 0, T = 1
+        }
+    };
+    bool has = false;  // (HEAD) the lane holds a pixel of the image
+    if constexpr (HEAD) nr.alive = false;
     if (id < p.total_rays) {
         const PixelRef r = locate(p, id);
         if constexpr (!FULL) {
@@ -726,20 +743,31 @@ void raygen_kernel(const KParams p, const PLANES... planes, const CullParams cul
             px = pixel_ptr(p, p.frames[r.frame], r);
             if (culled) reset_ray(nr);
             else setup_ray<FMA>(p, r, nr, vdir);
-            if (nr.alive) {
-                valid = true;
-            } else {
-                RayCounters z;  // a ray without a single sample
-                finish_ray<FMA, FULL>(p, nr, z, px, xy, frame);
-                if constexpr (AOV) store_aov(aov, frame, xy, 0.f, 1.f);  // no sample: D = 0, T = 1
-            }
+            if constexpr (HEAD) has = true;
+            else keep_or_finish();
         }
+    }
+    // Lead-in march: the block's rays step through the empty space in front of their first hit sample here, side
+    // by side (every lane of the wave is here); a ray that ends there is no longer alive and takes the path of a
+    // ray without a sample -- finish_ray reads entered = true, light = 1: alpha = 0.
+    uint32_t head_n[kHeadStatWords] = {0u, 0u, 0u};  // (wave-uniform) rays entered, retired, samples marched
+    if constexpr (HEAD) {
+        head_n[0] = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(nr.alive));
+        if (head_n[0] != 0u)
+            head_n[2] = p.brick_blocked ? head_march<FMA, kQueryN2Blocked>(p, head, nr)
+                                        : head_march<FMA, kQueryN2>(p, head, nr);
+        head_n[1] = head_n[0] - (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(nr.alive));
+        if (has) keep_or_finish();
     }
     // compaction into the queue that owns the workgroup's blocks (vr_dev_rays.h)
     const unsigned long long m_valid = __builtin_amdgcn_ballot_w64(valid);
     __shared__ uint32_t wave_culled[GW];  // (read behind the barriers of reserve_ray_slots)
+    __shared__ uint32_t wave_head[HEAD ? GW : 1][kHeadStatWords];
     if constexpr (!FULL && GW > 1) {
         if (cull.mask && lane == 0) wave_culled[wave] = culled ? 1u : 0u;
+        if constexpr (HEAD) {
+            if (lane < kHeadStatWords) wave_head[wave][lane] = lane == 0 ? head_n[0] : lane == 1 ? head_n[1] : head_n[2];
+        }
     }
     const uint32_t my_base = reserve_ray_slots<GW>(p, m_valid, lane, wave);
     if constexpr (!FULL) {
@@ -759,6 +787,22 @@ void raygen_kernel(const KParams p, const PLANES... planes, const CullParams cul
             }
             if (n)
                 atomicAdd(cull.stats + (blockIdx.x & (uint32_t)(kCullStatLines - 1)) * kCullStatStride + threadIdx.x,
+                          (unsigned long long)n);
+        }
+    }
+    if constexpr (HEAD) {
+        // the observable (vr_tree_head_stats): the workgroup's three sums, one atomic instruction (three lanes,
+        // three words of one line; the lines are dealt over the workgroups as the cull's are)
+        if (threadIdx.x < (uint32_t)kHeadStatWords) {
+            uint32_t n = 0;
+            if constexpr (GW > 1) {
+#pragma unroll
+                for (int w = 0; w < GW; ++w) n += wave_head[w][threadIdx.x];
+            } else {
+                n = threadIdx.x == 0u ? head_n[0] : threadIdx.x == 1u ? head_n[1] : head_n[2];
+            }
+            if (n)
+                atomicAdd(head.stats + (blockIdx.x & (uint32_t)(kCullStatLines - 1)) * kCullStatStride + threadIdx.x,
                           (unsigned long long)n);
         }
     }
@@ -1065,8 +1109,9 @@ hipError_t launch_fp(const KParams& p, int64_t total_blocks, int n_cus, int wave
 // Ray generation + the persistent march of one launch (the probe overlay is launch_render's own).
 // rays: a ray list takes the place of the frames' pixels (never with AOV planes).
 template <typename... PLANES>
-hipError_t launch_march(const KParams& p, const CullParams& cull, int fp_mode, int n_cus, int waves_override,
-                        int gen_waves, hipStream_t stream, const RayList* rays, const PLANES&... planes) {
+hipError_t launch_march(const KParams& p, const CullParams& cull, const HeadParams& head, int fp_mode, int n_cus,
+                        int waves_override, int gen_waves, hipStream_t stream, const RayList* rays,
+                        const PLANES&... planes) {
     const int64_t total_blocks = p.n_wave_blocks * p.n_frames;
     {   // ray generation: gen_waves wave blocks (8x8 pixels each) per workgroup
         const bool full = needs_full(p);
@@ -1077,7 +1122,9 @@ hipError_t launch_march(const KParams& p, const CullParams& cull, int fp_mode, i
             if constexpr (sizeof...(PLANES) == 0 && GW_ >= 4)                                       \
                 hipLaunchKernelGGL((raygen_rays_kernel<FMA_, FULL_, GW_>), grid_, block_, 0, stream, p, *rays); \
         }                                                                                           \
-        else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_, PLANES...>), grid_, block_, 0, stream, p, planes..., cull); \
+        else if (!FULL_ && head.max_rounds > 0)                                                     \
+            hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_, !FULL_, PLANES...>), grid_, block_, 0, stream, p, planes..., cull, head); \
+        else hipLaunchKernelGGL((raygen_kernel<FMA_, FULL_, GW_, false, PLANES...>), grid_, block_, 0, stream, p, planes..., cull, head); \
     } while (0)
 #define VR_GEN_GW(FMA_, FULL_)                                                                      \
     do {                                                                                            \
@@ -1115,10 +1162,10 @@ hipError_t launch_block_mask(const KParams& p, const MaskParams& m, hipStream_t 
     return hipGetLastError();
 }
 
-hipError_t launch_render(const KParams& p, const CullParams& cull, int fp_mode, int n_cus, int waves_override,
-                         int gen_waves, hipStream_t stream, const RayList* rays) {
+hipError_t launch_render(const KParams& p, const CullParams& cull, const HeadParams& head, int fp_mode, int n_cus,
+                         int waves_override, int gen_waves, hipStream_t stream, const RayList* rays) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    const hipError_t e = launch_march(p, cull, fp_mode, n_cus, waves_override, gen_waves, stream, rays);
+    const hipError_t e = launch_march(p, cull, head, fp_mode, n_cus, waves_override, gen_waves, stream, rays);
     if (e != hipSuccess || !p.enable_probe || p.probe_disp_size <= 0) return e;
     const int side = p.probe_disp_size + 5;
     const dim3 pgrid((unsigned)((side * side + 255) / 256), (unsigned)p.n_frames);
@@ -1135,10 +1182,10 @@ hipError_t launch_prepare_aov(const AovParams& a, const AovTable& tbl, hipStream
 }
 
 // (no probe overlay: vr_render_aov refuses enable_probe)
-hipError_t launch_render_aov(const KParams& p, const AovParams& a, const CullParams& cull, int fp_mode, int n_cus,
-                             int waves_override, int gen_waves, hipStream_t stream) {
+hipError_t launch_render_aov(const KParams& p, const AovParams& a, const CullParams& cull, const HeadParams& head,
+                             int fp_mode, int n_cus, int waves_override, int gen_waves, hipStream_t stream) {
     if (p.n_wave_blocks <= 0 || p.n_frames <= 0) return hipSuccess;
-    return launch_march(p, cull, fp_mode, n_cus, waves_override, gen_waves, stream, /* rays */ nullptr, a);
+    return launch_march(p, cull, head, fp_mode, n_cus, waves_override, gen_waves, stream, /* rays */ nullptr, a);
 }
 
 hipError_t launch_probe(const KParams& p, const float probe[3], float* out_dev,

@@ -96,6 +96,8 @@ hipError_t alloc_launch_scratch(VrTreeOpaque* t) {
     const size_t cull_sz = (size_t)vr::kCullStatLines * vr::kCullStatStride * sizeof(unsigned long long);
     if (e == hipSuccess) e = t->cull_stats.alloc(cull_sz);
     if (e == hipSuccess) e = hipMemset(t->cull_stats.get(), 0, cull_sz);
+    if (e == hipSuccess) e = t->head_stats.alloc(cull_sz);
+    if (e == hipSuccess) e = hipMemset(t->head_stats.get(), 0, cull_sz);
     if (e == hipSuccess) e = t->probe_buf.alloc(sizeof(float) * (size_t)t->desc.data_dim * kLaunchSlots);
     for (unsigned i = 0; i < kLaunchSlots && e == hipSuccess; ++i) e = t->slots[i].done.create();
     if (e == hipSuccess) e = t->slot_frames.alloc(sizeof(vr::FrameDesc) * vr::kMaxBatch * kLaunchSlots);
