@@ -350,11 +350,11 @@ int vr_tree_step(vr_tree_t tree, const VrStep* s, void* stream);
  * (apply); child_out == child; N outside what vr_tree_upload accepts (2..16); capacity < 1 or beyond INT32_MAX; n_new < 0;
  * workspace_bytes too small or a misaligned workspace; n_arrays outside 0..VR_REFINE_MAX_ARRAYS, or arrays NULL
  * when n_arrays > 0; per array elem_bytes not 2 or 4, dim < 1, an unknown fill, NULL src or dst, dst == src.
- * Not offered: merging / pruning leaves and compacting the node array (that changes the numbering and needs a
- * remap of everything indexed by slot; vr_tree_upload tolerates unreachable nodes, so a collapse without
- * compaction is the natural next step), refining the device layout of an uploaded tree without a re-upload,
- * quantised inputs, `extra` (it is not indexed by slot), and choosing what to refine: max_weight, hits and
- * grad_data are already in the file's indexing, so a threshold is the caller's one line. */
+ * Merging leaves back into their parent slot and compacting the node array is vr_collapse_plan / vr_collapse_apply
+ * below (that changes the numbering, and the calls hand out the maps).  Not offered: refining the device layout of
+ * an uploaded tree without a re-upload, quantised inputs, `extra` (it is not indexed by slot), and choosing what to
+ * refine: max_weight, hits and grad_data are already in the file's indexing, so a threshold is the caller's one
+ * line. */
 enum { VR_REFINE_COPY = 0, VR_REFINE_ZERO = 1 };
 #define VR_REFINE_MAX_ARRAYS 8
 typedef struct VrRefineArray {   /* one companion array, indexed as VrTreeDesc.data: slot * dim + e */
@@ -382,6 +382,89 @@ typedef struct VrRefine {
 int64_t vr_refine_workspace(int N, int64_t capacity);
 int vr_refine_plan(const VrRefine* r, int64_t* n_new, void* stream);
 int vr_refine_apply(const VrRefine* r, void* stream);
+/* ---- Collapsing nodes and compacting a tree, on the device ---- */
+/* The opposite direction (svox's `merge`): selected nodes all of whose slots are leaves are merged into the parent
+ * slot that links to them, and the node array is COMPACTED, so the numbering changes; the calls hand out the maps
+ * between the two numberings and carry companion arrays through them.  Conventions as vr_refine_*: no tree handle,
+ * arrays in the FILE's layout in device memory, the calling thread's current device, the caller's workspace, plan
+ * has the one host-blocking step and apply only enqueues.  With N3 = N^3, in plain integers:
+ * Which nodes collapse
+ *   - node m is a FRONTIER node iff child[m*N3 + j] == 0 for all j.
+ *   - node m is COLLAPSED iff 1 <= m < capacity, bit m & 31 of sel[m >> 5] is set and m is a frontier node.  The
+ *     selection is per NODE (a threshold of max_weight.view(capacity, N3).amax(1) is the caller's one line).
+ *   - bit 0 is ignored (the root has no slot to collapse into), and so are bits at or beyond capacity and bits of
+ *     nodes that are not frontier nodes.
+ * One level per call: a collapsed node has no links, so nothing below it exists; collapsing deeper is done by
+ * repeating the call, as svox's merge does.
+ * New numbering
+ *   - the kept nodes (not collapsed) keep their relative order: the p-th kept node in ascending old index is new
+ *     node p.  src_node[p] is the old index of new node p, node_map[src_node[p]] = p, node_map[m] = -1 for a
+ *     collapsed m.  n_keep = capacity - n_collapsed >= 1.  Unique and bit-reproducible.
+ *   - nodes that no slot links to are kept like any other: the calls do not walk the tree.
+ * New child array, for a kept node n with p = node_map[n] and slot j
+ *   - child[n*N3 + j] == 0: child_out[p*N3 + j] = 0.
+ *   - otherwise let m = n + child[n*N3 + j].  If m is collapsed: child_out[p*N3 + j] = 0; this slot is the MERGED
+ *     SLOT of m, and into_slot[m] = p*N3 + j.  Otherwise child_out[p*N3 + j] = node_map[m] - p.
+ *   - into_slot is -1 for kept nodes and for collapsed nodes nobody links to.
+ * Companion arrays, each indexed slot * dim + e as VrRefineArray is
+ *   - dst[(p*N3 + j)*dim + e] = src[(src_node[p]*N3 + j)*dim + e], moved as bits; a merged slot follows the array's
+ *     rule instead:
+ *       VR_COLLAPSE_KEEP  the bits the slot already held (after a refine with COPY: the pre-refine values);
+ *       VR_COLLAPSE_ZERO  zero bits;
+ *       VR_COLLAPSE_MEAN  per element e, the mean over the N3 slots of m: the elements of slots k = 0..N3-1 of m
+ *                         are read as floats (elem_bytes 2: binary16, 4: binary32) and summed in binary32 in
+ *                         ASCENDING k, one rounding per add, starting from the k = 0 element; the sum is divided by
+ *                         (float)N3, correctly rounded; for binary16 the result is rounded to nearest even, by the
+ *                         rule of vr_tree_update_data(VR_DATA_F32): subnormals are produced, overflow goes to
+ *                         +-inf.  A NaN result has an unspecified payload.
+ * Contract: child is a tree vr_tree_upload accepts.  A link outside [1, capacity) is never followed (no
+ * out-of-range load); it leaves that one child_out word unspecified and nothing else.  A node linked from two slots
+ * collapses into both; into_slot names one of them, and ZERO / MEAN reach that one.
+ * vr_collapse_plan forms the collapse words (sel AND frontier, bit 0 and the tail bits cleared), the popcounts of
+ * the keep words and an exclusive scan of those in the workspace, copies the total to *n_keep and waits for
+ * `stream`.  vr_collapse_apply takes the unchanged workspace of a plan of the same child and sel, and that plan's
+ * n_keep, and writes child_out, the maps that are not NULL and every dst.  Every store is bounded by the n_keep it
+ * was TOLD: a new index >= n_keep writes nothing, so a caller's mistake gives wrong contents, never an out-of-range
+ * store.  n_collapsed == 0 is legal: the outputs are copies of the inputs.
+ * The workspace: at least vr_collapse_workspace(N, capacity) bytes (-1 for arguments the calls refuse; no device
+ * call), 256-byte aligned, free again once apply's work on `stream` is done.  Of VrCollapse, plan reads child, sel,
+ * workspace, workspace_bytes, capacity and N; apply reads everything.
+ * VR_ERR_INVALID_ARGUMENT, before any device call: NULL c, child, sel, workspace or n_keep (plan) or child_out
+ * (apply); child_out == child; N outside 2..16; capacity outside [1, INT32_MAX]; n_keep outside [1, capacity]
+ * (apply); workspace_bytes too small or a misaligned workspace; n_arrays outside 0..VR_COLLAPSE_MAX_ARRAYS, or
+ * arrays NULL when n_arrays > 0; per array elem_bytes not 2 or 4, dim < 1, an unknown rule, NULL src or dst,
+ * dst == src.  VR_ERR_UNSUPPORTED: into_slot, or an array with ZERO / MEAN (they go by an into_slot of the
+ * workspace), for more than 2^31 slots.
+ * Not offered: removing whole subtrees in one call, dropping unreachable nodes, a max or sum rule (weights, hits),
+ * quantised inputs, changing the device layout of an uploaded tree without the re-upload, `extra`. */
+enum { VR_COLLAPSE_KEEP = 0, VR_COLLAPSE_ZERO = 1, VR_COLLAPSE_MEAN = 2 };
+#define VR_COLLAPSE_MAX_ARRAYS 8
+typedef struct VrCollapseArray {  /* one companion array, indexed as VrTreeDesc.data: slot * dim + e */
+    const void* src;              /* device, capacity * N^3 * dim elements */
+    void*       dst;              /* device, n_keep * N^3 * dim elements, != src */
+    int32_t elem_bytes;           /* 2 or 4: elements move as bits; MEAN reads binary16 / binary32 */
+    int32_t dim;                  /* elements per slot, >= 1 */
+    int32_t rule;                 /* what a merged slot gets: VR_COLLAPSE_KEEP / _ZERO / _MEAN */
+    int32_t reserved;
+} VrCollapseArray;
+typedef struct VrCollapse {
+    const int32_t*  child;        /* device [capacity * N^3], the file's relative offsets, 0 = leaf */
+    const uint32_t* sel;          /* device bitmap over NODES: bit m & 31 of word m >> 5, ceil(capacity / 32) words */
+    int32_t* child_out;           /* device [n_keep * N^3], != child                                     (apply) */
+    int32_t* node_map;            /* device [capacity]: new index of an old node, -1 if collapsed; or NULL (apply) */
+    int32_t* src_node;            /* device [n_keep]: old index of a new node; or NULL                    (apply) */
+    int32_t* into_slot;           /* device [capacity]: the merged slot of a collapsed node, else -1; or NULL (apply) */
+    const VrCollapseArray* arrays;  /* HOST array of n_arrays entries                                     (apply) */
+    void*   workspace;
+    int64_t workspace_bytes;
+    int64_t capacity;
+    int64_t n_keep;               /* what plan returned                                                  (apply) */
+    int32_t N;
+    int32_t n_arrays;             /* 0..VR_COLLAPSE_MAX_ARRAYS */
+} VrCollapse;
+int64_t vr_collapse_workspace(int N, int64_t capacity);
+int vr_collapse_plan(const VrCollapse* c, int64_t* n_keep, void* stream);
+int vr_collapse_apply(const VrCollapse* c, void* stream);
 
 /* ---- render ----------------------------------------------------------- */
 void vr_default_options(VrRenderOptions* opt);

@@ -32,6 +32,9 @@ ORDER_MAX_BITS, ORDER_MAX_PAYLOAD = 5, 8  # VrRayOrder.bits / .payload_dim
 REFINE_COPY, REFINE_ZERO = 0, 1  # VrRefineArray.fill
 REFINE_FILLS = {"copy": REFINE_COPY, "zero": REFINE_ZERO}
 REFINE_MAX_ARRAYS = 8
+COLLAPSE_KEEP, COLLAPSE_ZERO, COLLAPSE_MEAN = 0, 1, 2  # VrCollapseArray.rule
+COLLAPSE_RULES = {"keep": COLLAPSE_KEEP, "zero": COLLAPSE_ZERO, "mean": COLLAPSE_MEAN}
+COLLAPSE_MAX_ARRAYS = 8
 
 
 class VrTreeDesc(C.Structure):
@@ -121,6 +124,18 @@ class VrRefine(C.Structure):
                 ("capacity", C.c_int64), ("n_new", C.c_int64), ("N", C.c_int32), ("n_arrays", C.c_int32)]
 
 
+class VrCollapseArray(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("elem_bytes", C.c_int32), ("dim", C.c_int32),
+                ("rule", C.c_int32), ("reserved", C.c_int32)]
+
+
+class VrCollapse(C.Structure):
+    _fields_ = [("child", C.c_void_p), ("sel", C.c_void_p), ("child_out", C.c_void_p), ("node_map", C.c_void_p),
+                ("src_node", C.c_void_p), ("into_slot", C.c_void_p), ("arrays", C.POINTER(VrCollapseArray)),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64), ("capacity", C.c_int64),
+                ("n_keep", C.c_int64), ("N", C.c_int32), ("n_arrays", C.c_int32)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -172,6 +187,9 @@ PROTOTYPES = {
     "vr_refine_workspace": (C.c_int64, [C.c_int, C.c_int64]),
     "vr_refine_plan": (C.c_int, [C.POINTER(VrRefine), C.POINTER(C.c_int64), C.c_void_p]),
     "vr_refine_apply": (C.c_int, [C.POINTER(VrRefine), C.c_void_p]),
+    "vr_collapse_workspace": (C.c_int64, [C.c_int, C.c_int64]),
+    "vr_collapse_plan": (C.c_int, [C.POINTER(VrCollapse), C.POINTER(C.c_int64), C.c_void_p]),
+    "vr_collapse_apply": (C.c_int, [C.POINTER(VrCollapse), C.c_void_p]),
     "vr_render_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
                                  C.POINTER(VrRayOut), C.c_void_p]),
     "vr_accumulate_weights_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),

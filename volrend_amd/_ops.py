@@ -525,6 +525,94 @@ def refine(tree, sel, companions=(), stream=None) -> dict:
     return {"tree": new, "companions": outs, "src_slot": src_slot, "n_new": n_new}
 
 
+# ---- a tree with selected frontier nodes collapsed and the node array compacted (vr_collapse_plan / _apply) ----
+def collapse(tree, sel, companions=(), values="mean", stream=None) -> dict:
+    """A NEW tree in which the selected frontier nodes of ``tree`` (nodes all of whose slots are leaves) are merged
+    into the parent slot that links to them, and the node array is compacted -- vr_collapse_plan / vr_collapse_apply
+    on the tree's binary16 values (``read_data``) and its child array, then an upload of the result from device memory
+    (``N3Tree.from_device_arrays``).  No value crosses to the host.  One level per call: repeat it to collapse deeper.
+
+    ``sel``: a bool tensor of ``capacity`` elements, one per NODE, or the int32 bitmap of ceil(capacity / 32) words
+    (bit m & 31 of word m >> 5) -- e.g. ``max_weight.view(capacity, -1).amax(1) < t``.  A set bit collapses its node
+    if the node is a frontier node; bit 0 (the root) and bits of other nodes are ignored.  The kept nodes keep their
+    relative order: the p-th kept node in ascending old index is new node p.
+    ``companions``: up to 7 ``(tensor, rule)`` pairs, each tensor float16 / float32 / int32 with capacity * N^3 * k
+    elements indexed like the file's ``data`` array; the slots of kept nodes move with their node, and ``rule`` says
+    what a merged slot (the parent slot of a collapsed node) gets: "keep" (what it held), "zero", or "mean" (float16 /
+    float32 only: per element the mean over the collapsed node's N^3 slots, summed in float32 in ascending slot order).
+    ``values``: the rule for the tree's own values.  ``read_data`` reports the sigma of internal slots as +0, so
+    "keep" produces EMPTY leaves (their coefficients are what the file held); "mean", the default, is svox's merge.
+
+    Returns {"tree": the new ``N3Tree`` (same geometry, format, ``extra`` and NDC), "companions": the restated
+    tensors [n_keep, ...] in order, "node_map": int32 [capacity], the new index of an old node or -1, "src_node":
+    int32 [n_keep], the old index of a new node, "into_slot": int32 [capacity], the new slot a collapsed node went
+    into or -1, "n_keep": int}.  Host-blocking (the plan's count and the upload).  The old tree stays valid; the caller
+    frees it."""
+    _ = tree.handle
+    N3, cap = tree.N ** 3, tree.capacity
+    n_slots, words = cap * N3, (cap + 31) // 32
+    companions = [tuple(p) if isinstance(p, (tuple, list)) else (p,) for p in companions]
+    if len(companions) + 1 > _abi.COLLAPSE_MAX_ARRAYS:
+        raise ValueError(f"at most {_abi.COLLAPSE_MAX_ARRAYS - 1} companions, not {len(companions)}")
+    if values not in _abi.COLLAPSE_RULES:
+        raise ValueError(f"values names 'keep', 'zero' or 'mean', not {values!r}")
+    packed = str(getattr(sel, "dtype", "")).replace("torch.", "") == "bool"
+    bufs = [Buf("sel", sel, ("bool",), None, (cap, f"capacity = {cap} flags")) if packed else
+            Buf("sel", sel, (I32,), None, (words, f"ceil(capacity / 32) = {words} words"))]
+    dims = []
+    for i, p in enumerate(companions):
+        if len(p) != 2 or p[1] not in _abi.COLLAPSE_RULES:
+            raise ValueError(f"companions[{i}] must be (tensor, 'keep', 'zero' or 'mean')")
+        count = int(np.prod(_shape_of(p[0]), dtype=np.int64)) if hasattr(p[0], "shape") or hasattr(
+            p[0], "__cuda_array_interface__") else 0
+        if count < n_slots or count % n_slots:
+            raise ValueError(f"companions[{i}] must have capacity * N^3 * k = {n_slots} * k elements, not {count}")
+        dims.append(count // n_slots)
+        bufs.append(Buf(f"companions[{i}]", p[0], (F16, F32) if p[1] == "mean" else (F16, F32, I32)))
+    c = check(tree, bufs)
+    import torch
+    from ._tree import N3Tree
+    device = torch.device("cuda", c.device_index())
+    L, sp = _abi.lib(), _stream_ptr(stream)
+    with torch.cuda.device(device):
+        if packed:
+            sel = _pack_bits(sel)
+            torch.cuda.current_stream(device).synchronize()   # (torch's stream need not be ``stream``)
+        data = read_data(tree, stream=stream)
+        child = torch.from_numpy(np.ascontiguousarray(tree.child_, dtype=np.int32)).to(device)
+        ws = torch.empty(int(L.vr_collapse_workspace(tree.N, cap)), dtype=torch.uint8, device=device)
+        r = _abi.VrCollapse()
+        r.child, r.sel = child.data_ptr(), int(sel.data_ptr()) if packed else c.ptr["sel"]
+        r.workspace, r.workspace_bytes = ws.data_ptr(), ws.numel()
+        r.capacity, r.N = cap, tree.N
+        n_keep = C.c_int64(0)
+        _abi.check(L.vr_collapse_plan(C.byref(r), C.byref(n_keep), sp))
+        n_keep = int(n_keep.value)
+        node = (n_keep, tree.N, tree.N, tree.N)
+        child_out = torch.empty(node, dtype=torch.int32, device=device)
+        node_map, into_slot = (torch.empty(cap, dtype=torch.int32, device=device) for _ in range(2))
+        src_node = torch.empty(n_keep, dtype=torch.int32, device=device)
+        data_out = torch.empty(node + (tree.data_dim,), dtype=torch.float16, device=device)
+        outs = [torch.empty(node + ((k,) if k > 1 else ()), dtype=getattr(torch, c.dtype[f"companions[{i}]"]),
+                            device=device) for i, k in enumerate(dims)]
+        arrays = (_abi.VrCollapseArray * (len(outs) + 1))()
+        srcs = [data.data_ptr()] + [c.ptr[f"companions[{i}]"] for i in range(len(companions))]
+        for a, src, dst, k, rule in zip(arrays, srcs, [data_out] + outs, [tree.data_dim] + dims,
+                                        [values] + [p[1] for p in companions]):
+            a.src, a.dst, a.elem_bytes, a.dim, a.rule = src, dst.data_ptr(), dst.element_size(), k, \
+                _abi.COLLAPSE_RULES[rule]
+        r.child_out, r.node_map, r.src_node, r.into_slot = (x.data_ptr() for x in (child_out, node_map, src_node,
+                                                                                    into_slot))
+        r.n_keep, r.arrays, r.n_arrays = n_keep, arrays, len(arrays)
+        _abi.check(L.vr_collapse_apply(C.byref(r), sp))
+        _abi.check(L.vr_stream_sync(sp))   # (the upload reads the arrays on streams of its own)
+        new = N3Tree.from_device_arrays(child_out, data_out, tree.offset, tree.scale, tree.data_format,
+                                        extra=getattr(tree, "extra_", None),
+                                        ndc=(tree.ndc_width, tree.ndc_height, tree.ndc_focal) if tree.use_ndc else None)
+    return {"tree": new, "companions": outs, "node_map": node_map, "src_node": src_node, "into_slot": into_slot,
+            "n_keep": n_keep}
+
+
 # ---- a sparse optimiser step, in place (vr_tree_step) ----
 def tree_step(tree, master, grad, touched, *, kind="sgd", lr, lr_sigma=None, m=None, v=None, betas=(0.9, 0.999),
               eps: float = 1e-8, step: int = 1, stream=None) -> None:

@@ -353,7 +353,7 @@ class N3Tree:
     render_backward_rays, touched_words = _ops.render_backward_rays, _ops.touched_words
     fit_rays, order_rays = _ops.fit_rays, _ops.order_rays
     step, update_data, read_data = _ops.tree_step, _ops.update_data, _ops.read_data
-    refine = _ops.refine
+    refine, collapse = _ops.refine, _ops.collapse
 
     def info(self) -> dict:
         i = _abi.VrTreeInfo()

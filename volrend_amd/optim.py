@@ -172,6 +172,25 @@ class SparseTreeOptimizer:
         self.touched = torch.zeros(api.touched_words(self.tree), dtype=torch.int32, device=self.master.device)
         return res["src_slot"]
 
+    def collapse(self, sel):
+        """Merges the selected frontier nodes into their parent slots and compacts the tree (``api.collapse``; ``sel``
+        is per NODE) between ``step()`` and the next ``backward`` / ``fit``: ``self.tree`` becomes the collapsed tree,
+        ``master`` is gathered into the new numbering with the MEAN of a collapsed node's slots in its merged slot,
+        ``m`` / ``v`` are gathered and zero in merged slots, ``grad`` and ``touched`` are zeros of the new size.  The
+        new tree then takes ``update_data(master)``, so that it holds binary16(master) in every slot.  Returns
+        ``node_map`` (int32 [old capacity]): the new index of an old node, -1 if it collapsed.  The old tree stays
+        valid for whoever still holds it."""
+        pairs = [(self.master, "mean")] + ([(self.m, "zero"), (self.v, "zero")] if self.kind == "adam" else [])
+        res = api.collapse(self.tree, sel, pairs, values="mean", stream=self._stream())
+        self.tree = res["tree"]
+        self.master = res["companions"][0]
+        if self.kind == "adam":
+            self.m, self.v = res["companions"][1:3]
+        self.grad = torch.zeros_like(self.master)
+        self.touched = torch.zeros(api.touched_words(self.tree), dtype=torch.int32, device=self.master.device)
+        api.update_data(self.tree, self.master, stream=self._stream())
+        return res["node_map"]
+
     def step(self) -> None:
         """The optimiser step over the marked slots; afterwards ``grad`` and ``touched`` are zero again."""
         self.steps += 1
