@@ -35,6 +35,9 @@ REFINE_MAX_ARRAYS = 8
 COLLAPSE_KEEP, COLLAPSE_ZERO, COLLAPSE_MEAN = 0, 1, 2  # VrCollapseArray.rule
 COLLAPSE_RULES = {"keep": COLLAPSE_KEEP, "zero": COLLAPSE_ZERO, "mean": COLLAPSE_MEAN}
 COLLAPSE_MAX_ARRAYS = 8
+GEOM_MAX_DEPTH, POINTS_MAX_K = 64, 64  # VR_GEOM_MAX_DEPTH / VR_POINTS_MAX_K
+POINTS_CENTER, POINTS_JITTER = 0, 1  # VrSlotPoints.mode
+POINTS_MODES = {"center": POINTS_CENTER, "jitter": POINTS_JITTER}
 
 
 class VrTreeDesc(C.Structure):
@@ -136,6 +139,17 @@ class VrCollapse(C.Structure):
                 ("n_keep", C.c_int64), ("N", C.c_int32), ("n_arrays", C.c_int32)]
 
 
+class VrGeometry(C.Structure):
+    _fields_ = [("child", C.c_void_p), ("parent_slot", C.c_void_p), ("node_depth", C.c_void_p),
+                ("node_origin", C.c_void_p), ("capacity", C.c_int64), ("N", C.c_int32), ("reserved", C.c_int32)]
+
+
+class VrSlotPoints(C.Structure):
+    _fields_ = [("node_depth", C.c_void_p), ("node_origin", C.c_void_p), ("slots", C.c_void_p),
+                ("points", C.c_void_p), ("depth", C.c_void_p), ("side", C.c_void_p), ("capacity", C.c_int64),
+                ("n", C.c_int64), ("N", C.c_int32), ("k", C.c_int32), ("mode", C.c_int32), ("seed", C.c_uint32)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -190,6 +204,8 @@ PROTOTYPES = {
     "vr_collapse_workspace": (C.c_int64, [C.c_int, C.c_int64]),
     "vr_collapse_plan": (C.c_int, [C.POINTER(VrCollapse), C.POINTER(C.c_int64), C.c_void_p]),
     "vr_collapse_apply": (C.c_int, [C.POINTER(VrCollapse), C.c_void_p]),
+    "vr_tree_geometry": (C.c_int, [C.POINTER(VrGeometry), C.c_void_p]),
+    "vr_slot_points": (C.c_int, [C.POINTER(VrSlotPoints), C.c_void_p]),
     "vr_render_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
                                  C.POINTER(VrRayOut), C.c_void_p]),
     "vr_accumulate_weights_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),

@@ -613,6 +613,121 @@ def collapse(tree, sel, companions=(), values="mean", stream=None) -> dict:
             "n_keep": n_keep}
 
 
+# ---- where a slot is (vr_tree_geometry / vr_slot_points) ----
+_GEOMETRY_OUT = ("parent_slot", "node_depth", "node_origin")
+
+
+def _child_on_device(tree, device):
+    """The tree's child array as an int32 tensor on ``device`` (the host copy ``child_``, as ``refine`` puts it
+    there), complete before the caller enqueues on a stream of its own."""
+    import torch
+    child = torch.from_numpy(np.ascontiguousarray(tree.child_, dtype=np.int32)).to(device)
+    torch.cuda.current_stream(device).synchronize()   # (torch's stream need not be the caller's)
+    return child
+
+
+def geometry(tree, want=_GEOMETRY_OUT, stream=None) -> dict:
+    """Where the nodes of ``tree`` are -- vr_tree_geometry on its child array, enqueued on ``stream``; in the file's
+    numbering, as everything indexed by slot (s = node * N^3 + (ix * N + iy) * N + iz).
+
+    ``want``: any of "parent_slot" int32 [capacity] (the slot that links to the node; -1 for the root and for a node
+    nothing links to), "node_depth" int32 [capacity] (links from the root, the ``depth`` of ``query_points`` for the
+    node's leaves; -1 where the chain does not reach the root within 64 links) and "node_origin" int32 [capacity, 3]:
+    the node's lower corner in the N^depth grid of its level -- the library's uint32 words modulo 2^32, as the bits
+    of an int32 tensor (torch computes with those; exact while N^depth <= 2^31, ``.view(torch.uint32)`` beyond).
+    Returns a dict of torch tensors on the tree's device; host-blocking (the child array goes up from the host copy
+    and the call waits for ``stream``; the C call only enqueues).  A slot's cell: depth ``node_depth[s // N^3]``,
+    lower corner ``(node_origin[s // N^3] * N + (ix, iy, iz)) / N^(depth + 1)`` in tree coordinates."""
+    _ = tree.handle
+    want = parse_want(want, _GEOMETRY_OUT, empty_ok=False)
+    c = check(tree, [])
+    import torch
+    device = torch.device("cuda", c.device_index())
+    cap = tree.capacity
+    with torch.cuda.device(device):
+        child = _child_on_device(tree, device)
+        res = allocate(c, {"parent_slot": (I32, (cap,)), "node_depth": (I32, (cap,)), "node_origin": (I32, (cap, 3))},
+                       {}, want, zeros=False)
+        g = _abi.VrGeometry()
+        g.child, g.capacity, g.N = child.data_ptr(), cap, tree.N
+        g.parent_slot, g.node_depth, g.node_origin = (c.ptr.get(w) for w in _GEOMETRY_OUT)
+        if g.parent_slot is None:   # the walk's links: from torch's cache, not from the device pool the C call would use
+            links = torch.empty(cap, dtype=torch.int32, device=device)
+            g.parent_slot = links.data_ptr()
+        _abi.check(_abi.lib().vr_tree_geometry(C.byref(g), _stream_ptr(stream)))
+        _abi.check(_abi.lib().vr_stream_sync(_stream_ptr(stream)))   # (the child copy is torch's to free)
+    return {w: res[w] for w in want}
+
+
+_tree_geometry = geometry   # (slot_points has a parameter of that name)
+
+
+def slot_points(tree, slots, k: int = 1, mode: str = "center", seed: int = 0, space: str = "tree", geometry=None,
+                stream=None) -> dict:
+    """``k`` points in the cell of each slot of ``slots`` [n] (int32, on the tree's device, any order, repeats
+    allowed; e.g. ``torch.nonzero(leaf & mask)``) -- vr_slot_points, one launch, enqueued on ``stream``: what svox's
+    ``tree.sample(k)`` draws, for any list of slots.
+
+    ``mode``: "center" (every point the cell's centre) or "jitter" (a hash of (slot, point, axis, ``seed``): the same
+    bits whatever the list, its order or its split into calls).  ``geometry``: the dict of ``geometry()`` with
+    "node_depth" and "node_origin" -- computed here when None.  ``space``: "tree" -- the library's bits, which
+    ``query_points(space="tree")`` takes as they are and, for N a power of two and cells of at least 2^-24, finds the
+    slot with -- or "world": ``(p - offset) / scale`` in torch, the inverse of the tree's offset + scale * x; not
+    bit-pinned, and it waits for ``stream``.
+    Returns {"points": float32 [n, k, 3], "depth": int32 [n], "side": float32 [n], the edge of the slot's cell in
+    tree coordinates}.  A slot index out of range or of a node without a depth gives NaN points, depth -1, side NaN."""
+    _ = tree.handle
+    if not isinstance(k, int) or isinstance(k, bool) or not 1 <= k <= _abi.POINTS_MAX_K:
+        raise ValueError(f"k must be an integer in 1..{_abi.POINTS_MAX_K}, not {k!r}")
+    if mode not in _abi.POINTS_MODES:
+        raise ValueError(f"mode must be 'center' or 'jitter', not {mode!r}")
+    if not isinstance(seed, int) or isinstance(seed, bool) or not 0 <= seed < 2 ** 32:
+        raise ValueError(f"seed must be an integer in 0..2^32 - 1, not {seed!r}")
+    if space not in _abi.SPACES:
+        raise ValueError(f"space must be 'world' or 'tree', not {space!r}")
+    cap = tree.capacity
+    bufs = [Buf("slots", slots, (I32,), ("n",), rows=True)]
+    if geometry is not None:
+        if not isinstance(geometry, dict) or any(w not in geometry for w in ("node_depth", "node_origin")):
+            raise ValueError("geometry must be a dict with 'node_depth' and 'node_origin' (what geometry() returns)")
+        bufs += [Buf("geometry['node_depth']", geometry["node_depth"], (I32,), (cap,)),
+                 Buf("geometry['node_origin']", geometry["node_origin"], (I32,), (cap, 3))]
+    c = check(tree, bufs)
+    res = allocate(c, {"points": (F32, ("n", k, 3)), "depth": (I32, ("n",)), "side": (F32, ("n",))}, {},
+                   ("points", "depth", "side"), zeros=False)
+    if c.n == 0:  # (empty tensors have no address to pass, and nothing would be enqueued)
+        return res
+    if geometry is None:
+        geo = _tree_geometry(tree, ("node_depth", "node_origin"), stream=stream)
+        c.ptr["geometry['node_depth']"], c.ptr["geometry['node_origin']"] = (
+            int(geo[w].data_ptr()) for w in ("node_depth", "node_origin"))
+    p = _abi.VrSlotPoints()
+    p.node_depth, p.node_origin = c.ptr["geometry['node_depth']"], c.ptr["geometry['node_origin']"]
+    p.slots, p.points, p.depth, p.side = c.ptr["slots"], c.ptr["points"], c.ptr["depth"], c.ptr["side"]
+    p.capacity, p.n, p.N, p.k, p.mode, p.seed = cap, c.n, tree.N, k, _abi.POINTS_MODES[mode], seed
+    L, sp = _abi.lib(), _stream_ptr(stream)
+    _abi.check(L.vr_slot_points(C.byref(p), sp))
+    if geometry is None or space == "world":
+        _abi.check(L.vr_stream_sync(sp))   # (the arrays made here are torch's to free; torch computes on its own stream)
+    if space == "world":
+        import torch
+        off, scale = (torch.as_tensor(np.asarray(v, np.float32), device=res["points"].device)
+                      for v in (tree.offset, tree.scale))
+        res["points"] = (res["points"] - off) / scale
+    return res
+
+
+def parent_depth(tree, stream=None):
+    """The ``parent_depth`` array svox keeps and its tree files carry: int32 [capacity, 2], row m = (the slot that
+    links to node m, the depth of node m); the root's row is (0, 0), as svox stores it.  From ``geometry()``; a torch
+    tensor on the tree's device (``synth.save_npz(..., parent_depth=...)`` writes it)."""
+    import torch
+    geo = geometry(tree, ("parent_slot", "node_depth"), stream=stream)
+    out = torch.stack([geo["parent_slot"], geo["node_depth"]], dim=1)
+    out[0, 0] = 0
+    return out
+
+
 # ---- a sparse optimiser step, in place (vr_tree_step) ----
 def tree_step(tree, master, grad, touched, *, kind="sgd", lr, lr_sigma=None, m=None, v=None, betas=(0.9, 0.999),
               eps: float = 1e-8, step: int = 1, stream=None) -> None:

@@ -354,6 +354,7 @@ class N3Tree:
     fit_rays, order_rays = _ops.fit_rays, _ops.order_rays
     step, update_data, read_data = _ops.tree_step, _ops.update_data, _ops.read_data
     refine, collapse = _ops.refine, _ops.collapse
+    geometry, slot_points, parent_depth = _ops.geometry, _ops.slot_points, _ops.parent_depth
 
     def info(self) -> dict:
         i = _abi.VrTreeInfo()

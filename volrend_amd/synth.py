@@ -259,8 +259,10 @@ def make_config_tree(name: str, **overrides) -> SynthTree:
     return t
 
 
-def save_npz(tree: SynthTree, path: str, compressed: bool = False) -> None:
-    """Write the svox/PlenOctree ``tree.npz`` layout (reference src/n3tree.cpp:228-362)."""
+def save_npz(tree: SynthTree, path: str, compressed: bool = False, parent_depth=None) -> None:
+    """Write the svox/PlenOctree ``tree.npz`` layout (reference src/n3tree.cpp:228-362).
+    ``parent_depth``: int32 [capacity, 2], what ``N3Tree.parent_depth()`` returns (svox's loader reads it); the
+    default writes zeros."""
     arrays = dict(
         data_dim=np.int64(tree.data_dim),
         data_format=np.array(tree.data_format),
@@ -269,7 +271,8 @@ def save_npz(tree: SynthTree, path: str, compressed: bool = False) -> None:
         invradius3=tree.invradius3.astype(np.float32),
         offset=tree.offset.astype(np.float32),
         # svox bookkeeping keys (ignored by the loader, dropped by compress_octree.py:62-66)
-        parent_depth=np.zeros((tree.capacity, 2), dtype=np.int32),
+        parent_depth=(np.zeros((tree.capacity, 2), dtype=np.int32) if parent_depth is None else
+                      np.asarray(parent_depth, dtype=np.int32).reshape(tree.capacity, 2)),
         n_internal=np.int32(tree.capacity),
         n_free=np.int32(0),
         depth_limit=np.int32(tree.depth),
