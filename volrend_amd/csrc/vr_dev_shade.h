@@ -227,6 +227,84 @@ __device__ __forceinline__ void add_group(const char* row, GET&& get, float* acc
     }
 }
 
+// The same sums where get() is an LDS round trip (the one-pass flavours of the render kernel: a ds_bpermute out
+// of the owner lane's registers): a group that fetches its basis values, waits and then computes spends most of its
+// time waiting, and a shade round is one dependent path per wave.  Here a group's basis values are requested one
+// group AHEAD of their use and its record words in front of the next group's permutes: LDS returns in order, so
+// the wait of a group's arithmetic counts down to the next group's permutes and leaves them in flight.  begin()
+// asks for b0 and the first group; it needs no record and may stand in front of the wait for the record DMA.
+// The operations and their association are add_group's, group order c0, 9..15, 4..8, 1..3.
+// (Not the record words one group ahead as well: 6-8 registers over the caps of SH16 and SH9 -- scratch.  Not SH9's
+// last group ahead: 2 registers over its cap.)
+template <int BASIS, int LO, int HI>
+struct AheadGroup {
+    float b[VR_MAX_BASIS];  // (LO..HI used)
+    GroupWin<BASIS, 0, LO, HI> w0;
+    GroupWin<BASIS, 1, LO, HI> w1;
+    GroupWin<BASIS, 2, LO, HI> w2;
+    template <typename GET>
+    __device__ __forceinline__ void fetch_basis(GET&& get) {
+#pragma unroll
+        for (int i = LO; i <= HI; ++i) b[i] = get(i);
+    }
+    __device__ __forceinline__ void fetch_words(const char* row) {
+        w0.load(row);
+        w1.load(row);
+        w2.load(row);
+    }
+    template <int FMA>
+    __device__ __forceinline__ void add(float* acc) const {
+        acc[0] += DotGroup<FMA, 0 * BASIS, LO, HI>::run(b, w0);
+        acc[1] += DotGroup<FMA, 1 * BASIS, LO, HI>::run(b, w1);
+        acc[2] += DotGroup<FMA, 2 * BASIS, LO, HI>::run(b, w2);
+    }
+};
+
+template <int FMA, int BASIS>
+struct SumsAhead {
+    static_assert(BASIS == 4 || BASIS == 9 || BASIS == 16, "the one-pass record sizes");
+    AheadGroup<BASIS, 0, 0> g0;
+    AheadGroup<BASIS, 9, 15> ga;
+    AheadGroup<BASIS, 4, 8> gb;
+    AheadGroup<BASIS, 1, 3> gc;
+    // Nothing crosses: the scheduler, minimising registers under the flavour's cap, would sink every permute to its
+    // first use.
+    static __device__ __forceinline__ void fence() { __builtin_amdgcn_sched_barrier(0); }
+
+    template <typename GET>
+    __device__ __forceinline__ void begin(GET&& get) {
+        g0.fetch_basis(get);
+        if constexpr (BASIS >= 16) ga.fetch_basis(get);
+        else if constexpr (BASIS >= 9) gb.fetch_basis(get);
+        else gc.fetch_basis(get);
+        fence();
+    }
+    template <typename GET>
+    __device__ __forceinline__ void finish(const char* row, GET&& get, float* acc) {
+        g0.fetch_words(row);
+        fence();
+        acc[0] = coef_mul<0 * BASIS>(g0.b[0], g0.w0);
+        acc[1] = coef_mul<1 * BASIS>(g0.b[0], g0.w1);
+        acc[2] = coef_mul<2 * BASIS>(g0.b[0], g0.w2);
+        if constexpr (BASIS >= 16) {
+            ga.fetch_words(row);
+            gb.fetch_basis(get);
+            fence();
+            ga.template add<FMA>(acc);
+        }
+        if constexpr (BASIS >= 9) {
+            gb.fetch_words(row);
+            if constexpr (BASIS >= 16) gc.fetch_basis(get);
+            fence();
+            gb.template add<FMA>(acc);
+            if constexpr (BASIS < 16) gc.fetch_basis(get);
+        }
+        gc.fetch_words(row);
+        fence();
+        gc.template add<FMA>(acc);
+    }
+};
+
 template <int FMA, int BASIS, bool FENCE = false, typename GET>
 __device__ __forceinline__ void channel_sums(const char* row, GET&& get, float* acc) {
     static_assert(BASIS > 1, "SH / SG / ASG sizes only");

@@ -308,9 +308,9 @@ void render_kernel(const KParams p, const PLANES... planes) {
         auto basis_of = [&](int i) -> float {
             return u2f((uint32_t)__builtin_amdgcn_ds_bpermute(own4, (int)f2u(mybasis[i])));
         };
-        // One-pass flavours fetch each group of basis values right where the (whole) wave uses
-        // it; the two-pass flavour (SH25) computes with half the wave at a time, so it gathers
-        // everything up front while every owner lane is still active.
+        // One-pass flavours fetch each group of basis values one group ahead of where the (whole) wave
+        // uses it (SumsAhead); the two-pass flavour (SH25) computes with half the wave at a time, so it
+        // gathers everything up front while every owner lane is still active.
         float bfull[ST::kPasses > 1 ? NB : 1];
         if constexpr (ST::kPasses > 1) {
 #pragma unroll
@@ -336,13 +336,18 @@ void render_kernel(const KParams p, const PLANES... planes) {
                         issue_records<BASIS, true>(p, stage, it_leaf, ring_head, lane, n, pass);
                     else
                         issue_records<BASIS, false>(p, stage, it_leaf, ring_head, lane, n, pass);
+                    // (one pass: the owner's first basis values -- b0 and the first group, vr_dev_shade.h SumsAhead
+                    // -- are requested here, in front of the wait: their LDS round trips run under the DMA's)
+                    SumsAhead<FMA, ST::kPasses == 1 ? BASIS : 16> sums;
+                    if constexpr (ST::kPasses == 1) sums.begin(basis_get);
                     __syncthreads();  // the DMAs have landed (vmcnt(0)) and are visible
                     // (one pass: ALL lanes run the arithmetic -- an owner lane without an item
                     // of its own must stay active for the permutes; only `have` lanes keep results)
                     if (ST::kPasses == 1 || lane / ST::kPass == pass) {
                         const char* row = stage + (lane % ST::kPass) * ST::kRow;
                         float acc[3];
-                        channel_sums<FMA, BASIS>(row, basis_get, acc);
+                        if constexpr (ST::kPasses == 1) sums.finish(row, basis_get, acc);
+                        else channel_sums<FMA, BASIS>(row, basis_get, acc);
                         // rt_core.cuh:161: weight / (1 + expf(-tmp)) per channel
                         // (the sigmoids of channels 0 / 1 share packed mul / fma / add instructions)
                         const float2v s01 = weighted_sigmoid2(weight, acc[0], acc[1]);
