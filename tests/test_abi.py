@@ -219,3 +219,13 @@ def test_no_kernel_source_is_compiled_through_an_include():
         text = open(os.path.join(csrc, f), errors="replace").read()
         assert not re.search(r"^\s*#\s*include\s*[\"<][^\">]*\.hip[\">]", text, flags=re.M), f
         assert "VR_KERNEL_PASS" not in text, f
+
+
+def test_refusals_and_last_error_from_eight_threads(lib_path, tmp_path):
+    """tests/cpp/threads_check.cpp `errors` (built without HIP: it opens no device): 8 threads each make 2000 calls
+    that are refused before any tree is followed -- vr_tree_upload with N < 2, with capacity 0 or with an unknown
+    format, vr_reserve_rays(NULL) -- thread i kind i % 4 with a parameter of its own in the message.  After each
+    call the thread holds the return code and the text of vr_last_error() to what its own refusal gave when made
+    alone at start-up: the message buffer is the calling thread's."""
+    got = build_util.run_key_values(build_util.cpp_program("threads_check", tmp_path), "errors")
+    assert got == {"calls": "16000"}

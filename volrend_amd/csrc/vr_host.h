@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <condition_variable>
 #include <mutex>
 #include <vector>
 
@@ -51,7 +52,7 @@ struct LaunchSlot {
     DeviceEvent done;
     bool used = false;          // `done` has been recorded at least once
     hipStream_t last_stream = nullptr;  // the stream of that launch
-    bool growing = false;       // its ray buffer is being reallocated outside the launch mutex: skip it
+    bool growing = false;       // its ray buffer is being reallocated outside the launch mutex: skip it (all growing: wait)
     DeviceBuffer rays;          // ray buffer, grown on demand (or up front by vr_reserve)
 };
 
@@ -90,6 +91,7 @@ struct VrTreeOpaque : TreeShape {
     LaunchSlot slots[kLaunchSlots];
     unsigned launch_seq = 0;
     std::mutex launch_mutex;  // slot bookkeeping + enqueue order of one launch; guards `tn`
+    std::condition_variable slot_grown;  // a slot stopped `growing`: a launch that found all of them growing chooses again
     Tuning tn;                // this tree's knobs (vr_tree_set_tuning)
     int n_cus = 256;
 };
@@ -127,7 +129,8 @@ hipError_t refresh_occupancy(const VrTreeOpaque* t, hipStream_t hs);
 
 // Launch slot: per-launch scratch in device memory (ring, see LaunchSlot).  Picks the slot of this
 // launch, points `k` at its scratch and makes its ray buffer large enough (`need` bytes).  `guard` holds the
-// launch mutex on entry and on return, and is dropped in between while a slot grows.  (vr_slots.cpp)
+// launch mutex on entry and on return, and is dropped in between while a slot grows -- this launch's, or, when every
+// slot is growing under another thread, until one of them is done: the launch waits, it is not refused.  (vr_slots.cpp)
 int acquire_slot(VrTreeOpaque* t, std::unique_lock<std::mutex>& guard, hipStream_t hs, vr::KParams& k,
                  size_t need, unsigned& slot);
 

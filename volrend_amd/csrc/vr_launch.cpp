@@ -279,8 +279,9 @@ struct Turn { const vr::KParams& k; const Tuning& tn; const LaunchPlan& plan; in
 //   * The launch mutex covers slot bookkeeping and the enqueue order of one launch, and everything that other
 //     calls change under it: the knobs (vr_tree_set_tuning), the touch bitmaps (vr_touch_enable / vr_touch_count
 //     (re)allocate them), the tables made on first use.  It is dropped ONCE, inside acquire_slot, while a slot
-//     grows: so the launch goes by a copy of the knobs, and the tree's part of `k` is filled after acquire_slot
-//     has returned -- from there to the last kernel launch the mutex is held.
+//     grows (or while the launch waits for one, all of them growing): so the launch goes by a copy of the
+//     knobs, and the tree's part of `k` is filled after acquire_slot has returned -- from there to the last
+//     kernel launch the mutex is held.
 //   * The file-order table is made before anything else (the call's one host-blocking step), also by a warm-up
 //     call -- no frames, or an empty list -- which launches nothing.
 template <typename Enqueue>

@@ -44,26 +44,33 @@ size_t colour_record_bytes(const VrTreeOpaque* t, uint32_t total_rays) {
 
 int acquire_slot(VrTreeOpaque* t, std::unique_lock<std::mutex>& guard, hipStream_t hs, vr::KParams& k,
                  size_t need, unsigned& slot) {
-    slot = kLaunchSlots;
-    for (int want_fit = 1; want_fit >= 0 && slot == kLaunchSlots; --want_fit) {
-        for (int pass = 0; pass < 2 && slot == kLaunchSlots; ++pass)
-            for (unsigned i = 0; i < kLaunchSlots; ++i) {
-                const LaunchSlot& c = t->slots[i];
-                if (c.growing || (want_fit && c.rays.bytes() < need)) continue;
-                const bool ok = pass == 0 ? (c.used && c.last_stream == hs)
-                                          : (!c.used || hipEventQuery(c.done.get()) == hipSuccess);
-                if (ok) {
-                    slot = i;
-                    break;
+    for (;;) {
+        slot = kLaunchSlots;
+        for (int want_fit = 1; want_fit >= 0 && slot == kLaunchSlots; --want_fit) {
+            for (int pass = 0; pass < 2 && slot == kLaunchSlots; ++pass)
+                for (unsigned i = 0; i < kLaunchSlots; ++i) {
+                    const LaunchSlot& c = t->slots[i];
+                    if (c.growing || (want_fit && c.rays.bytes() < need)) continue;
+                    const bool ok = pass == 0 ? (c.used && c.last_stream == hs)
+                                              : (!c.used || hipEventQuery(c.done.get()) == hipSuccess);
+                    if (ok) {
+                        slot = i;
+                        break;
+                    }
                 }
-            }
-    }
-    (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is an answer, not an error
-    if (slot == kLaunchSlots) {  // all busy elsewhere: queue up behind one (not one that is growing)
+        }
+        (void)hipGetLastError();  // hipEventQuery's hipErrorNotReady is an answer, not an error
+        // all busy elsewhere: queue up behind one (not one that is growing)
         for (unsigned a = 0; a < kLaunchSlots && slot == kLaunchSlots; ++a)
             if (!t->slots[(t->launch_seq + a) % kLaunchSlots].growing) slot = (t->launch_seq + a) % kLaunchSlots;
-        if (slot == kLaunchSlots)
-            return fail(VR_ERR_HIP, "all %u launch slots are being resized by other threads", kLaunchSlots);
+        if (slot != kLaunchSlots) break;
+        // Every slot is being resized by another thread: wait (the mutex is dropped meanwhile) until one of
+        // them is done, then choose again by the same rules.
+        t->slot_grown.wait(guard, [t] {
+            for (const LaunchSlot& c : t->slots)
+                if (!c.growing) return true;
+            return false;
+        });
     }
     t->launch_seq++;
     LaunchSlot& ls = t->slots[slot];
@@ -82,6 +89,7 @@ int acquire_slot(VrTreeOpaque* t, std::unique_lock<std::mutex>& guard, hipStream
         const hipError_t ge = replace_ray_buffer(ls, need);
         guard.lock();
         ls.growing = false;
+        t->slot_grown.notify_all();  // (success or failure: the slot can be picked again)
         if (ge != hipSuccess)
             return fail(hip_code(ge), "ray buffer of %zu bytes: %s", need, hipGetErrorString(ge));
     }
