@@ -10,7 +10,7 @@ ROCM ?= /opt/rocm
 PKG = volrend_amd
 HOST = $(PKG)/csrc/host
 HOST_SRC = $(HOST)/npz.cpp $(HOST)/n3tree.cpp $(HOST)/camera.cpp $(HOST)/opts.cpp \
-           $(HOST)/imwrite.cpp $(HOST)/renderer.cpp $(HOST)/query.cpp $(HOST)/update.cpp $(HOST)/step.cpp $(HOST)/refine.cpp $(HOST)/collapse.cpp $(HOST)/geometry.cpp $(HOST)/tile_shard.cpp \
+           $(HOST)/imwrite.cpp $(HOST)/renderer.cpp $(HOST)/query.cpp $(HOST)/update.cpp $(HOST)/step.cpp $(HOST)/refine.cpp $(HOST)/collapse.cpp $(HOST)/geometry.cpp $(HOST)/quantize.cpp $(HOST)/tile_shard.cpp \
            $(HOST)/volume_renderer.cpp
 HOST_OBJ = $(HOST_SRC:.cpp=.o)
 CXXFLAGS = -O2 -std=c++17 -fPIC -Wall -Wextra -Iinclude

@@ -539,6 +539,62 @@ typedef struct VrSlotPoints {
 int vr_tree_geometry(const VrGeometry* g, void* stream);
 int vr_slot_points(const VrSlotPoints* p, void* stream);
 
+/* ---- quantise a tree on the device ------------------------------------- *
+ * vr_quantize is the encoder of the format vr_tree_upload_quantized / vr_decode_quantized read: the median cut of
+ * scripts/compress_octree.py (unweighted), per basis function, on a data array in the FILE's layout in device memory.
+ * The four outputs are exactly the arrays of VrQuantDesc with n_quant = n_basis - n_retained.  Conventions as
+ * vr_decode_quantized and vr_refine_*: no tree handle, the calling thread's current device, the workspace is the
+ * caller's (vr_quantize_workspace bytes, 256-byte aligned, free again once the work on `stream` is done).  The call
+ * ONLY ENQUEUES on `stream`: it has no host-blocking step.
+ * Basis function j, channel c of slot s is data[s * data_dim + j + c * n_basis]; sigma_s is data[s * data_dim +
+ * data_dim - 1].  The definition, which the result meets bit for bit:
+ *   - Kept slots.  Slot s is kept iff (float)sigma_s > sigma_thresh.  A NaN sigma is not kept.  Internal slots take
+ *     part, as they do in the reference script.
+ *   - sigma[s] = the bits of sigma_s if kept, else +0.
+ *   - data_retained[r][s][c] = the bits of basis r, channel c if kept, else +0.
+ *   - quant_map[j][s] = 0 for a slot that is not kept.
+ *   - Median cut, per quantised basis function b = n_retained + j, independently.  The points are p_s = (R, G, B) of
+ *     b over the kept slots.  All points start in box 0.  For every level l = 0 .. bits-1 and every non-empty box
+ *     k < 2^l with n points: per axis, the range is max - min of the box's values, computed in binary64 (exact for
+ *     binary16 inputs); the split axis is the one with the largest range, ties to the lowest axis; the points are
+ *     ordered by their value on that axis in the total order of the binary16 bit patterns (sign-magnitude, so -0
+ *     comes before +0), ties by ASCENDING SLOT INDEX; the first ceil(n/2) points go to box 2k, the rest to box 2k+1.
+ *     A box is always split, even when all its points are equal.  After the last level quant_map[j][s] = the box of
+ *     p_s, which is below 2^bits.
+ *   - Codebook.  Per box k with cnt > 0 points and per channel: S = the exact sum of the values as int64 multiples of
+ *     2^-24 (every finite binary16 is one; integer adds make the sum independent of order); quant_colors[j][k][c] =
+ *     ((double)S / (double)cnt) * 2^-24, converted to binary32 to nearest even, then to binary16 to nearest even.
+ *     Rows of empty boxes, and rows at or beyond 2^bits, are zero bits.
+ *   - Every element of all four outputs is written by the call.
+ * Consequences: an entry lies within [min, max] of its box on every axis; if at most 2^bits slots are kept, every box
+ * holds at most one point and decoding returns each kept value exactly, as a value (a -0 comes back as +0).
+ * Contract on values: the coefficients of kept slots are finite and the sum of |x| within any box is below 2^39
+ * (true for 2^23 points of any finite binary16 values).  Outside it the codebook and map of that basis function are
+ * unspecified; every code is still below 2^bits and nothing is stored out of range.
+ * The result is unique and bit-reproducible: it does not depend on the stream, the workspace contents, or repeats.
+ * VR_ERR_INVALID_ARGUMENT, before any device call: NULL q, data, quant_colors, quant_map, sigma or workspace;
+ * data_retained present while n_retained == 0, or absent while it is not; n_slots outside [1, 2^31); data_dim < 4 or
+ * (data_dim - 1) % 3 != 0; n_retained outside 0 .. n_basis - 1; bits outside 1..16; a NaN sigma_thresh; a workspace
+ * smaller than vr_quantize_workspace says or not 256-byte aligned; an output equal to `data`.  Nothing is
+ * VR_ERR_UNSUPPORTED.
+ * Not offered: the script's --weighted cut; deflate (the caller's file writer compresses); `extra`; quantising an
+ * uploaded tree's device layout in place (the caller does vr_tree_read_data -> vr_quantize). */
+typedef struct VrQuantize {
+    const uint16_t* data;          /* device [n_slots][data_dim] binary16, file layout (VrTreeDesc.data) */
+    uint16_t* quant_colors;        /* device [n_quant][65536][3] binary16 */
+    uint16_t* quant_map;           /* device [n_quant][n_slots] */
+    uint16_t* sigma;               /* device [n_slots] binary16 */
+    uint16_t* data_retained;       /* device [n_retained][n_slots][3]; NULL iff n_retained == 0 */
+    void*   workspace; int64_t workspace_bytes;
+    int64_t n_slots;               /* capacity * N^3, 1 .. 2^31-1 */
+    int32_t data_dim;              /* (data_dim - 1) % 3 == 0; n_basis = (data_dim - 1) / 3 */
+    int32_t n_retained;            /* 0 .. n_basis - 1; n_quant = n_basis - n_retained >= 1 */
+    int32_t bits;                  /* 1..16 */
+    float   sigma_thresh;          /* not NaN */
+} VrQuantize;
+int64_t vr_quantize_workspace(int64_t n_slots, int data_dim);   /* -1 for refused arguments; no device call */
+int vr_quantize(const VrQuantize* q, void* stream);
+
 /* ---- render ----------------------------------------------------------- */
 void vr_default_options(VrRenderOptions* opt);
 void vr_default_frame(VrFrame* frame);

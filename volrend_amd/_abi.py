@@ -38,6 +38,7 @@ COLLAPSE_MAX_ARRAYS = 8
 GEOM_MAX_DEPTH, POINTS_MAX_K = 64, 64  # VR_GEOM_MAX_DEPTH / VR_POINTS_MAX_K
 POINTS_CENTER, POINTS_JITTER = 0, 1  # VrSlotPoints.mode
 POINTS_MODES = {"center": POINTS_CENTER, "jitter": POINTS_JITTER}
+QUANT_MAX_BITS, QUANT_ROWS = 16, 65536  # VrQuantize.bits; the rows of one codebook
 
 
 class VrTreeDesc(C.Structure):
@@ -150,6 +151,13 @@ class VrSlotPoints(C.Structure):
                 ("n", C.c_int64), ("N", C.c_int32), ("k", C.c_int32), ("mode", C.c_int32), ("seed", C.c_uint32)]
 
 
+class VrQuantize(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("quant_colors", C.c_void_p), ("quant_map", C.c_void_p), ("sigma", C.c_void_p),
+                ("data_retained", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64),
+                ("n_slots", C.c_int64), ("data_dim", C.c_int32), ("n_retained", C.c_int32), ("bits", C.c_int32),
+                ("sigma_thresh", C.c_float)]
+
+
 class VrQueryOut(C.Structure):
     _fields_ = [("sigma", C.c_void_p), ("depth", C.c_void_p), ("local", C.c_void_p),
                 ("coeffs", C.c_void_p), ("rgb", C.c_void_p)]
@@ -206,6 +214,8 @@ PROTOTYPES = {
     "vr_collapse_apply": (C.c_int, [C.POINTER(VrCollapse), C.c_void_p]),
     "vr_tree_geometry": (C.c_int, [C.POINTER(VrGeometry), C.c_void_p]),
     "vr_slot_points": (C.c_int, [C.POINTER(VrSlotPoints), C.c_void_p]),
+    "vr_quantize_workspace": (C.c_int64, [C.c_int64, C.c_int]),
+    "vr_quantize": (C.c_int, [C.POINTER(VrQuantize), C.c_void_p]),
     "vr_render_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions), C.c_int,
                                  C.POINTER(VrRayOut), C.c_void_p]),
     "vr_accumulate_weights_rays": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(VrRays), C.POINTER(VrRenderOptions),

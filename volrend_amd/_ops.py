@@ -728,6 +728,87 @@ def parent_depth(tree, stream=None):
     return out
 
 
+# ---- the median-cut encoder of the compressed file format (vr_quantize) ----
+class _DeviceOf:
+    """Stands where ``_args.check`` asks a tree for its device, for a data array that is no tree's: the device the
+    array is on."""
+
+    def __init__(self, x):
+        self._x = x
+
+    def info(self) -> dict:
+        index = getattr(getattr(self._x, "device", None), "index", None)
+        return {"device": 0 if index is None else int(index)}
+
+
+def _quantize_args(data_dim, bits, retain, sigma_thresh) -> None:
+    """What vr_quantize refuses of its scalars, as ValueErrors before any C call."""
+    if not isinstance(data_dim, int) or data_dim < 4 or (data_dim - 1) % 3:
+        raise ValueError(f"data_dim must be 3 * n_basis + 1 with n_basis >= 1, not {data_dim!r}")
+    if not isinstance(bits, int) or isinstance(bits, bool) or not 1 <= bits <= _abi.QUANT_MAX_BITS:
+        raise ValueError(f"bits must be an integer in 1..{_abi.QUANT_MAX_BITS}, not {bits!r}")
+    n_basis = (data_dim - 1) // 3
+    if not isinstance(retain, int) or isinstance(retain, bool) or not 0 <= retain <= n_basis - 1:
+        raise ValueError(f"retain must be an integer in 0..n_basis - 1 = {n_basis - 1}, not {retain!r}")
+    if isinstance(sigma_thresh, bool) or not isinstance(sigma_thresh, (int, float)) or sigma_thresh != sigma_thresh:
+        raise ValueError(f"sigma_thresh must be a number and not NaN, not {sigma_thresh!r}")
+
+
+def quantize(tree_or_data, *, bits: int = 16, retain: int = 1, sigma_thresh: float = 2.0, stream=None) -> dict:
+    """The median-cut compression of scripts/compress_octree.py (unweighted; its defaults), on the device --
+    vr_quantize, enqueued on ``stream``.  ``tree_or_data``: an uploaded tree, whose current values are read with
+    ``read_data``, or a float16 tensor [..., data_dim] in the file's layout on the device.
+
+    Slots with ``sigma > sigma_thresh`` are kept; per basis function beyond the first ``retain`` the (R, G, B) of the
+    kept slots are cut ``bits`` times at the median of their widest axis and every box is replaced by its mean (the
+    definition, exact to the bit, is in include/volrend_hip.h).  Returns {"quant_colors": float16 [n_quant, 65536, 3],
+    "quant_map": int16 [n_quant, n_slots] (the library's uint16 codes as the bits of an int16 tensor: ``.cpu().numpy()
+    .view(numpy.uint16)``), "sigma": float16 [n_slots], "data_retained": float16 [retain, n_slots, 3] or None}: the
+    arrays of a VrQuantDesc, which ``N3Tree.save(quantize=...)`` writes.  Host-blocking: waits for ``stream`` (the
+    workspace is torch's to free; the C call only enqueues)."""
+    if hasattr(tree_or_data, "handle") or not hasattr(tree_or_data, "shape"):
+        tree = tree_or_data
+        _ = tree.handle
+        _quantize_args(tree.data_dim, bits, retain, sigma_thresh)
+        data = read_data(tree, stream=stream)
+        owner, data_dim = tree, tree.data_dim
+    else:
+        data = tree_or_data
+        shape = tuple(data.shape)
+        data_dim = int(shape[-1]) if shape else 0
+        _quantize_args(data_dim, bits, retain, sigma_thresh)
+        owner = _DeviceOf(data)
+    n_slots = 1
+    for d in tuple(data.shape)[:-1]:
+        n_slots *= int(d)
+    if n_slots < 1 or n_slots >= 2 ** 31:
+        raise ValueError(f"data must have between 1 and 2^31 - 1 slots, not {n_slots}")
+    c = check(owner, [Buf("data", data, (F16,), tuple(data.shape))])
+    n_quant = (data_dim - 1) // 3 - retain
+    import torch
+    device = torch.device("cuda", c.device_index())
+    L = _abi.lib()
+    need = int(L.vr_quantize_workspace(n_slots, data_dim))
+    res = {"quant_colors": torch.empty((n_quant, _abi.QUANT_ROWS, 3), dtype=torch.float16, device=device),
+           "quant_map": torch.empty((n_quant, n_slots), dtype=torch.int16, device=device),
+           "sigma": torch.empty((n_slots,), dtype=torch.float16, device=device),
+           "data_retained": torch.empty((retain, n_slots, 3), dtype=torch.float16, device=device) if retain else None}
+    work = torch.empty((need + 256,), dtype=torch.uint8, device=device)
+    q = _abi.VrQuantize()
+    q.data = c.ptr["data"]
+    q.quant_colors, q.quant_map, q.sigma = (int(res[k].data_ptr()) for k in ("quant_colors", "quant_map", "sigma"))
+    q.data_retained = int(res["data_retained"].data_ptr()) if retain else None
+    q.workspace = (int(work.data_ptr()) + 255) // 256 * 256
+    q.workspace_bytes = need
+    q.n_slots, q.data_dim, q.n_retained, q.bits, q.sigma_thresh = n_slots, data_dim, retain, bits, float(sigma_thresh)
+    sp = _stream_ptr(stream)
+    with torch.cuda.device(device):
+        torch.cuda.current_stream(device).synchronize()   # (torch's allocations are its stream's; ours may differ)
+        _abi.check(L.vr_quantize(C.byref(q), sp))
+        _abi.check(L.vr_stream_sync(sp))
+    return res
+
+
 # ---- a sparse optimiser step, in place (vr_tree_step) ----
 def tree_step(tree, master, grad, touched, *, kind="sgd", lr, lr_sigma=None, m=None, v=None, betas=(0.9, 0.999),
               eps: float = 1e-8, step: int = 1, stream=None) -> None:

@@ -355,6 +355,53 @@ class N3Tree:
     step, update_data, read_data = _ops.tree_step, _ops.update_data, _ops.read_data
     refine, collapse = _ops.refine, _ops.collapse
     geometry, slot_points, parent_depth = _ops.geometry, _ops.slot_points, _ops.parent_depth
+    quantize = _ops.quantize
+
+    def save(self, path: str, quantize=None, *, from_device: bool = False) -> None:
+        """Writes the tree as a ``tree.npz`` that ``open`` and the reference's ``load_npz`` read: ``child``,
+        ``offset``, ``invradius3``, ``data_dim``, ``data_format``, ``extra_data`` when the tree has one and svox's
+        ``parent_depth``; deflated (``numpy.savez_compressed``).
+
+        ``quantize=None`` writes ``data``: the host array, or -- where ``data_`` is None (a device-built tree,
+        ``clear_cpu_memory``, a quantised upload) or ``from_device`` is set (the host array is stale after
+        ``step`` / ``update_data``) -- the device's values through ``read_data``.
+        ``quantize=dict(bits=, retain=, sigma_thresh=)`` (any subset; the defaults of ``quantize()``) writes the
+        median-cut form of scripts/compress_octree.py instead, computed on the device from the uploaded tree:
+        ``quant_colors`` [n_quant, 65536, 3], ``quant_map`` [n_quant, capacity, N, N, N], ``sigma`` [capacity, N, N, N]
+        and, with ``retain`` > 0, ``data_retained`` [retain, capacity, N, N, N, 3].  Host-blocking.  The NDC sidecar
+        (``*_poses_bounds.npy``) is not written."""
+        if not path.endswith(".npz"):
+            raise ValueError("tree file must end in .npz")
+        if quantize is not None:
+            if not isinstance(quantize, dict) or any(k not in ("bits", "retain", "sigma_thresh") for k in quantize):
+                raise ValueError("quantize must be None or a dict with any of 'bits', 'retain', 'sigma_thresh'")
+        if self.child_ is None:
+            raise RuntimeError("tree has no child array")
+        name, dim = self.data_format
+        fmt = "RGBA" if name == "RGBA" else f"{name}{dim}"
+        shape = (self.capacity, self.N, self.N, self.N)
+        arrays = dict(data_dim=np.int64(self.data_dim), data_format=np.array(fmt),
+                      child=np.ascontiguousarray(self.child_, dtype=np.int32),
+                      invradius3=np.asarray(self.scale, np.float32), offset=np.asarray(self.offset, np.float32))
+        if self.extra_ is not None:
+            arrays["extra_data"] = np.asarray(self.extra_, np.float32)
+        if quantize is not None:
+            q = _ops.quantize(self, **quantize)
+            n_quant = q["quant_map"].shape[0]
+            arrays["quant_colors"] = q["quant_colors"].cpu().numpy()
+            arrays["quant_map"] = q["quant_map"].cpu().numpy().view(np.uint16).reshape((n_quant,) + shape)
+            arrays["sigma"] = q["sigma"].cpu().numpy().reshape(shape)
+            if q["data_retained"] is not None:
+                r = q["data_retained"].cpu().numpy()
+                arrays["data_retained"] = r.reshape((r.shape[0],) + shape + (3,))
+        elif self.data_ is not None and not from_device:
+            arrays["data"] = np.ascontiguousarray(self.data_, np.float16).reshape(shape + (self.data_dim,))
+        elif self._loaded:
+            arrays["data"] = _ops.read_data(self).cpu().numpy()
+        else:
+            raise RuntimeError("tree has no data (clear_cpu_memory was called) and is not on the device")
+        arrays["parent_depth"] = (self.parent_depth().cpu().numpy() if self._loaded else _parent_depth_host(self.child_))
+        np.savez_compressed(path, **arrays)
 
     def info(self) -> dict:
         i = _abi.VrTreeInfo()
@@ -372,6 +419,30 @@ class N3Tree:
             self.free_device()
         except Exception:
             pass
+
+
+def _parent_depth_host(child) -> np.ndarray:
+    """svox's ``parent_depth`` [capacity, 2] from a host child array, for a tree that is not on the device: row m =
+    (the slot that links to node m, the depth of node m), the root's row (0, 0); (-1, -1) for a node nothing
+    reachable links to.  Breadth-first from the root."""
+    cap = child.shape[0]
+    flat = np.ascontiguousarray(child, np.int32).reshape(cap, -1)
+    N3 = flat.shape[1]
+    out = np.full((cap, 2), -1, np.int32)
+    out[0] = 0
+    frontier = np.array([0], np.int64)
+    for depth in range(1, 65):
+        links = flat[frontier]
+        node, j = np.nonzero(links)
+        if node.size == 0:
+            break
+        target = frontier[node] + links[node, j]
+        ok = (target >= 1) & (target < cap)
+        target, slot = target[ok], (frontier[node] * N3 + j)[ok]
+        fresh = out[target, 1] < 0
+        out[target[fresh], 0], out[target[fresh], 1] = slot[fresh], depth
+        frontier = np.unique(target[fresh])
+    return out
 
 
 def _quant_arrays(z, child) -> dict:

@@ -22,6 +22,6 @@ from ._frame import (CAMERA_DEFAULT_FOCAL_LENGTH, VOLREND_GLOBAL_BASIS_MAX, AovP
                      assemble_tiles, assemble_tiles_batch, compact_bytes, launch_renderer, launch_renderer_batch,
                      set_tuning)
 from ._ops import (_touched_ptr, accumulate_weights, accumulate_weights_rays, collapse, fit_rays, geometry, order_rays,  # noqa: F401
-                   parent_depth, query_grid, query_points, read_data, refine, render_backward, render_backward_rays, render_rays, slot_points, touched_words, tree_step,
+                   parent_depth, quantize, query_grid, query_points, read_data, refine, render_backward, render_backward_rays, render_rays, slot_points, touched_words, tree_step,
                    update_data)
 from ._tree import N3Tree, _decode_arrays, _decode_quantised, _quant_arrays, parse_data_format  # noqa: F401

@@ -24,10 +24,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libvolrend_hip.so")
-SOURCES = ["vr_render.hip", "vr_weights.hip", "vr_grad.hip", "vr_fit.hip", "vr_update.hip", "vr_tree_kernels.hip", "vr_query.hip", "vr_order.hip", "vr_refine.hip", "vr_collapse.hip", "vr_geometry.hip", "vr_api.cpp", "vr_upload.cpp", "vr_tree_walk.cpp",
-           "vr_h2d.cpp", "vr_launch.cpp", "vr_launch_plan.cpp", "vr_slots.cpp", "vr_values.cpp", "vr_query.cpp", "vr_order.cpp", "vr_refine.cpp", "vr_collapse.cpp", "vr_geometry.cpp"]
+SOURCES = ["vr_render.hip", "vr_weights.hip", "vr_grad.hip", "vr_fit.hip", "vr_update.hip", "vr_tree_kernels.hip", "vr_query.hip", "vr_order.hip", "vr_refine.hip", "vr_collapse.hip", "vr_geometry.hip", "vr_quantize.hip", "vr_api.cpp", "vr_upload.cpp", "vr_tree_walk.cpp",
+           "vr_h2d.cpp", "vr_launch.cpp", "vr_launch_plan.cpp", "vr_slots.cpp", "vr_values.cpp", "vr_query.cpp", "vr_order.cpp", "vr_refine.cpp", "vr_collapse.cpp", "vr_geometry.cpp", "vr_quantize.cpp"]
 HEADERS = ["vr_internal.h", "vr_device_math.h", "vr_host.h", "vr_dev_layout.h", "vr_dev_shade.h", "vr_dev_query.h",
-           "vr_dev_rays.h", "vr_dev_march.h", "vr_dev_backward.h", "vr_query.h", "vr_order.h", "vr_refine.h", "vr_collapse.h", "vr_geometry.h", "vr_tree_walk.h", "vr_launch_plan.h", "vr_h2d.h", os.path.join(ROOT, "include", "volrend_hip.h"),
+           "vr_dev_rays.h", "vr_dev_march.h", "vr_dev_backward.h", "vr_query.h", "vr_order.h", "vr_refine.h", "vr_collapse.h", "vr_geometry.h", "vr_quantize.h", "vr_tree_walk.h", "vr_launch_plan.h", "vr_h2d.h", os.path.join(ROOT, "include", "volrend_hip.h"),
            os.path.join(ROOT, "include", "volrend", "internal", "hip_owners.hpp")]
 EXPERIMENTS = os.path.join(ROOT, "tools", "experiments")
 HOOK_FLAGS = ("-DVR_ABLATE", "-DVR_TIMELINE", "-DVR_ROLE_DEBUG", "-DVR_MIN_WAVES_PER_EU", "-DVR_SH16_ROWS",

@@ -1,5 +1,5 @@
 // vr_host.h -- shared by the host sources of libvolrend_hip.so (vr_api.cpp, vr_upload.cpp, vr_launch.cpp,
-// vr_slots.cpp, vr_values.cpp, vr_query.cpp, vr_order.cpp, vr_refine.cpp, vr_collapse.cpp, vr_geometry.cpp).  Host only (not for the .hip units); nothing here is exported
+// vr_slots.cpp, vr_values.cpp, vr_query.cpp, vr_order.cpp, vr_refine.cpp, vr_collapse.cpp, vr_geometry.cpp, vr_quantize.cpp).  Host only (not for the .hip units); nothing here is exported
 // from the library.  Three host units stand beside it with headers of their own: vr_tree_walk.{h,cpp} (the walks
 // of an upload over the child array; no HIP), vr_launch_plan.{h,cpp} (struct Tuning and the scheduling rules of a
 // launch; no HIP) and vr_h2d.{h,cpp} (the upload's staged copy pipeline).

@@ -197,3 +197,10 @@ class SparseTreeOptimizer:
         api.tree_step(self.tree, self.master, self.grad, self.touched, kind=self.kind, lr=self.lr,
                       lr_sigma=self.lr_sigma, m=self.m, v=self.v, betas=self.betas, eps=self.eps, step=self.steps,
                       stream=self._stream())
+
+    def save(self, path: str, quantize=None) -> None:
+        """Writes ``self.tree`` as it stands on the device -- behind every step enqueued so far, which this waits
+        for -- with ``N3Tree.save``: ``data`` from the device's values, or with ``quantize=dict(bits=, retain=,
+        sigma_thresh=)`` the median-cut form."""
+        self._stream().synchronize()
+        self.tree.save(path, quantize=quantize, from_device=True)
