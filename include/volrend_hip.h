@@ -255,7 +255,9 @@ int vr_tree_info(vr_tree_t tree, VrTreeInfo* info);
  * what a slot is, as it did at upload: the sigma of an internal slot in data_dev is ignored.  `extra` (SG / ASG
  * lobes) is not part of `data` and is not touched.
  * vr_tree_read_data: writes the tree's current values to data_dev -- the bits of what was uploaded or last
- * written, with the sigma of internal slots as +0.  update(read(tree)) changes nothing.
+ * written, with the sigma of internal slots as +0.  update(read(tree)) changes nothing.  A slot of a node the root does
+ * not reach whose link leaves [1, capacity) is a leaf to the upload (no topology check covers such a link, and it is
+ * never followed): its node word carries the leaf bit, so it reads back its sigma, not +0, and an update writes it.
  * Contract: both calls only enqueue on `stream`, run on the tree's device whatever the calling thread's current
  * device is, and take no launch slot.  The first of them on a tree puts two tables on the device under the
  * tree's mutex -- the 4-bytes-per-node file-order table of vr_accumulate_weights (whose n_frames == 0 call is
@@ -474,7 +476,9 @@ int vr_collapse_apply(const VrCollapse* c, void* stream);
  * vr_tree_geometry, per NODE m of child [capacity * N3]
  *   - parent_slot[m] = the slot s with child[s] != 0 and s / N3 + child[s] == m; -1 for node 0 and for a node no slot
  *     links to.  A link outside [1, capacity) is never followed: there is no out-of-range store.  Contract: child is a
- *     tree vr_tree_upload accepts; a node linked from two slots gets one of them.
+ *     tree vr_tree_upload accepts; a node linked from two slots gets one of them.  vr_tree_upload also accepts files
+ *     in which a node the root does not reach links into the tree: for those files the row of the doubly linked node,
+ *     and the depth and origin of everything below it, are unspecified.
  *   - node_depth[m] = the number of links from node 0 (the root is 0): what VrQueryOut.depth reports for a leaf slot
  *     of m.  -1 for a node whose parent chain does not reach node 0 within VR_GEOM_MAX_DEPTH links.  The walk up the
  *     chain is a counted loop of at most VR_GEOM_MAX_DEPTH steps, whatever the input holds (cycles among unreachable

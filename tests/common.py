@@ -564,11 +564,15 @@ def rows_of(tree):
     return tree.child.reshape(tree.capacity, -1).astype(np.int64)
 
 
-def scrambled(child, seed=7):
+def scrambled(child, seed=7, new_of=None):
     """The construction of tests/test_gpu_chain.py::test_tree_with_backward_links on the child array:
-    the nodes in a random order, root first.  -> (new child array, new index of every old node)."""
+    the nodes in a random order, root first (or in the order ``new_of``, a permutation that keeps node 0).
+    -> (new child array, new index of every old node)."""
     cap = child.shape[0]
-    new_of = np.concatenate([[0], 1 + np.random.default_rng(seed).permutation(cap - 1)])
+    if new_of is None:
+        new_of = np.concatenate([[0], 1 + np.random.default_rng(seed).permutation(cap - 1)])
+    new_of = np.asarray(new_of, np.int64)
+    assert new_of[0] == 0 and np.array_equal(np.sort(new_of), np.arange(cap))
     tgt = np.where(child != 0, np.arange(cap)[:, None] + child, -1)
     out = np.zeros_like(child)
     out[new_of] = np.where(tgt >= 0, new_of[np.maximum(tgt, 0)] - new_of[:, None], 0)
@@ -581,6 +585,94 @@ def with_unreachable(child):
     extra[1, 2] = 1
     extra[3, 0] = -(child.shape[0] + 2)       # -> node 1 of the tree
     return np.concatenate([child, extra])
+
+
+def node_levels(child):
+    """int [capacity]: the number of links from node 0 to each node of a child array [capacity, N^3]; -1 for a node
+    the root does not reach.  A link outside [1, capacity) is not followed."""
+    child = np.asarray(child).astype(np.int64)
+    cap = child.shape[0]
+    level = np.full(cap, -1, np.int64)
+    level[0] = 0
+    front, d = np.array([0]), 0
+    while front.size:
+        tgt = (front[:, None] + child[front])[child[front] != 0]
+        front = tgt[(tgt >= 1) & (tgt < cap)]
+        d += 1
+        assert (level[front] < 0).all(), "not a tree"
+        level[front] = d
+    return level
+
+
+def subtree_sizes(child):
+    """int [capacity]: nodes in the subtree of every node the root reaches (itself included); 0 for the others."""
+    child = np.asarray(child).astype(np.int64)
+    level = node_levels(child)
+    size = (level >= 0).astype(np.int64)
+    for d in range(int(level.max()), 0, -1):
+        n, j = np.nonzero((child != 0) & (level == d - 1)[:, None])
+        np.add.at(size, n, size[n + child[n, j]])
+    return size
+
+
+# The kinds of renumbered(), in the order in which they are applied.
+#   pruned        one internal slot of depth `prune_depth` loses its link: a leaf with the record it holds; its
+#                 subtree (>= 8 nodes) stays in the array with its values, linked among itself, out of the root's reach
+#                 -- a caller who prunes without compacting
+#   random        scrambled()'s order, root first: links forward and backward
+#   reversed      node i >= 1 at capacity - i: every link backward, the general walk's worst order
+#   slack_zero    7 all-zero nodes behind the tree: a file saved with more capacity than it uses
+#   slack_linked  with_unreachable()'s five nodes (one links to the next, one into the tree: node 1 is linked from two
+#                 slots), one of them with a further link outside [1, capacity); all five hold dense, bright records
+#                 (every coefficient 3.0, sigma 200): whatever reaches them changes a pixel, a weight or a gradient
+RENUMBER_KINDS = ("pruned", "random", "reversed", "slack_zero", "slack_linked")
+SLACK_ZERO_NODES = 7
+BRIGHT_COEFF, BRIGHT_SIGMA = 3.0, 200.0
+
+
+def renumbered(tree, kinds, seed=7, prune_depth=2):
+    """``tree`` (a SynthTree) restated as the same scene under another numbering and with nodes the root does not
+    reach: the ``kinds`` of RENUMBER_KINDS, applied in that order whatever order they are given in.  Records move
+    with their nodes; ``extra``, offset and scale are carried along.  -> (tree2, new_of): ``new_of[old node]`` is
+    the node's index in ``tree2`` (the nodes a slack kind appends have no old index)."""
+    kinds = tuple(kinds)
+    assert kinds and all(k in RENUMBER_KINDS for k in kinds) and len(set(kinds)) == len(kinds), kinds
+    cap, N = tree.capacity, tree.N
+    N3, dd = N ** 3, tree.data_dim
+    child = rows_of(tree).copy()
+    data = np.array(tree.data, np.float16).reshape(cap, N3, dd)
+    new_of = np.arange(cap)
+    if "pruned" in kinds:
+        size = subtree_sizes(child)
+        n, j = np.nonzero((child != 0) & (node_levels(child) == prune_depth - 1)[:, None])
+        big = size[n + child[n, j]] >= 8
+        assert big.any(), f"no internal slot of depth {prune_depth} has a subtree of 8 nodes"
+        child[n[big][0], j[big][0]] = 0
+    for kind in ("random", "reversed"):
+        if kind in kinds:
+            order = None if kind == "random" else np.concatenate([[0], cap - np.arange(1, cap)])
+            child, p = scrambled(child, seed, order)
+            moved = np.empty_like(data)
+            moved[p] = data
+            data, new_of = moved, p[new_of]
+    if "slack_zero" in kinds:
+        child = np.concatenate([child, np.zeros((SLACK_ZERO_NODES, N3), np.int64)])
+        data = np.concatenate([data, np.zeros((SLACK_ZERO_NODES, N3, dd), np.float16)])
+    if "slack_linked" in kinds:
+        child = with_unreachable(child)
+        child[-1, N3 - 1] = 9                 # -> capacity + 8: outside the array, never followed
+        bright = np.full((5, N3, dd), BRIGHT_COEFF, np.float16)
+        bright[..., -1] = BRIGHT_SIGMA
+        data = np.concatenate([data, bright])
+    cap2 = child.shape[0]
+    tree2 = dataclasses.replace(tree, child=child.astype(np.int32).reshape(cap2, N, N, N),
+                                data=np.ascontiguousarray(data).reshape(cap2, N, N, N, dd))
+    return tree2, new_of
+
+
+def orphan_nodes(tree):
+    """bool [capacity]: the nodes of a tree that the root does not reach."""
+    return node_levels(rows_of(tree)) < 0
 
 
 # ---- one frame on the GPU against the oracle (torch is handed in) --------------------------------------------------

@@ -174,6 +174,9 @@ def tree_of(name):
         return common.small_scene(depth=7, basis_dim=4, seed=1201), 4.0, None
     if name == "ndc":
         return common.small_scene(depth=5, basis_dim=4, seed=51), 4.0, au.NDC
+    if name.startswith("renum_"):   # a scene of tests/renumber_util.py, pruned, in its own numbering
+        from tests import renumber_util as rn
+        return rn.case(name[6:], ("pruned",))["orig"], 4.0, None
     raise KeyError(name)
 
 

@@ -54,6 +54,11 @@ TREES = {
     "unreachable": lambda: with_unreachable(rows_of(common.small_scene(depth=4))),
     "unreachable_scrambled": lambda: with_unreachable(scrambled(rows_of(common.small_scene(depth=4)))[0]),
     "deep_chain": lambda: rows_of(common.deep_chain_tree_n2(28)[0]),
+    # common.renumbered: every link backward; a subtree cut off in the middle of the array; both, and slack behind
+    "reversed": lambda: rows_of(common.renumbered(common.small_scene(depth=4), ["reversed"])[0]),
+    "pruned": lambda: rows_of(common.renumbered(common.small_scene(depth=5, basis_dim=9, seed=391), ["pruned"])[0]),
+    "pruned_reversed_slack": lambda: rows_of(common.renumbered(common.small_scene(depth=5, basis_dim=9, seed=391),
+                                                               ["pruned", "reversed", "slack_linked"])[0]),
 }
 
 
@@ -210,7 +215,7 @@ def test_plain_numbering_is_preorder(exe, tmp_path, tree):
     check_runs(tree, perm, np.flatnonzero(level != 255))
 
 
-BRICK_TREES = ["scene4", "scrambled", "unreachable_scrambled"]
+BRICK_TREES = ["scene4", "scrambled", "unreachable_scrambled", "reversed", "pruned", "pruned_reversed_slack"]
 # scene4 has node levels 0..3: (3, 2) puts the roots at the deepest level and (1, 4) asks for a level that
 # does not exist, so roots have none or only some of their BL - 1 levels below them; BL = 1: no front
 SHAPES = [(1, 2), (2, 2), (1, 3), (3, 2), (2, 1), (1, 1), (1, 4)]

@@ -114,15 +114,19 @@ def n_bricks(tree, top_levels, brick_levels):
 
 @functools.lru_cache(maxsize=None)
 def variant(name, which):
-    """Data set `which` (1 or 2) of a scene, float16 in the file's shape, read-only: every coefficient seeded
+    """Data set `which` (1 or 2) of a scene (variant_of with the scene's seed), computed once."""
+    return variant_of(case(name)["tree"], which, 1000 * which + sum(map(ord, name)), chain=name == "chain")
+
+
+def variant_of(tree, which, seed, chain=False):
+    """Data set `which` (1 or 2) of a tree, float16 in the file's shape, read-only: every coefficient seeded
     random (those of internal slots too: upload stores them), and sigma by the rank r of a leaf among all leaves
     ordered by depth -- set 1 occupies r % 2 == 0, set 2 occupies (r // 2) % 2 == 0, so that between the two sets
     any four leaves of consecutive rank (so every range of depths that holds four leaves: every kind of
     leaf_kinds) have one that turns on, one that turns off, one that stays on and one that stays off.  Unoccupied
     leaves alternate between 0 and 0.004 (below sigma_thresh, not zero).  Internal slots get a non-zero sigma,
-    which the library must ignore."""
-    tree = case(name)["tree"]
-    rng = np.random.default_rng(1000 * which + sum(map(ord, name)))
+    which the library must ignore; so do the slots of nodes the root does not reach, leaves or not."""
+    rng = np.random.default_rng(seed)
     shape = tree.data.shape
     n3 = tree.N ** 3
     data = (rng.standard_normal(shape) * 0.6).astype(np.float32)
@@ -135,7 +139,7 @@ def variant(name, which):
     rank.reshape(-1)[idx[np.argsort(d.reshape(-1)[idx], kind="stable")]] = np.arange(idx.size)
     occupied = leaf & ((rank % 2 == 0) if which == 1 else ((rank // 2) % 2 == 0))
     dense = np.exp(rng.uniform(np.log(2.0), np.log(60.0), size=d.shape))
-    if name == "chain":   # steps near the target are ~1e-8 long (common.deep_chain_tree_n2)
+    if chain:   # steps near the target are ~1e-8 long (common.deep_chain_tree_n2)
         dense = np.where(d > 14, dense * 1e3, dense)
     sigma = np.where(occupied, dense, np.where(rank % 3 == 0, 0.0, 0.004))
     sigma = np.where(leaf, sigma, 7.0 + which)
@@ -151,9 +155,13 @@ def with_data(tree, data):
 
 
 def stored(tree, data):
-    """What the device holds of `data` (float16, the file's shape): the bits, the sigma of internal slots +0."""
+    """What the device holds of `data` (float16, the file's shape): the bits, the sigma of internal slots +0.  A slot
+    is internal where its link points inside [1, capacity).  The root reaches no other link; a node it does not reach
+    may hold one that leaves the array, and the upload makes a leaf of that slot: it reads back its sigma."""
     out = np.array(data, np.float16, copy=True)
-    out[..., -1][np.asarray(tree.child) != 0] = 0
+    child = np.asarray(tree.child).astype(np.int64)
+    target = np.arange(child.shape[0]).reshape((-1,) + (1,) * (child.ndim - 1)) + child
+    out[..., -1][(child != 0) & (target >= 1) & (target < child.shape[0])] = 0
     return out
 
 

@@ -423,25 +423,30 @@ class N3Tree:
 
 def _parent_depth_host(child) -> np.ndarray:
     """svox's ``parent_depth`` [capacity, 2] from a host child array, for a tree that is not on the device: row m =
-    (the slot that links to node m, the depth of node m), the root's row (0, 0); (-1, -1) for a node nothing
-    reachable links to.  Breadth-first from the root."""
+    (the slot that links to node m, the depth of node m), the root's row (0, 0).  The rule of vr_tree_geometry
+    (include/volrend_hip.h), so that ``save`` writes the same array for a tree on and off the device: the slot is
+    the one whose link, inside [1, capacity), points at m, whether or not the root reaches that slot's node, and -1
+    where there is none; the depth is the number of links up that chain to node 0, and -1 where the chain does not
+    get there within 64 links."""
     cap = child.shape[0]
-    flat = np.ascontiguousarray(child, np.int32).reshape(cap, -1)
-    N3 = flat.shape[1]
-    out = np.full((cap, 2), -1, np.int32)
-    out[0] = 0
-    frontier = np.array([0], np.int64)
-    for depth in range(1, 65):
-        links = flat[frontier]
-        node, j = np.nonzero(links)
-        if node.size == 0:
+    flat = np.ascontiguousarray(child, np.int32).reshape(-1).astype(np.int64)
+    N3 = flat.size // cap
+    s = np.flatnonzero(flat)
+    m = s // N3 + flat[s]
+    ok = (m >= 1) & (m < cap)
+    parent = np.full(cap, -1, np.int64)
+    parent[m[ok]] = s[ok]
+    cur = np.arange(cap)
+    depth = np.zeros(cap, np.int64)
+    for _ in range(64):
+        step = (cur != 0) & (parent[cur] >= 0)
+        if not step.any():
             break
-        target = frontier[node] + links[node, j]
-        ok = (target >= 1) & (target < cap)
-        target, slot = target[ok], (frontier[node] * N3 + j)[ok]
-        fresh = out[target, 1] < 0
-        out[target[fresh], 0], out[target[fresh], 1] = slot[fresh], depth
-        frontier = np.unique(target[fresh])
+        cur = np.where(step, parent[cur] // N3, cur)
+        depth += step
+    depth[cur != 0] = -1
+    out = np.stack([parent, depth], axis=1).astype(np.int32)
+    out[0] = 0
     return out
 
 
